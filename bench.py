@@ -13,10 +13,14 @@ Multi-GPU: one process per GPU (torch.distributed.run); each rank verifies its
 own independent shard -- no data-path collective.  gloo is used
 only for the timing barrier and the max-over-ranks reduction.
 
-Prints ONE JSON line (rank 0).  Extra fields: roofline (integer-VALU bound,
-peak = measured v_mad_u64_u32 rate), cpu_baseline (the oracle C port timed on
-this host's cores), CheckTx small-batch latency (host path, PCIe included),
-and the bitmap parity check of the timed batch against the known verdicts.
+Prints ONE JSON line (rank 0).  A plain run sets up, warms up, times the steps
+and prints the headline fields (value, ms_per_step).  --full adds everything
+else, each in runs of its own: roofline (integer-VALU bound, peak = measured
+v_mad_u64_u32 rate, from a serialized calibration pass), cpu_baseline (the
+oracle C port timed on this host's cores), CheckTx small-batch latency (host
+path, PCIe included), the extras, and the bitmap parity check of the timed
+batch against the known verdicts.  --dump-outputs DIR writes the verdicts of
+the last timed step as DIR/accept.npy.
 """
 from __future__ import annotations
 
@@ -381,6 +385,22 @@ def checktx_latency(ver, pub, sig, dig, threads, sizes=(1, 16, 32, 64, 128, 256,
     return out
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, name, verdicts, share=1):
+    """--dump-outputs: the verdicts (0/1 per signature, what a caller of the
+    timed path receives once the accept bitmap is unpacked) as float32 in
+    DIR/<name>.npy.  At most DUMP_MAX_BYTES over all `share` writers: a larger
+    output is cut to a fixed, seeded sample of its items (in item order)."""
+    v = np.asarray(verdicts)
+    cap = (DUMP_MAX_BYTES // max(1, share) - 4096) // 4
+    if v.size > cap:
+        v = v[np.sort(np.random.default_rng(0xD0).choice(v.size, cap, replace=False))]
+    os.makedirs(dirname, exist_ok=True)
+    np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(v, np.float32))
+
+
 PMC_SUMMARY = os.path.join(os.path.dirname(os.path.abspath(__file__)), "profiles", "pmc_latest.json")
 
 
@@ -397,6 +417,59 @@ def load_pmc(kernel):
         return None
 
 
+def parity_checks(ver, step, rank, n, pub, dig, exp, d_pub, d_dig, d_bits, bits):
+    """--full, after the warm-up: (mismatches, adversarial mismatches, adversarial
+    rejects expected) of the resident batch; the inputs are back in place on return."""
+    # parity of the resident batch against the verdicts known by construction
+    ver.dev_download(bits, d_bits)
+    got = unpack_bits(bits, n)
+    mismatches = int(np.count_nonzero(got != exp))
+
+    # parity on an adversarial copy of the same batch (a kernel that accepted
+    # everything would pass the all-valid check above): 1/8 of the items get a
+    # malformed pubkey prefix (ParsePubKey rejects), 1/8 a flipped digest bit
+    # (ECDSA rejects); expected verdicts by construction
+    rng = np.random.default_rng(0xADF + rank)
+    sel = rng.random(n)
+    bad_pfx, bad_dig = sel < 0.125, (sel >= 0.125) & (sel < 0.25)
+    apub, adig = pub.copy(), dig.copy()
+    apub[bad_pfx, 0] = 0x05
+    adig[bad_dig, 31] ^= 1
+    aexp = exp & ~(bad_pfx | bad_dig)
+    ver.dev_upload(d_pub, apub)
+    ver.dev_upload(d_dig, adig)
+    step()
+    ver.dev_sync()
+    ver.dev_download(bits, d_bits)
+    adv_mismatches = int(np.count_nonzero(unpack_bits(bits, n) != aexp))
+    adv_rejected = int(n - aexp.sum())
+    ver.dev_upload(d_pub, pub)
+    ver.dev_upload(d_dig, dig)
+    return mismatches, adv_mismatches, adv_rejected
+
+
+def headline(args, world, n, elapsed_max):
+    """The result line of a plain run; --full adds its fields to it."""
+    return {
+        "metric": "secp256k1 verifies/sec at 1/2/4/8 MI355X; p50 latency @64-tx CheckTx batch",
+        "value": round(world * n * args.steps / elapsed_max, 1),
+        "unit": "verifies/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(elapsed_max / args.steps * 1e3, 3),
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "u32",
+        "data": "synthetic: OpenSSL-signed low-S ECDSA over random SHA-256 digests, 65,536 keys round-robin",
+        "config": {"workload": "C2: 1M random secp256k1 sigs over 32-byte sha256 digests per GPU "
+                               "(bit-exact bitmap vs btcec semantics)",
+                   "items_per_gpu": n, "keys": args.keys, "adversarial_fraction": args.adversarial,
+                   "global_batch": n * world, "parallelism": f"shard{world} (independent per-GPU shards, no collective)"},
+    }
+
+
 def main(argv=None, verifier_factory=None, workload_fn=None):
     """verifier_factory(local_rank) / workload_fn(n, seed, keys, adv, threads) are
     injection points for tests/test_bench_dist.py (gloo, CPU, fake verifier)."""
@@ -410,13 +483,23 @@ def main(argv=None, verifier_factory=None, workload_fn=None):
     ap.add_argument("--threads", type=int, default=host_cores()["effective"] or 1,
                     help="CPU baseline / workload threads (default: every CPU this process may run on: the "
                          "affinity mask, capped by the cgroup CPU quota when one is set)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-latency", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the C3 / message-path / C1 / C4 lines")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: parity of the timed batch and of an adversarial copy, the per-kernel "
+                         "roofline (a serialized calibration pass, the live ALU peak), the CPU baseline, the CheckTx "
+                         "latency curve and the extras; a plain run times the steps and prints the headline fields")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the verdicts of the last timed step (float32, one per signature; a seeded sample "
+                         "above 64 MB) to DIR/accept.npy (rank r > 0: DIR/accept_rank<r>.npy)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-latency", action="store_true", help="with --full: skip the CheckTx latency curve")
+    ap.add_argument("--no-extras", action="store_true",
+                    help="with --full: skip the C3 / message-path / C1 / C4 lines")
     ap.add_argument("--inproc", action="store_true",
                     help="the node's shape: ONE process, one gv_open over --gpus devices (0 = every visible one), "
                          "gv_verify_digests_bits from host buffers of items x devices signatures; per-device rates")
     args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.inproc:
         return run_inproc(args, verifier_factory, workload_fn)
 
@@ -464,34 +547,13 @@ def main(argv=None, verifier_factory=None, workload_fn=None):
         step()
     ver.dev_sync()
 
-    # parity of the resident batch against the verdicts known by construction
     bits = np.zeros(nwords, np.uint64)
-    ver.dev_download(bits, d_bits)
-    got = unpack_bits(bits, n)
-    mismatches = int(np.count_nonzero(got != exp))
+    if args.full:
+        mismatches, adv_mismatches, adv_rejected = parity_checks(ver, step, rank, n, pub, dig, exp,
+                                                                 d_pub, d_dig, d_bits, bits)
 
-    # parity on an adversarial copy of the same batch (a kernel that accepted
-    # everything would pass the all-valid check above): 1/8 of the items get a
-    # malformed pubkey prefix (ParsePubKey rejects), 1/8 a flipped digest bit
-    # (ECDSA rejects); expected verdicts by construction
-    rng = np.random.default_rng(0xADF + rank)
-    sel = rng.random(n)
-    bad_pfx, bad_dig = sel < 0.125, (sel >= 0.125) & (sel < 0.25)
-    apub, adig = pub.copy(), dig.copy()
-    apub[bad_pfx, 0] = 0x05
-    adig[bad_dig, 31] ^= 1
-    aexp = exp & ~(bad_pfx | bad_dig)
-    ver.dev_upload(d_pub, apub)
-    ver.dev_upload(d_dig, adig)
-    step()
-    ver.dev_sync()
-    ver.dev_download(bits, d_bits)
-    adv_mismatches = int(np.count_nonzero(unpack_bits(bits, n) != aexp))
-    adv_rejected = int(n - aexp.sum())
-    ver.dev_upload(d_pub, pub)
-    ver.dev_upload(d_dig, dig)
-    del apub, adig
-
+    # kernel events stay on in a plain run too: the timed region is the same
+    # measurement with and without --full
     ver.set_option("time_kernels", 1)
     ver.stage_stats4()                    # reset the event ring
     barrier()
@@ -503,6 +565,20 @@ def main(argv=None, verifier_factory=None, workload_fn=None):
     barrier()
     elapsed = time.perf_counter() - t_start
     cnt_p, pipe_stages = ver.stage_stats4()
+    if args.dump_outputs:
+        ver.dev_download(bits, d_bits)
+        dump_outputs(args.dump_outputs, "accept" if rank == 0 else f"accept_rank{rank}", unpack_bits(bits, n), world)
+    if not args.full:
+        ver.set_option("time_kernels", 0)
+        for p in (d_pub, d_sig, d_dig, d_bits):
+            ver.dev_free(p)
+        ver.close()
+        elapsed_max = allmax(elapsed)
+        if rank == 0:
+            print(json.dumps(headline(args, world, n, elapsed_max)), flush=True)
+        if dist is not None:
+            dist.destroy_process_group()
+        return
     grp0 = ver.group_stats() if hasattr(ver, "group_stats") else (0, 0)
     routes0 = ver.route_stats() if hasattr(ver, "route_stats") else {}
     # The timed loop is pipelined (gv_set_option "pipeline_dev": call k+1's
@@ -563,23 +639,8 @@ def main(argv=None, verifier_factory=None, workload_fn=None):
     achieved = n * w[ladder] / (ecmult_ms * 1e-3) if ecmult_ms > 0 else 0.0
     pmc = load_pmc(ladder)
     traffic = round(pmc["hbm_bytes_per_item"] * n) if pmc else None
-    result = {
-        "metric": "secp256k1 verifies/sec at 1/2/4/8 MI355X; p50 latency @64-tx CheckTx batch",
-        "value": round(value, 1),
-        "unit": "verifies/s",
-        "n_gpus": world,
-        "steps": args.steps,
-        "warmup": args.warmup,
-        "ms_per_step": round(ms_per_step, 3),
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "u32",
-        "data": "synthetic: OpenSSL-signed low-S ECDSA over random SHA-256 digests, 65,536 keys round-robin",
-        "config": {"workload": "C2: 1M random secp256k1 sigs over 32-byte sha256 digests per GPU "
-                               "(bit-exact bitmap vs btcec semantics)",
-                   "items_per_gpu": n, "keys": args.keys, "adversarial_fraction": args.adversarial,
-                   "global_batch": n * world, "parallelism": f"shard{world} (independent per-GPU shards, no collective)",
+    result = headline(args, world, n, elapsed_max)
+    result["config"].update({
                    "route": ("in-batch key grouping: each distinct key parsed and tabulated once (k_dedupe, "
                              "k_keys_chain + k_keys_tables), items on the keyed "
                              + (f"{5 * (kg_layout(kg)[0] - 1)}-doubling ladder k_ecmult_kn<5, {kg}> ({kg} groups of "
@@ -590,7 +651,8 @@ def main(argv=None, verifier_factory=None, workload_fn=None):
                                 else "k_ecmult_k4 (G on the unsplit scalar: 11 25-bit windows)" if k4f
                                 else "k_ecmult_k4 (GLV G: 14 20-bit windows)")
                              if grouped else "per-item pub33 pipeline (every item decompresses its key)"),
-                   "distinct_keys_per_batch": round(u_keys) if grouped else None},
+                   "distinct_keys_per_batch": round(u_keys) if grouped else None})
+    result.update({
         "roofline": {
             "bound": "valu",
             "kernel": ladder,
@@ -633,7 +695,7 @@ def main(argv=None, verifier_factory=None, workload_fn=None):
                    "adversarial_mismatches": total_adv_mismatch,
                    "reference": "verdicts known by construction: the timed batch (valid signatures) and an "
                                 "adversarial copy (1/8 malformed prefix, 1/8 flipped digest bit -> rejected)"},
-    }
+    })
 
     lat = None
     if rank == 0 and world == 1 and not args.no_latency:
@@ -743,8 +805,10 @@ def run_inproc(args, verifier_factory=None, workload_fn=None):
     mismatches = int(np.count_nonzero(unpack_bits(bits, n) != exp))
     t = time.perf_counter()
     for _ in range(args.steps):
-        ver.verify_batch_digests_bits(pub, sig, dig)
+        bits = ver.verify_batch_digests_bits(pub, sig, dig)
     elapsed = time.perf_counter() - t
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, "accept", unpack_bits(bits, n))
     slices = ver.last_slices()
     ver.close()
     value = n * args.steps / elapsed

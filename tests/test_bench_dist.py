@@ -27,7 +27,7 @@ def test_two_rank_bench_aggregation():
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()),
            os.path.join(REPO, "tests", "dist_bench_worker.py"),
            "--gpus", "2", "--steps", str(steps), "--warmup", "1", "--items", str(n),
-           "--no-cpu-baseline", "--no-latency", "--no-extras"]
+           "--full", "--no-cpu-baseline", "--no-latency", "--no-extras"]
     env = dict(os.environ, OMP_NUM_THREADS="1")
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=300, env=env, cwd=REPO)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -44,6 +44,57 @@ def test_two_rank_bench_aggregation():
     assert par["adversarial_checked"] == 2 * n and par["adversarial_mismatches"] == 0
     assert 0.2 * 2 * n < par["adversarial_rejects_expected"] < 0.5 * 2 * n
     assert set(out["roofline"]["kernels"]) == {"k_scalar_inv", "k_prep", "k_ecmult"}
+
+
+def test_plain_run_is_lean_and_dumps_the_timed_verdicts(tmp_path, capsys):
+    """Without --full: the headline fields only, exactly --steps timed calls after
+    --warmup, no parity / calibration passes; --dump-outputs writes the last timed
+    step's verdicts as float32, the same from run to run."""
+    sys.path.insert(0, os.path.join(REPO, "tests"))
+    import bench
+    import dist_bench_worker as W
+    n, steps, warmup = 1000, 3, 2
+    calls = []
+
+    class Counting(W.FakeVerifier):
+        def dev_verify_digests(self, *a, **k):
+            calls.append(1)
+            super().dev_verify_digests(*a, **k)
+
+    dumps = []
+    for d in ("a", "b"):
+        del calls[:]
+        bench.main(["--gpus", "1", "--steps", str(steps), "--warmup", str(warmup), "--items", str(n),
+                    "--dump-outputs", str(tmp_path / d)], verifier_factory=Counting, workload_fn=W.workload)
+        assert len(calls) == steps + warmup
+        lines = [l for l in capsys.readouterr().out.splitlines() if l.startswith("{")]
+        assert len(lines) == 1
+        out = json.loads(lines[0])
+        assert {"metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"} <= set(out)
+        assert out["steps"] == steps and out["ms_per_step"] >= 10.0      # the fake's 10 ms per call
+        assert abs(out["value"] - n / (out["ms_per_step"] * 1e-3)) / out["value"] < 0.01
+        assert not {"parity", "roofline", "pipeline", "cpu_baseline", "extras", "checktx_latency_ms"} & set(out)
+        assert os.listdir(tmp_path / d) == ["accept.npy"]
+        dumps.append(np.load(tmp_path / d / "accept.npy"))
+    assert dumps[0].dtype == np.float32 and dumps[0].shape == (n,)
+    assert np.array_equal(dumps[0], W.workload(n, 0xC2, 65536, 0.0, 1)[3])
+    assert np.array_equal(dumps[0], dumps[1])
+
+
+def test_dump_outputs_caps_the_file_with_a_fixed_sample(tmp_path):
+    import bench
+    v = (np.arange(5000) % 3 == 0).astype(np.uint8)
+    old = bench.DUMP_MAX_BYTES
+    bench.DUMP_MAX_BYTES = 8192
+    try:
+        bench.dump_outputs(str(tmp_path), "x", v)
+        bench.dump_outputs(str(tmp_path), "y", v)
+    finally:
+        bench.DUMP_MAX_BYTES = old
+    x = np.load(tmp_path / "x.npy")
+    assert x.dtype == np.float32 and 0 < x.size < v.size
+    assert os.path.getsize(tmp_path / "x.npy") <= 8192
+    assert np.array_equal(x, np.load(tmp_path / "y.npy"))
 
 
 class _FakeMultiDevice:

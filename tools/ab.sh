@@ -8,7 +8,7 @@ mkdir -p "$OUT"
 for rep in 1 2; do
   for lib in "$@"; do
     name=$(basename "$lib" .so)
-    GV_LIB="$lib" timeout -k 10 300 python bench.py --steps 5 --warmup 2 --no-extras --no-cpu-baseline \
+    GV_LIB="$lib" timeout -k 10 300 python bench.py --full --steps 5 --warmup 2 --no-extras --no-cpu-baseline \
       > "$OUT/${name}_$rep.json" 2> "$OUT/${name}_$rep.err" || { echo "bench $name failed"; tail -20 "$OUT/${name}_$rep.err"; exit 1; }
     python3 -c "import json,sys; b=json.load(open('$OUT/${name}_$rep.json')); print('$name', $rep, round(b['value']/1e6,2), 'M/s', b['pipeline'], 'p50@64', b['checktx_p50_ms_64'])"
   done

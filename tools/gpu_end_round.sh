@@ -13,10 +13,10 @@ WHAT=${2:-bench}
 ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 cd "$ROOT" && mkdir -p "$OUT"
 if [ "$WHAT" = bench ]; then
-  timeout -k 10 900 python -u bench.py > "$OUT/bench.json" 2> "$OUT/bench.err" || { tail -30 "$OUT/bench.err"; exit 1; }
+  timeout -k 10 900 python -u bench.py --full > "$OUT/bench.json" 2> "$OUT/bench.err" || { tail -30 "$OUT/bench.err"; exit 1; }
   tail -c 400 "$OUT/bench.json"
   ( cd /tmp && export TMPDIR=/tmp && timeout -k 10 240 rocprofv3 --kernel-trace --stats -d "$ROOT/$OUT/prof" -o run \
-      --output-format csv -- python3 "$ROOT/bench.py" --steps 10 --warmup 3 --no-cpu-baseline --no-latency --no-extras \
+      --output-format csv -- python3 "$ROOT/bench.py" --full --steps 10 --warmup 3 --no-cpu-baseline --no-latency --no-extras \
       > "$ROOT/$OUT/bench_prof.json" 2> "$ROOT/$OUT/bench_prof.err" ) || { tail -30 "$OUT/bench_prof.err"; exit 1; }
   python3 tools/prof_timed.py "$OUT/prof/run_kernel_trace.csv" 10 "$OUT/prof/kernel_timed.csv" > "$OUT/prof/timed.txt"
   head -12 "$OUT/prof/timed.txt"

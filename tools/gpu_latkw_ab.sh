@@ -8,7 +8,7 @@ timeout -k 10 600 python3 -u -m pytest -x -v --timeout 300 --timeout-method thre
 tail -2 $O/tests.log
 for i in 1 2; do
   for v in 1 0; do
-    GV_LAT_KW=$v timeout -k 10 300 python3 bench.py --steps 5 --warmup 2 --no-extras --no-cpu-baseline > $O/b_${v}_$i.json 2> $O/b_${v}_$i.err || { tail -20 $O/b_${v}_$i.err; exit 1; }
+    GV_LAT_KW=$v timeout -k 10 300 python3 bench.py --full --steps 5 --warmup 2 --no-extras --no-cpu-baseline > $O/b_${v}_$i.json 2> $O/b_${v}_$i.err || { tail -20 $O/b_${v}_$i.err; exit 1; }
     python3 -c "import json; d=json.load(open('$O/b_${v}_$i.json')); print('lat_kw $v rep $i', {k: v.get('keyed_p50_ms') for k, v in d['checktx_latency_ms'].items()})"
   done
 done

@@ -10,7 +10,7 @@ ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 mkdir -p "$ROOT/$OUT"
 cd /tmp && export TMPDIR=/tmp
 rocprofv3 -L > "$ROOT/$OUT/counters_list.txt" 2>&1 || true
-BENCH=("$ROOT/bench.py" --steps 2 --warmup 1 --no-cpu-baseline --no-latency --no-extras --items "$N")
+BENCH=("$ROOT/bench.py" --full --steps 2 --warmup 1 --no-cpu-baseline --no-latency --no-extras --items "$N")
 if [ "${MODE:-secp}" = ed ]; then BENCH=("$ROOT/tools/ed_probe.py" "$N" 16); fi   # ed25519 kernels
 if [ "${MODE:-secp}" = item ]; then BENCH+=(--keys "$N"); fi                           # per-item route: every key distinct
 if [ "${MODE:-secp}" = kw ]; then BENCH=("$ROOT/tools/kw_pmc_probe.py"); fi          # the resident arena's wide-window ladder
