@@ -82,12 +82,14 @@ typedef struct gvk_batch {
   // (GV_K6_GTAB_WORDS: the full-scalar 24-bit-window G tables); gtab4 unused
   const uint32_t* gtab6;
   int k6;
-  // kqw == 1 (with k6 == GV_KW_NG1 or GV_KW_NG2): kqt / kqt2 / kzq are the
-  // resident arena's wide-window tables (GV_KW_NT entries per group) and the
-  // ladder is k_ecmult_kn<GV_KW_QW, k6>.  kqw == 2: the grouped route's
+  // kqw == 1: kqt / kqt2 / kzq are the resident arena's wide-window tables of
+  // width kwq (GV_KW_QW, or GV_KWN_QW: the narrow set; 2^(kwq-1) entries per
+  // group) in k6 groups (one or two windows per group: gvk_kw_ng) and the
+  // ladder is k_ecmult_kn<kwq, k6>.  kqw == 2: the grouped route's
   // 5-bit many-group tables (GV_QTAB_N entries, k6 groups, one of GV_KG_NGS):
   // k_ecmult_kn<GV_QW, k6>
   int kqw;
+  int kwq;
   // k4 batches with gtabf set: the G half on the unsplit scalar (GV_GF_*),
   // k_prep<.., GF> digits and k_ecmult_k4<true> over gtabf (GV_GF_WORDS)
   const uint32_t* gtabf;
@@ -166,7 +168,8 @@ static_assert(GV_K6_QW * GV_K6_QWIN >= 130 && GV_K6_GW * GV_K6_GWIN >= 257, "k6 
 // and no doublings (768 KiB of tables per key), or 6 groups and 11 doublings
 // (384 KiB).  G as on the k6 ladders (11 24-bit windows after the last
 // doubling, gtab6).  Built at gv_keys_load beside the k6 tables while the key
-// set fits (kw2, then kn on the k6 tables otherwise).  A/B on one box,
+// set fits (kw2, then the narrow set GV_KWN_* below, then kn on the k6 tables
+// otherwise).  A/B on one box,
 // c2_key_cache (65,536 keys), one window per group: QW 7 / 8 / 9 =
 // 329-344 / 366 / 380-381M/s (round 5, profiles/r05/kw/); round 6
 // (profiles/r06/ab/kqw/): QW 9 / 10 / 11 / 12 = 421-430 / 452-467 / 482-488 /
@@ -190,6 +193,37 @@ static_assert(GV_K6_QW * GV_K6_QWIN >= 130 && GV_K6_GW * GV_K6_GWIN >= 257, "k6 
 static_assert(GV_KW_QW >= 7 && GV_KW_QW <= 12 && GV_KW_NG1 <= 19, "wide arena layout");
 static_assert(GV_KW_QWIN + GV_K6_GWIN <= GV_DIGIT_ROWS, "wide-window digits fit the digit rows");
 static_assert(GV_KW_QW * GV_KW_QWIN >= 130, "wide windows cover the GLV halves");
+// The narrow wide-window set beside it (GV_KWN_*, k_ecmult_kn<GV_KWN_QW, NG>):
+// the same entry format, ladder and G half at a smaller window width, for key
+// sets the GV_KW_QW-bit arena no longer holds -- gv_keys_load picks the layout
+// (gv_runtime.cpp).  QW = 9 (default): 256 entries, 15 windows, 30 Q
+// additions; 15 groups and no doublings (240 KiB of tables per key) or 8
+// groups and 9 doublings (128 KiB).  Compiled only below GV_KW_QW, so an A/B
+// build with another GV_KW_QW keeps compiling (GV_KWN 0: one width).
+#ifndef GV_KWN_QW
+#define GV_KWN_QW 9
+#endif
+#define GV_KWN (GV_KWN_QW < GV_KW_QW)
+#define GV_KWN_NT (1 << (GV_KWN_QW - 1))                  // 256 table entries per group
+#define GV_KWN_QWIN ((130 + GV_KWN_QW - 1) / GV_KWN_QW)   // 15 windows per GLV half
+#define GV_KWN_KEY_WORDS (GV_KWN_NT * GV_KW_ENT_WORDS)   // one group table (16,384 B)
+#define GV_KWN_NG1 GV_KWN_QWIN                            // one window per group: 15 groups
+#define GV_KWN_NG2 ((GV_KWN_QWIN + 1) / 2)                // two windows per group: 8 groups
+#if GV_KWN
+static_assert(GV_KWN_QW >= 7 && GV_KWN_NG1 <= 19, "narrow wide arena layout");
+static_assert(GV_KWN_QWIN + GV_K6_GWIN <= GV_DIGIT_ROWS, "narrow wide-window digits fit the digit rows");
+static_assert(GV_KWN_QW * GV_KWN_QWIN >= 130, "narrow wide windows cover the GLV halves");
+#endif
+// The wide-format widths of this build and their layouts: entries per group,
+// group-table words, groups with wpg (1 or 2) windows per group.
+inline int gvk_kw_width_ok(int qw) { return qw == GV_KW_QW || (GV_KWN && qw == GV_KWN_QW); }
+inline int gvk_kw_nt(int qw) { return 1 << (qw - 1); }
+inline size_t gvk_kw_key_words(int qw) { return (size_t)gvk_kw_nt(qw) * GV_KW_ENT_WORDS; }
+inline int gvk_kw_ng(int qw, int wpg) {
+  if (qw <= 0) return 0;
+  const int qwin = (130 + qw - 1) / qw;
+  return wpg == 1 ? qwin : (qwin + 1) / 2;
+}
 
 // The grouped route's many-group ladder (option "kg", k_ecmult_kn<GV_QW, NG>,
 // round 6): the in-batch key tables keep k4's 16-entry 5-bit windows (26 per
@@ -348,13 +382,14 @@ hipError_t gvk_keys_build6(const uint8_t* pub33, uint32_t n, uint32_t C, uint32_
                            uint32_t* in_r, uint32_t* in_s, uint32_t* in_e, uint32_t* scratch, int with_qe,
                            uint32_t base, uint32_t* kqt6, uint32_t* kzq6, uint32_t kC, uint32_t* kok, uint32_t* kqt62,
                            uint32_t* kzq62, hipStream_t st);
-// The resident arena's wide-window tables (ng = GV_KW_NG1 or GV_KW_NG2 groups
-// of GV_KW_NT entries), same arguments as gvk_keys_build6 (kqtw:
-// GV_KW_KEY_WORDS per slot, kqtw2: ng - 1 rows per slot, kzqw2: (ng - 1) x 8 rows).
+// The resident arena's wide-window tables of width qw (GV_KW_QW or GV_KWN_QW)
+// in ng = gvk_kw_ng(qw, 1 or 2) groups of gvk_kw_nt(qw) entries, same
+// arguments as gvk_keys_build6 (kqtw: gvk_kw_key_words(qw) per slot, kqtw2:
+// ng - 1 rows per slot, kzqw2: (ng - 1) x 8 rows).
 hipError_t gvk_keys_build_wide(const uint8_t* pub33, uint32_t n, uint32_t C, uint32_t* in_x, uint32_t* in_pfx,
                            uint32_t* in_r, uint32_t* in_s, uint32_t* in_e, uint32_t* scratch, int with_qe,
                            uint32_t base, uint32_t* kqtw, uint32_t* kzqw, uint32_t kC, uint32_t* kok, uint32_t* kqtw2,
-                           uint32_t* kzqw2, int ng, hipStream_t st);
+                           uint32_t* kzqw2, int qw, int ng, hipStream_t st);
 // the full-scalar G tables (GV_GF_WORDS words); base_scratch: 96 words
 hipError_t gvk_gen_gtablef(uint32_t* gtabf, uint32_t* base_scratch, hipStream_t st);
 // Key-table builds (k_keys_chain + k_keys_fwd + k_keys_back): scratch of

@@ -637,6 +637,17 @@ GV_DEV bool parse_pubkey(u32 pre, const fe& x, fe& y) {
 // KEYED = true: the item's key is slot kslot[g] of the key arena (gv_keys_load:
 // parsed once, table resident); an out-of-range slot or a rejected key makes
 // the item false.  qidx[g] receives the (clamped) slot for k_ecmult.
+// A Q window width whose key tables are in the wide format (gv_kernels.h
+// GV_KW_*: GV_KW_ENT_WORDS canonical words per entry, ceil(130 / QW) windows
+// per GLV half): the resident arena's GV_KW_QW and, where compiled, the
+// narrow set's GV_KWN_QW.
+template <int QW>
+struct KWide {
+  static constexpr bool value = QW == GV_KW_QW || (GV_KWN && QW == GV_KWN_QW);
+  static constexpr int QWIN = value ? (130 + QW - 1) / QW : 0;
+};
+static_assert(!KWide<GV_QW>::value && !KWide<GV_K6_QW>::value, "the wide widths are not the 5- / 6-bit ladders'");
+
 // GV_PREP_WAVES: minimum waves per SIMD for k_prep (0 = compiler's choice; A/B)
 #ifndef GV_PREP_WAVES
 #define GV_PREP_WAVES 0
@@ -650,11 +661,12 @@ GV_DEV bool parse_pubkey(u32 pre, const fe& x, fe& y) {
 // GV_K6_GW-bit G windows) instead of GV_QW / GV_GW.
 // GF (keyed k4 only): G digits of the unsplit u1 (GV_GF_WIN signed
 // GV_GF_W-bit windows, one int32 row each: digits[(GV_QWIN + j)*C + g]).
-// KW (with K6, GF): GV_KW_QW-bit Q windows (the resident arena's wide-window
-// tables), G as K6.
+// KWQ (with K6, GF; 0: none): KWQ-bit Q windows over ceil(130 / KWQ) rows (the
+// resident arena's wide-window tables: GV_KW_QW, or GV_KWN_QW for the narrow
+// set), G as K6.
 // KG (with K6, GF): GV_QW-bit Q windows (the grouped route's many-group
 // tables, option "kg"), G as K6.
-template <bool KEYED, bool K6 = false, bool GF = false, bool KW = false, bool KG = false>
+template <bool KEYED, bool K6 = false, bool GF = false, int KWQ = 0, bool KG = false>
 __global__ __launch_bounds__(256) GV_PREP_ATTR void k_prep(u32 C, u32 n, const u32* in_x, const u32* in_pfx,
                                                const u32* in_r, const u32* in_s, const u32* in_e,
                                                const u32* in_w, u32* digits, u32* qt, u32* zq_out,
@@ -730,10 +742,10 @@ __global__ __launch_bounds__(256) GV_PREP_ATTR void k_prep(u32 C, u32 n, const u
   // [-2^(GV_GW-1), 2^(GV_GW-1)]) as int32: digits[(GV_QWIN + 2j)*C + g] = dG1,
   // digits[(GV_QWIN + 2j + 1)*C + g] = dG2, j = 0..GV_GWIN-1.
   static_assert(GF || !K6, "the k6 ladder takes G on the unsplit scalar");
-  static_assert(!KW || K6, "wide-window digits: the k6 ladder's G windows");
-  static_assert(!KG || (K6 && !KW), "kg digits: 5-bit Q windows, the k6 ladder's G windows");
-  constexpr int QW = KW ? GV_KW_QW : KG ? GV_QW : K6 ? GV_K6_QW : GV_QW;
-  constexpr int QWIN = KW ? GV_KW_QWIN : KG ? GV_QWIN : K6 ? GV_K6_QWIN : GV_QWIN;
+  static_assert(!KWQ || (K6 && KWide<KWQ>::value), "wide-window digits: a wide width, the k6 ladder's G windows");
+  static_assert(!KG || (K6 && !KWQ), "kg digits: 5-bit Q windows, the k6 ladder's G windows");
+  constexpr int QW = KWQ ? KWQ : KG ? GV_QW : K6 ? GV_K6_QW : GV_QW;
+  constexpr int QWIN = KWQ ? KWide<KWQ>::QWIN : KG ? GV_QWIN : K6 ? GV_K6_QWIN : GV_QWIN;
   constexpr int GW = GV_GW, GWIN = GV_GWIN;
   constexpr int GFW = K6 ? GV_K6_GW : GV_GF_W, GFWIN = K6 ? GV_K6_GWIN : GV_GF_WIN;
 #pragma unroll
@@ -784,12 +796,13 @@ __constant__ const int kLGrpBit[GV_LGRP] = {0, 35, 70, 100};
 // w0(k), i.e. its table is that of 2^(QW w0(k)) Q; the ladder runs P
 // positions.  <5, 4>: k_ecmult_k4 (groups at bits 0, 35, 70, 100); <6, 4>:
 // the grouped route's k6 (0, 36, 72, 102); <6, GV_KN_ARENA_NG> and
-// <GV_KW_QW, GV_KW_NG1 / GV_KW_NG2>: the resident arena's table sets.
+// <GV_KW_QW, GV_KW_NG1 / GV_KW_NG2> and <GV_KWN_QW, GV_KWN_NG1 / GV_KWN_NG2>:
+// the resident arena's table sets.
 template <int QW, int NG>
 struct KLayout {
-  static constexpr int QWIN = QW == GV_QW ? GV_QWIN : QW == GV_KW_QW ? GV_KW_QWIN : GV_K6_QWIN;
+  static constexpr int QWIN = QW == GV_QW ? GV_QWIN : KWide<QW>::value ? KWide<QW>::QWIN : GV_K6_QWIN;
   static constexpr int NT = 1 << (QW - 1);                  // table entries per group
-  static constexpr int EW = QW == GV_KW_QW ? GV_KW_ENT_WORDS : GV_QENT_WORDS;   // words per entry
+  static constexpr int EW = KWide<QW>::value ? GV_KW_ENT_WORDS : GV_QENT_WORDS;   // words per entry
   static constexpr int P = (QWIN + NG - 1) / NG;            // ladder positions
   static constexpr int R = QWIN - (P - 1) * NG;             // groups with P windows
   static constexpr int nw(int k) { return k < R ? P : P - 1; }
@@ -805,6 +818,11 @@ static_assert(KLayout<6, GV_KN_ARENA_NG>::w0(GV_KN_ARENA_NG - 1) + KLayout<6, GV
 static_assert(KLayout<GV_KW_QW, GV_KW_NG2>::w0(GV_KW_NG2 - 1) + KLayout<GV_KW_QW, GV_KW_NG2>::nw(GV_KW_NG2 - 1) ==
                       GV_KW_QWIN && KLayout<GV_KW_QW, GV_KW_NG2>::P == 2 && KLayout<GV_KW_QW, GV_KW_NG1>::P == 1,
               "wide arena groups cover the windows");
+#if GV_KWN
+static_assert(KLayout<GV_KWN_QW, GV_KWN_NG2>::w0(GV_KWN_NG2 - 1) + KLayout<GV_KWN_QW, GV_KWN_NG2>::nw(GV_KWN_NG2 - 1) ==
+                      GV_KWN_QWIN && KLayout<GV_KWN_QW, GV_KWN_NG2>::P == 2 && KLayout<GV_KWN_QW, GV_KWN_NG1>::P == 1,
+              "narrow wide arena groups cover the windows");
+#endif
 
 // Affine x, y (8 x 32 words) of a finite Jacobian point.
 GV_DEV void gej29_to_affine_words(fe& x8, fe& y8, const gej29& p) {
@@ -1801,6 +1819,8 @@ __global__ __launch_bounds__(256) GV_ECMULT_ATTR void k_ecmult_k4(const u32* gta
 // QW = GV_KW_QW (the arena's wide-window tables, GV_KW_*: 11 by default): 12
 // eleven-bit windows per GLV half, in 12 groups (one position, no doublings)
 // or 6 (two positions, 11 doublings), 1,024-entry tables, 24 Q additions.
+// QW = GV_KWN_QW (the narrow set, GV_KWN_*: 9 by default): 15 nine-bit windows
+// in 15 groups or 8 (9 doublings), 256-entry tables, 30 Q additions.
 // The group layout as constant tables (row 0: NG = 4, row 1: the arena's NG,
 // row 2: the wide arena's NG) -- indexing them keeps the ladder's register
 // allocation at that of k4
@@ -1809,8 +1829,9 @@ __global__ __launch_bounds__(256) GV_ECMULT_ATTR void k_ecmult_k4(const u32* gta
     KLayout<QW, NG>::F(7), KLayout<QW, NG>::F(8), KLayout<QW, NG>::F(9), KLayout<QW, NG>::F(10), \
     KLayout<QW, NG>::F(11), KLayout<QW, NG>::F(12), KLayout<QW, NG>::F(13), KLayout<QW, NG>::F(14), \
     KLayout<QW, NG>::F(15), KLayout<QW, NG>::F(16), KLayout<QW, NG>::F(17), KLayout<QW, NG>::F(18)
-// rows 4.. : the grouped route's 5-bit many-group layouts (GV_KG_NGS)
-__constant__ const int kKnW0[8][19] = {
+// rows 4..7: the grouped route's 5-bit many-group layouts (GV_KG_NGS); rows
+// 8, 9: the narrow wide-window set's two layouts
+__constant__ const int kKnW0[8 + 2 * GV_KWN][19] = {
     {GV_KN_ROW(6, 4, w0)},
     {GV_KN_ROW(6, GV_KN_ARENA_NG, w0)},
     {GV_KN_ROW(GV_KW_QW, GV_KW_NG2, w0)},
@@ -1818,8 +1839,13 @@ __constant__ const int kKnW0[8][19] = {
     {GV_KN_ROW(GV_QW, 6, w0)},
     {GV_KN_ROW(GV_QW, 7, w0)},
     {GV_KN_ROW(GV_QW, 9, w0)},
-    {GV_KN_ROW(GV_QW, 4, w0)}};
-__constant__ const int kKnNW[8][19] = {
+    {GV_KN_ROW(GV_QW, 4, w0)},
+#if GV_KWN
+    {GV_KN_ROW(GV_KWN_QW, GV_KWN_NG2, w0)},
+    {GV_KN_ROW(GV_KWN_QW, GV_KWN_NG1, w0)},
+#endif
+};
+__constant__ const int kKnNW[8 + 2 * GV_KWN][19] = {
     {GV_KN_ROW(6, 4, nw)},
     {GV_KN_ROW(6, GV_KN_ARENA_NG, nw)},
     {GV_KN_ROW(GV_KW_QW, GV_KW_NG2, nw)},
@@ -1827,9 +1853,14 @@ __constant__ const int kKnNW[8][19] = {
     {GV_KN_ROW(GV_QW, 6, nw)},
     {GV_KN_ROW(GV_QW, 7, nw)},
     {GV_KN_ROW(GV_QW, 9, nw)},
-    {GV_KN_ROW(GV_QW, 4, nw)}};
+    {GV_KN_ROW(GV_QW, 4, nw)},
+#if GV_KWN
+    {GV_KN_ROW(GV_KWN_QW, GV_KWN_NG2, nw)},
+    {GV_KN_ROW(GV_KWN_QW, GV_KWN_NG1, nw)},
+#endif
+};
 #undef GV_KN_ROW
-static_assert(GV_KN_ARENA_NG <= 16 && GV_KW_NG1 <= 19, "layout table rows");
+static_assert(GV_KN_ARENA_NG <= 16 && GV_KW_NG1 <= 19 && (!GV_KWN || GV_KWN_NG1 <= 19), "layout table rows");
 
 constexpr int kn_row(int qw, int ng) {
   return qw == 6 && ng == 4                    ? 0
@@ -1840,6 +1871,8 @@ constexpr int kn_row(int qw, int ng) {
          : qw == GV_QW && ng == 7              ? 5
          : qw == GV_QW && ng == 9              ? 6
          : qw == GV_QW && ng == 4              ? 7
+         : GV_KWN && qw == GV_KWN_QW && ng == GV_KWN_NG2 ? 8
+         : GV_KWN && qw == GV_KWN_QW && ng == GV_KWN_NG1 ? 9
                                                : -1;
 }
 // GV_KN_GFRAME (default 1, round 6): after the last Q entry the accumulator
@@ -1929,7 +1962,7 @@ __global__ __launch_bounds__(256) GV_KN_ATTR void k_ecmult_kn(const u32* gtab6, 
     // slots 0..NG-1: Q of groups 0..NG-1; NG..2NG-1: lambda Q of groups
     // NG-1..0 on the lambda^2 frame; then (position 0) the 11 G windows
     // (the wide-window ladders only: the others would pass 168 VGPRs, 2 waves)
-    if constexpr (GV_KN_PREFETCH && QW == GV_KW_QW) {
+    if constexpr (GV_KN_PREFETCH && KWide<QW>::value) {
     constexpr int NSLOT = 2 * NG + GV_K6_GWIN;
     // slot s's digit (0: nothing to add -- a window past the group's, or G
     // off position 0) and the issue of its entry's loads into r
@@ -2181,7 +2214,11 @@ hipError_t gvk_verify(const gvk_batch* b, hipStream_t st) {
   const dim3 blk(256), grd(C / 256);
   // key-ordered lanes (gv_sort.hip): keyed k4 batches with sort scratch
   const bool k6 = b->kslot && b->k6 && b->gtab6;
-  const bool kw = k6 && b->kqw == 1 && (b->k6 == GV_KW_NG1 || b->k6 == GV_KW_NG2);   // the arena's wide-window tables
+  // the arena's wide-window tables: kwq their width (0: GV_KW_QW), in one of that width's two layouts
+  const int kwq = b->kwq ? b->kwq : GV_KW_QW;
+  const bool kw = k6 && b->kqw == 1 && gvk_kw_width_ok(kwq) &&
+                  (b->k6 == gvk_kw_ng(kwq, 1) || b->k6 == gvk_kw_ng(kwq, 2));
+  if (k6 && b->kqw == 1 && !kw) return hipErrorInvalidValue;
   const bool kg = k6 && b->kqw == 2;             // the grouped route's 5-bit many-group tables
   const bool gf = b->kslot && b->gtab4 && b->gtabf && !k6;   // k_ecmult_k4<true>
   const bool gfp = !b->kslot && b->gtabf;                     // per-item pub33: k_ecmult<false, true>
@@ -2211,12 +2248,19 @@ hipError_t gvk_verify(const gvk_batch* b, hipStream_t st) {
     if (b->keys_ready) (void)hipStreamWaitEvent(st, b->keys_ready, 0);   // grouped keys built beside s^-1
     if (b->ev[1]) (void)hipEventRecord(b->ev[1], st);
     if (kg)
-      hipLaunchKernelGGL((gv::k_prep<true, true, true, false, true>), grd, blk, 0, st, C, b->n, (const uint32_t*)nullptr,
+      hipLaunchKernelGGL((gv::k_prep<true, true, true, 0, true>), grd, blk, 0, st, C, b->n, (const uint32_t*)nullptr,
                          (const uint32_t*)nullptr, b->in_r, b->in_s, b->in_e, (const uint32_t*)w, b->digits,
                          (uint32_t*)nullptr, (uint32_t*)nullptr, b->flags, sorted ? b->srt.kslot : b->kslot,
                          b->kok, b->kcount, b->in_pfx);
+#if GV_KWN
+    else if (kw && kwq == GV_KWN_QW)
+      hipLaunchKernelGGL((gv::k_prep<true, true, true, GV_KWN_QW>), grd, blk, 0, st, C, b->n, (const uint32_t*)nullptr,
+                         (const uint32_t*)nullptr, b->in_r, b->in_s, b->in_e, (const uint32_t*)w, b->digits,
+                         (uint32_t*)nullptr, (uint32_t*)nullptr, b->flags, sorted ? b->srt.kslot : b->kslot,
+                         b->kok, b->kcount, b->in_pfx);
+#endif
     else if (kw)
-      hipLaunchKernelGGL((gv::k_prep<true, true, true, true>), grd, blk, 0, st, C, b->n, (const uint32_t*)nullptr,
+      hipLaunchKernelGGL((gv::k_prep<true, true, true, GV_KW_QW>), grd, blk, 0, st, C, b->n, (const uint32_t*)nullptr,
                          (const uint32_t*)nullptr, b->in_r, b->in_s, b->in_e, (const uint32_t*)w, b->digits,
                          (uint32_t*)nullptr, (uint32_t*)nullptr, b->flags, sorted ? b->srt.kslot : b->kslot,
                          b->kok, b->kcount, b->in_pfx);
@@ -2267,14 +2311,20 @@ hipError_t gvk_verify(const gvk_batch* b, hipStream_t st) {
 #undef GV_KG_LAUNCH
   else if (kg)
     return hipErrorInvalidValue;
+#define GV_KW_LAUNCH(QW, NG)                                                                                  \
+  hipLaunchKernelGGL((gv::k_ecmult_kn<QW, NG>), grd, blk, 0, se, b->gtab6, b->n, C, b->digits, b->kqt, b->kqt2, \
+                     b->kzq, b->flags, b->in_r, sorted ? b->srt.bits : b->bits, (const uint32_t*)b->in_pfx, b->kC)
+#if GV_KWN
+  else if (kw && kwq == GV_KWN_QW && b->k6 == GV_KWN_NG1)
+    GV_KW_LAUNCH(GV_KWN_QW, GV_KWN_NG1);
+  else if (kw && kwq == GV_KWN_QW)
+    GV_KW_LAUNCH(GV_KWN_QW, GV_KWN_NG2);
+#endif
   else if (kw && b->k6 == GV_KW_NG1)
-    hipLaunchKernelGGL((gv::k_ecmult_kn<GV_KW_QW, GV_KW_NG1>), grd, blk, 0, se, b->gtab6, b->n, C, b->digits,
-                       b->kqt, b->kqt2, b->kzq, b->flags, b->in_r, sorted ? b->srt.bits : b->bits,
-                       (const uint32_t*)b->in_pfx, b->kC);
+    GV_KW_LAUNCH(GV_KW_QW, GV_KW_NG1);
   else if (kw)
-    hipLaunchKernelGGL((gv::k_ecmult_kn<GV_KW_QW, GV_KW_NG2>), grd, blk, 0, se, b->gtab6, b->n, C, b->digits,
-                       b->kqt, b->kqt2, b->kzq, b->flags, b->in_r, sorted ? b->srt.bits : b->bits,
-                       (const uint32_t*)b->in_pfx, b->kC);
+    GV_KW_LAUNCH(GV_KW_QW, GV_KW_NG2);
+#undef GV_KW_LAUNCH
   else if (k6 && b->k6 == GV_KN_ARENA_NG)
     hipLaunchKernelGGL((gv::k_ecmult_kn<GV_K6_QW, GV_KN_ARENA_NG>), grd, blk, 0, se, b->gtab6, b->n, C, b->digits, b->kqt, b->kqt2,
                        b->kzq, b->flags, b->in_r, sorted ? b->srt.bits : b->bits, (const uint32_t*)b->in_pfx, b->kC);
@@ -2373,12 +2423,20 @@ hipError_t gvk_keys_build_rows_kg(uint32_t n, uint32_t C, const uint32_t* in_x, 
 hipError_t gvk_keys_build_wide(const uint8_t* pub33, uint32_t n, uint32_t C, uint32_t* in_x, uint32_t* in_pfx,
                                uint32_t* in_r, uint32_t* in_s, uint32_t* in_e, uint32_t* scratch, int with_qe,
                                uint32_t base, uint32_t* kqtw, uint32_t* kzqw, uint32_t kC, uint32_t* kok,
-                               uint32_t* kqtw2, uint32_t* kzqw2, int ng, hipStream_t st) {
+                               uint32_t* kqtw2, uint32_t* kzqw2, int qw, int ng, hipStream_t st) {
   if (n == 0) return hipSuccess;
-  if (ng != GV_KW_NG1 && ng != GV_KW_NG2) return hipErrorInvalidValue;
+  if (!gvk_kw_width_ok(qw) || (ng != gvk_kw_ng(qw, 1) && ng != gvk_kw_ng(qw, 2))) return hipErrorInvalidValue;
   const dim3 blk(256), grd(C / 256);
   hipLaunchKernelGGL(gv::k_unpack, grd, blk, 0, st, pub33, (const uint8_t*)nullptr, (const uint8_t*)nullptr, n, C,
                      in_x, in_pfx, in_r, in_s, in_e);
+#if GV_KWN
+  if (qw == GV_KWN_QW && ng == GV_KWN_NG1)
+    return keys_tables_launch<GV_KWN_QW, GV_KWN_NG1>(n, C, in_x, in_pfx, scratch, with_qe, base, kqtw, kzqw, kC, kok,
+                                                     kqtw2, kzqw2, st);
+  if (qw == GV_KWN_QW)
+    return keys_tables_launch<GV_KWN_QW, GV_KWN_NG2>(n, C, in_x, in_pfx, scratch, with_qe, base, kqtw, kzqw, kC, kok,
+                                                     kqtw2, kzqw2, st);
+#endif
   if (ng == GV_KW_NG1)
     return keys_tables_launch<GV_KW_QW, GV_KW_NG1>(n, C, in_x, in_pfx, scratch, with_qe, base, kqtw, kzqw, kC, kok,
                                                    kqtw2, kzqw2, st);

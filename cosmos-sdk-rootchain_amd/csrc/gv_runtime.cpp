@@ -158,15 +158,18 @@ struct Dev {
   uint32_t *kqt6 = nullptr, *kzq6 = nullptr, *kqt62 = nullptr, *kzq62 = nullptr;
   size_t keys6 = 0;                               // leading slots whose k6 tables are built
   // the resident arena's wide-window tables (option "keys_wide"): per slot
-  // kw_ng (GV_KW_NG1 = 12: one 11-bit window per group, or GV_KW_NG2 = 6: two;
-  // GV_KW_QW, gv_kernels.h) 1,024-entry group tables on one Z (kqtw: group 0, kqtw2:
-  // groups 1.., kzqw: the Z, 8 rows of stride kcapw; kzqw2: the chain's parked
-  // Zs), in an arena of their own (capacity kcapw) grown by doubling while the
-  // HBM budget holds it; keysw leading slots built.  kw_full: the budget
-  // refused a growth (no more wide-window builds until gv_keys_reset)
+  // kw_ng group tables of 2^(kw_qw - 1) entries on one Z -- kw_qw = GV_KW_QW
+  // (11: 1,024 entries; kw_ng = GV_KW_NG1 = 12: one window per group, or
+  // GV_KW_NG2 = 6: two) or GV_KWN_QW (9: 256 entries; GV_KWN_NG1 = 15 or
+  // GV_KWN_NG2 = 8; gv_kernels.h), the layout gv_keys_load picked (kWideLayouts)
+  // -- kqtw: group 0, kqtw2: groups 1.., kzqw: the Z, 8 rows of stride kcapw;
+  // kzqw2: the chain's parked Zs, in an arena of their own (capacity kcapw)
+  // grown by doubling while the HBM budget holds it; keysw leading slots
+  // built.  kw_full: the last layout's growth was refused (no more wide-window
+  // builds until gv_keys_reset)
   uint32_t *kqtw = nullptr, *kzqw = nullptr, *kqtw2 = nullptr, *kzqw2 = nullptr;
   size_t kcapw = 0, keysw = 0;
-  int kw_ng = 0;
+  int kw_ng = 0, kw_qw = 0;
   bool kw_full = false;
   // HBM held by the optional tables (G tables, key arenas) against ctx->hbm_budget
   size_t opt_bytes = 0;
@@ -368,8 +371,32 @@ int ensure_keys(Dev* d, size_t need, size_t used, hipStream_t st, size_t key_cap
   return GV_OK;
 }
 
-// Bytes per slot of the wide-window tables of ng groups.
-constexpr size_t key_wide_slot_bytes(int ng) { return ((size_t)GV_KW_KEY_WORDS * ng + 8 * (size_t)ng) * 4; }
+// Bytes per slot of the qw-bit wide-window tables of ng groups.
+inline size_t key_wide_slot_bytes(int qw, int ng) {
+  return qw && ng ? (gvk_kw_key_words(qw) * (size_t)ng + 8 * (size_t)ng) * 4 : 0;
+}
+
+// The wide arena's layouts in order of falling memory per key: 768, 384, 240
+// and 128 KiB of tables at 11 / 9 bits.  gv_keys_load starts an arena at the
+// first one its options allow ("keys_wide" 2: any, 1: two windows per group;
+// "keys_wide_qw": one width only) and moves the whole arena to the next
+// allowed one when ensure_keys_wide refuses a growth.
+struct WideLayout {
+  int qw, ng, wpg;                                // window width, groups, windows per group
+};
+const WideLayout kWideLayouts[] = {{GV_KW_QW, GV_KW_NG1, 1}, {GV_KW_QW, GV_KW_NG2, 2},
+#if GV_KWN
+                                   {GV_KWN_QW, GV_KWN_NG1, 1}, {GV_KWN_QW, GV_KWN_NG2, 2},
+#endif
+};
+constexpr int kWideLayoutCount = (int)(sizeof kWideLayouts / sizeof kWideLayouts[0]);
+// The first layout at or after index `from` of width only_qw (0: any) with at
+// least min_wpg windows per group; kWideLayoutCount when there is none.
+inline int wide_layout_next(int from, int only_qw, int min_wpg) {
+  for (int i = from; i < kWideLayoutCount; ++i)
+    if ((!only_qw || kWideLayouts[i].qw == only_qw) && kWideLayouts[i].wpg >= min_wpg) return i;
+  return kWideLayoutCount;
+}
 
 // Grow the wide-window arena to `need` slots keeping the first `used` (doubling, not
 // past key_cap, then exact -- as ensure_keys).  Returns false when the budget
@@ -378,16 +405,20 @@ constexpr size_t key_wide_slot_bytes(int ng) { return ((size_t)GV_KW_KEY_WORDS *
 // (plus 8 GiB of batch scratch: these tables are an optimisation and never
 // make a later gv_keys_load or batch fail), or when an allocation fails: the
 // arena is left as it was and batches keep the k6 tables.
-// The layout is d->kw_ng's; cap1 bounds the one-window layout's capacity (a
-// test hook, option "keys_wide1_cap").  ed_room: device memory the ed25519
-// key arena still needs to reach its own cap (reserved the same way).
+// The layout is d->kw_qw / d->kw_ng's; cap1 bounds the capacity of the
+// GV_KW_QW-bit one-window layout (a test hook, option "keys_wide1_cap"),
+// limit the new arena's bytes (option "keys_wide_mb"; 0: none).  ed_room:
+// device memory the ed25519 key arena still needs to reach its own cap
+// (reserved the same way).
 bool ensure_keys_wide(Dev* d, size_t need, size_t used, hipStream_t st, size_t key_cap, size_t budget,
-                      size_t ed_room, size_t cap1 = SIZE_MAX) {
+                      size_t ed_room, size_t limit, size_t cap1 = SIZE_MAX) {
   if (need <= d->kcapw) return true;
   const size_t grow = d->kcapw >= key_cap ? need : std::min<size_t>(2 * d->kcapw, std::max<size_t>(need, key_cap));
   const size_t cap = round_up(std::max<size_t>({need, grow, 4096}), 256);
-  const size_t slot_b = key_wide_slot_bytes(d->kw_ng);
-  if (d->kw_ng == GV_KW_NG1 && cap > cap1) return false;
+  const size_t slot_b = key_wide_slot_bytes(d->kw_qw, d->kw_ng);
+  const size_t kwords = gvk_kw_key_words(d->kw_qw);
+  if (d->kw_qw == GV_KW_QW && d->kw_ng == GV_KW_NG1 && cap > cap1) return false;
+  if (limit && cap * slot_b > limit) return false;
   if (d->opt_bytes + cap * slot_b > budget) return false;
   size_t free_b = 0, total_b = 0;
   if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) return false;
@@ -396,8 +427,8 @@ bool ensure_keys_wide(Dev* d, size_t need, size_t used, hipStream_t st, size_t k
   if (free_b < cap * slot_b + reserve) return false;
   const size_t ng1 = (size_t)d->kw_ng - 1;
   uint32_t *qt = nullptr, *zq = nullptr, *qt2 = nullptr, *zq2 = nullptr;
-  if (hipMalloc(&qt, cap * GV_KW_KEY_WORDS * 4) != hipSuccess || hipMalloc(&zq, cap * 8 * 4) != hipSuccess ||
-      hipMalloc(&qt2, cap * ng1 * GV_KW_KEY_WORDS * 4) != hipSuccess ||
+  if (hipMalloc(&qt, cap * kwords * 4) != hipSuccess || hipMalloc(&zq, cap * 8 * 4) != hipSuccess ||
+      hipMalloc(&qt2, cap * ng1 * kwords * 4) != hipSuccess ||
       hipMalloc(&zq2, cap * ng1 * 8 * 4) != hipSuccess) {
     for (uint32_t* p : {qt, zq, qt2, zq2}) if (p) (void)hipFree(p);
     (void)hipGetLastError();
@@ -405,8 +436,8 @@ bool ensure_keys_wide(Dev* d, size_t need, size_t used, hipStream_t st, size_t k
   }
   used = std::min(used, d->keysw);                // the slots whose wide-window tables exist
   if (used) {
-    bool ok = hipMemcpyAsync(qt, d->kqtw, used * GV_KW_KEY_WORDS * 4, hipMemcpyDeviceToDevice, st) == hipSuccess &&
-              hipMemcpyAsync(qt2, d->kqtw2, used * ng1 * GV_KW_KEY_WORDS * 4, hipMemcpyDeviceToDevice, st) ==
+    bool ok = hipMemcpyAsync(qt, d->kqtw, used * kwords * 4, hipMemcpyDeviceToDevice, st) == hipSuccess &&
+              hipMemcpyAsync(qt2, d->kqtw2, used * ng1 * kwords * 4, hipMemcpyDeviceToDevice, st) ==
                   hipSuccess;
     for (int r = 0; ok && r < 8; ++r)
       ok = hipMemcpyAsync(zq + r * cap, d->kzqw + r * d->kcapw, used * 4, hipMemcpyDeviceToDevice, st) == hipSuccess;
@@ -431,7 +462,7 @@ bool ensure_keys_wide(Dev* d, size_t need, size_t used, hipStream_t st, size_t k
 void free_keys_wide(Dev* d) {
   for (uint32_t** p : {&d->kqtw, &d->kzqw, &d->kqtw2, &d->kzqw2})
     if (*p) { (void)hipFree(*p); *p = nullptr; }
-  d->opt_bytes -= std::min(d->opt_bytes, d->kcapw * key_wide_slot_bytes(d->kw_ng));
+  d->opt_bytes -= std::min(d->opt_bytes, d->kcapw * key_wide_slot_bytes(d->kw_qw, d->kw_ng));
   d->kcapw = d->keysw = 0;
 }
 
@@ -699,9 +730,14 @@ struct gv_ctx {
                                 // front (217 / 210M/s; profiles/r06/ab/ab3, ab4)
   int keys_wide = 2;            // ... and wide-window tables while device memory holds them (GV_KEYS_WIDE): 2 = one
                                 // GV_KW_QW-bit window per group (11: 12 groups of 1,024 entries, no doublings, 24 Q
-                                // additions), moving to two per group (6 groups, 11 doublings) when that no longer fits;
-                                // 1 = two per group; 0 = none
+                                // additions), moving to two per group (6 groups, 11 doublings) when that no longer fits,
+                                // then to the GV_KWN_QW-bit layouts (keys_wide_qw); 1 = two per group; 0 = none
   size_t keys_wide1_cap = SIZE_MAX;   // test hook: the one-window layout's slot capacity ("keys_wide1_cap")
+  int keys_wide_qw = 0;         // the wide arena's window width ("keys_wide_qw", GV_KEYS_WIDE_QW): 0 = the GV_KW_QW-bit
+                                // layouts, then the GV_KWN_QW-bit ones when those no longer fit (kWideLayouts);
+                                // GV_KW_QW / GV_KWN_QW = that width's two layouts only
+  size_t keys_wide_bytes = 0;   // the wide arena is never allocated larger than this ("keys_wide_mb", GV_KEYS_WIDE_MB;
+                                // 0 = no limit): past it the arena moves down the layouts, then to the k6 tables
   bool keys_k6 = true;          // the resident arena (gv_keys_load) also holds k6 tables and its throughput batches
                                 // run k_ecmult_k6: the table build is paid once per key, not per batch (GV_KEYS_K6)
   size_t key_cap = GV_KEY_CAP;  // the callers' key-arena reset point: growth doubles up to here ("key_cap", GV_KEY_CAP)
@@ -1066,7 +1102,7 @@ int launch(gv_ctx* ctx, Dev* d, Set* s, size_t n, const uint8_t* pub, const uint
   if (kslot && !ka && !small && ctx->keys_wide && d->kqtw && d->kw_ng && d->gtab6 && d->keysw >= ctx->keys) {
     // the wide-window tables (their own arena: Z rows of stride kcapw)
     b.kqt = d->kqtw; b.kzq = d->kzqw; b.kqt2 = d->kqtw2; b.kC = (uint32_t)d->kcapw;
-    b.k6 = d->kw_ng; b.kqw = 1; b.gtab6 = d->gtab6;
+    b.k6 = d->kw_ng; b.kqw = 1; b.kwq = d->kw_qw; b.gtab6 = d->gtab6;
   } else if (kslot && !ka && !small && ctx->keys_k6 && d->kqt6 && d->gtab6 && d->keys6 >= ctx->keys) {
     b.kqt = d->kqt6; b.kzq = d->kzq6; b.kqt2 = d->kqt62;
     b.k6 = GV_KN_ARENA_NG; b.gtab6 = d->gtab6;
@@ -1098,10 +1134,11 @@ int launch(gv_ctx* ctx, Dev* d, Set* s, size_t n, const uint8_t* pub, const uint
     d->routes[kslot ? GV_ROUTE_LAT_KEYED : GV_ROUTE_LAT]++;
     if (kslot) {                                // keyed: 16 lanes per signature (group tables)
       lb.kqt2 = b.kqt2; lb.kzq2 = kzq2; lb.glat = d->glat;
-      if (sliced && !ka && ctx->keys_wide && ctx->lat_kw && d->kqtw && d->kw_ng == GV_KW_NG1 && d->gtab6 &&
-          d->keysw >= ctx->keys) {
-        // every slot has its one-window wide tables: k_verify_lat16_kw (no
-        // doublings; their own arena: Z rows of stride kcapw)
+      if (sliced && !ka && ctx->keys_wide && ctx->lat_kw && d->kqtw && d->kw_qw == GV_KW_QW &&
+          d->kw_ng == GV_KW_NG1 && d->gtab6 && d->keysw >= ctx->keys) {
+        // every slot has its GV_KW_QW-bit one-window wide tables:
+        // k_verify_lat16_kw (no doublings; their own arena: Z rows of stride
+        // kcapw); an arena of the narrow width takes the kn tables below
         lb.kqt = d->kqtw; lb.kzq = d->kzqw; lb.kqt2 = d->kqtw2; lb.kzq2 = nullptr; lb.kC = (uint32_t)d->kcapw;
         lb.gtab6 = d->gtab6; lb.kn = 2;
       } else if (sliced && !ka && ctx->keys_k6 && d->kqt6 && d->gtab6 && d->keys6 >= ctx->keys) {
@@ -1134,7 +1171,7 @@ int launch(gv_ctx* ctx, Dev* d, Set* s, size_t n, const uint8_t* pub, const uint
     }
     plan_sort(ctx, s, b, sort_base);
     d->routes[b.kqw == 2 && b.gtab6               ? GV_ROUTE_KG
-              : b.kqw && b.gtab6 && b.k6 == GV_KW_NG2 ? GV_ROUTE_KW2
+              : b.kqw && b.gtab6 && b.k6 == gvk_kw_ng(b.kwq, 2) ? GV_ROUTE_KW2
               : b.kqw && b.gtab6                ? GV_ROUTE_KW
               : b.k6 == GV_KN_ARENA_NG && b.gtab6 ? GV_ROUTE_KN
               : b.k6 && b.gtab6                ? GV_ROUTE_K6
@@ -2000,6 +2037,14 @@ int gv_open(const int* dev_ids, int n_dev, gv_ctx** out) {
     const int v = atoi(kk);
     if (v >= 0 && v <= 2) ctx->keys_wide = v;
   }
+  if (const char* kq = getenv("GV_KEYS_WIDE_QW")) {
+    const int v = atoi(kq);
+    if (v == 0 || gvk_kw_width_ok(v)) ctx->keys_wide_qw = v;
+  }
+  if (const char* km = getenv("GV_KEYS_WIDE_MB")) {
+    const long long v = atoll(km);
+    if (v >= 0 && v <= (long long)(SIZE_MAX >> 20)) ctx->keys_wide_bytes = (size_t)v << 20;
+  }
   if (const char* hl = getenv("GV_HOST_LADDER_STREAM")) ctx->host_ladder_stream = strcmp(hl, "0") != 0;
   parse_size_env("GV_ASYNC_CHUNK", &ctx->async_chunk);
   if (const char* ag = getenv("GV_ASYNC_GROWTH")) ctx->async_growth = std::max(1, std::min(64, atoi(ag)));
@@ -2321,7 +2366,7 @@ int gv_dev_verify_ed25519_msgs(gv_ctx* ctx, int dev_slot, size_t n, const void* 
 
 // ---- key arena
 namespace {
-// The wide-window tables (layout d->kw_ng) of the n keys pub33 (host) into
+// The wide-window tables (layout d->kw_qw / d->kw_ng) of the n keys pub33 (host) into
 // slots base.. of the wide arena, in chunks whose build scratch stays within
 // what the k6 build's chunks take.  The caller holds d->mu.
 int build_wide(gv_ctx* ctx, Dev* d, Set* s, hipStream_t st, const uint8_t* pub33, size_t n, size_t base) {
@@ -2331,14 +2376,14 @@ int build_wide(gv_ctx* ctx, Dev* d, Set* s, hipStream_t st, const uint8_t* pub33
     const size_t cn = std::min(stepw, n - c0);
     const size_t C = round_up(cn, 256);
     const int qew = ctx->keys_scratch ? 1 : 0;
-    const size_t ww = gvk_keys_scratch_words((uint32_t)cn, d->kw_ng, GV_KW_NT, qew);
+    const size_t ww = gvk_keys_scratch_words((uint32_t)cn, d->kw_ng, gvk_kw_nt(d->kw_qw), qew);
     const size_t Cs = std::max(C, round_up(ww / GV_QTAB_WORDS + 1, 256));
     if ((rc = ensure_cap(s, Cs))) return rc;
     if ((rc = set_acquire(s, st))) return rc;
     CK(hipMemcpyAsync(s->d_in, pub33 + c0 * 33, cn * 33, hipMemcpyHostToDevice, st));
     CK(gvk_keys_build_wide(s->d_in, (uint32_t)cn, (uint32_t)C, s->in_x, s->in_pfx, s->in_r, s->in_s, s->in_e, s->qtab,
                            qew, (uint32_t)(base + c0), d->kqtw, d->kzqw, (uint32_t)d->kcapw, d->kok, d->kqtw2,
-                           d->kzqw2, d->kw_ng, st));
+                           d->kzqw2, d->kw_qw, d->kw_ng, st));
     if ((rc = set_release(s, st))) return rc;
     CK(hipStreamSynchronize(st));
   }
@@ -2429,33 +2474,46 @@ int gv_keys_load(gv_ctx* ctx, size_t n, const uint8_t* pub33, uint32_t* slot_out
     }
     if (k6) d->keys6 = base + n;
     // the wide-window tables: while every earlier slot has them and memory
-    // holds the grown arena (a refusal stops them until gv_keys_reset:
-    // batches then take the k6 tables).  An arena started from slot 0 takes
-    // the option's layout; one window per group (15 tables per key) moves the
-    // whole arena to two per group (8 tables) when it no longer fits: the
-    // loaded slots' keys are read back from the k4 tables and rebuilt.
+    // holds the grown arena (a refusal of the last layout stops them until
+    // gv_keys_reset: batches then take the k6 tables).  An arena started from
+    // slot 0 takes the first layout the options allow (kWideLayouts); when a
+    // growth is refused the whole arena moves to the next allowed layout --
+    // one 11-bit window per group (12 tables of 64 KiB per key), two (6), one
+    // 9-bit window per group (15 tables of 16 KiB), two (8): the loaded slots'
+    // keys are read back from the k4 tables and rebuilt from slot 0.
     if (ctx->keys_wide && d->gtab6 && d->keysw == base && !d->kw_full) {
-      const int want = ctx->keys_wide == 2 ? GV_KW_NG1 : GV_KW_NG2;
-      if ((base == 0 || !d->kw_ng) && d->kw_ng != want) {
+      const int only_qw = ctx->keys_wide_qw;
+      int li = wide_layout_next(0, only_qw, ctx->keys_wide == 2 ? 1 : 2);
+      if (base != 0 && d->kw_ng) {                // a running arena keeps its layout
+        li = kWideLayoutCount;
+        for (int i = 0; i < kWideLayoutCount; ++i)
+          if (kWideLayouts[i].qw == d->kw_qw && kWideLayouts[i].ng == d->kw_ng) li = i;
+      } else if (li < kWideLayoutCount && (d->kw_ng != kWideLayouts[li].ng || d->kw_qw != kWideLayouts[li].qw)) {
         free_keys_wide(d);
-        d->kw_ng = want;
+        d->kw_qw = kWideLayouts[li].qw;
+        d->kw_ng = kWideLayouts[li].ng;
       }
       // the ed25519 arena's growth to ed_key_cap is reserved too (72 KB per key)
       const size_t ed_room = (ctx->ed_key_cap > d->ekcap ? ctx->ed_key_cap - d->ekcap : 0) *
                              ((size_t)GV_EDK_WORDS + 8 + 1) * 4;
-      bool ok = ensure_keys_wide(d, base + n, base, st, ctx->key_cap, ctx->hbm_budget, ed_room,
-                                 ctx->keys_wide1_cap);
-      if (!ok && d->kw_ng == GV_KW_NG1) {
-        // (a failed read-back only stops the wide tables: the k6 ones serve)
-        std::vector<uint8_t> old_pub;
-        const bool back = !base || read_back_pub33(ctx, d, st, base, old_pub) == GV_OK;
+      bool ok = li < kWideLayoutCount &&
+                ensure_keys_wide(d, base + n, base, st, ctx->key_cap, ctx->hbm_budget, ed_room,
+                                 ctx->keys_wide_bytes, ctx->keys_wide1_cap);
+      // (a failed read-back only stops the wide tables: the k6 ones serve)
+      std::vector<uint8_t> old_pub;
+      bool moved = false;
+      while (!ok && (li = wide_layout_next(li + 1, only_qw, 1)) < kWideLayoutCount) {
+        const bool back = moved || !base || read_back_pub33(ctx, d, st, base, old_pub) == GV_OK;
+        moved = true;
         free_keys_wide(d);
-        d->kw_ng = GV_KW_NG2;
-        ok = back && ensure_keys_wide(d, base + n, 0, st, ctx->key_cap, ctx->hbm_budget, ed_room);
-        // a failed rebuild only stops the wide tables (the k6 / k4 ones serve
-        // every slot): never a gv_keys_load error
-        if (ok && base && build_wide(ctx, d, s, st, old_pub.data(), base, 0) != GV_OK) ok = false;
+        d->kw_qw = kWideLayouts[li].qw;
+        d->kw_ng = kWideLayouts[li].ng;
+        if (!back) break;
+        ok = ensure_keys_wide(d, base + n, 0, st, ctx->key_cap, ctx->hbm_budget, ed_room, ctx->keys_wide_bytes);
       }
+      // a failed rebuild only stops the wide tables (the k6 / k4 ones serve
+      // every slot): never a gv_keys_load error
+      if (ok && moved && base && build_wide(ctx, d, s, st, old_pub.data(), base, 0) != GV_OK) ok = false;
       if (ok && build_wide(ctx, d, s, st, pub33, n, base) != GV_OK) ok = false;
       if (!ok) {
         (void)hipGetLastError();
@@ -2861,7 +2919,20 @@ int gv_get_option(gv_ctx* ctx, const char* key, long long* val) {
               {"async_growth", ctx->async_growth},
               {"async_whole", ctx->async_whole},
               {"lat_kw", ctx->lat_kw},
-              {"kw_qw", GV_KW_QW}};                  // read-only: the wide arena's window width (build)
+              {"keys_wide_qw", ctx->keys_wide_qw},
+              {"keys_wide_mb", (long long)(ctx->keys_wide_bytes >> 20)},
+              {"kw_qw", GV_KW_QW},                   // read-only: the wide arena's window width (build)
+              {"kwn_qw", GV_KWN ? GV_KWN_QW : 0}};   // read-only: its narrow width (build; 0: not compiled)
+  // read-only: the first device's wide arena as gv_keys_load left it -- its
+  // window width (0: no slot has wide tables) and its groups
+  if (!strcmp(key, "kw_arena_qw") || !strcmp(key, "kw_arena_ng")) {
+    if (ctx->devs.empty()) return GV_EINVAL;
+    Dev* d = ctx->devs[0];
+    std::lock_guard<std::mutex> lk(d->mu);
+    const bool live = d->kqtw && d->keysw;
+    *val = !live ? 0 : !strcmp(key, "kw_arena_qw") ? d->kw_qw : d->kw_ng;
+    return GV_OK;
+  }
   for (const auto& o : opts)
     if (!strcmp(key, o.k)) {
       *val = o.v;
@@ -2977,6 +3048,13 @@ int gv_set_option(gv_ctx* ctx, const char* key, long long val) {
       d->bits_used = false;
     }
     ctx->kg = (int)val;
+  } else if (!strcmp(key, "keys_wide_qw")) {
+    // the widths an arena started from slot 0 may take from now on
+    if (val != 0 && (val < 0 || val > 32 || !gvk_kw_width_ok((int)val))) return GV_EINVAL;
+    ctx->keys_wide_qw = (int)val;
+  } else if (!strcmp(key, "keys_wide_mb")) {
+    if (val < 0 || (unsigned long long)val > (SIZE_MAX >> 20)) return GV_EINVAL;
+    ctx->keys_wide_bytes = (size_t)val << 20;
   } else if (!strcmp(key, "keys_wide1_cap")) {
     if (val < 0) return GV_EINVAL;
     ctx->keys_wide1_cap = val == 0 ? SIZE_MAX : (size_t)val;

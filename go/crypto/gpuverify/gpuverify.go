@@ -219,6 +219,11 @@ type GPU struct {
 	// EdKeyCap: the same for the ed25519 key arena (72 KB of HBM per key;
 	// default GV_ED_KEY_CAP, env GV_ED_KEY_CAP).
 	EdKeyCap int
+	// KeysWideQW: the window widths the key arena's wide tables may take
+	// (gv_set_option "keys_wide_qw"): 0 = 11-bit tables, then 9-bit ones when
+	// those no longer fit; 11 or 9 = that width only.  Applies to an arena
+	// started from slot 0 (default 0, env GV_KEYS_WIDE_QW).
+	KeysWideQW int
 	// Logger, when set, reports every call that fell back to the CPU.
 	Logger Logger
 
@@ -258,6 +263,7 @@ func Open(devices []int) (*GPU, error) {
 	}
 	g := &GPU{ctx: ctx, CPUBelow: DefaultCPUBelow, Keyed: true, KeyLoadMin: DefaultKeyLoadMin,
 		KeyCap: envInt("GV_KEY_CAP", DefaultKeyCap), EdKeyCap: envInt("GV_ED_KEY_CAP", DefaultEdKeyCap),
+		KeysWideQW: envInt("GV_KEYS_WIDE_QW", 0),
 		slots: map[secp256k1.PubKeySecp256k1]uint32{}, edSlots: map[ed25519.PubKeyEd25519]uint32{}}
 	g.pool.ctx = ctx
 	// the library's arena growth doubles up to the reset points the shim uses
@@ -267,6 +273,10 @@ func Open(devices []int) (*GPU, error) {
 		return nil, err
 	}
 	if err := g.SetOption("ed_key_cap", int64(g.EdKeyCap)); err != nil {
+		g.Close()
+		return nil, err
+	}
+	if err := g.SetOption("keys_wide_qw", int64(g.KeysWideQW)); err != nil {
 		g.Close()
 		return nil, err
 	}

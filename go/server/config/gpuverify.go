@@ -36,6 +36,10 @@ type GPUVerifyConfig struct {
 	// KeyCap, EdKeyCap: arena sizes at which the arenas are reset.
 	KeyCap   int `mapstructure:"key-cap"`
 	EdKeyCap int `mapstructure:"ed-key-cap"`
+	// KeysWideQW: window widths of the key arena's wide tables (gv_set_option
+	// keys_wide_qw): 0 = 11-bit, then 9-bit when those no longer fit; 11 or 9
+	// = that width only.
+	KeysWideQW int `mapstructure:"keys-wide-qw"`
 	// CacheEntries: the verdict cache (0 = no cache).
 	CacheEntries int `mapstructure:"cache-entries"`
 	// CheckTxWindowTxs / CheckTxWindow: the concurrent-CheckTx accumulation
@@ -54,7 +58,7 @@ type GPUVerifyConfig struct {
 func DefaultGPUVerifyConfig() GPUVerifyConfig {
 	return GPUVerifyConfig{
 		Enable: false, Devices: "", MaxBatch: 1 << 20, CPUBelow: 4, Keyed: true, KeyLoadMin: 4096,
-		KeyCap: 1 << 22, EdKeyCap: 1 << 16, CacheEntries: 1 << 20, CheckTxWindowTxs: 64,
+		KeyCap: 1 << 22, EdKeyCap: 1 << 16, KeysWideQW: 0, CacheEntries: 1 << 20, CheckTxWindowTxs: 64,
 		CheckTxWindow: 200 * time.Microsecond, PreVerifyBlocks: true,
 	}
 }
@@ -85,6 +89,8 @@ func (c GPUVerifyConfig) Validate() error {
 		return fmt.Errorf("gpu-verify.max-batch must be >= 256, got %d", c.MaxBatch)
 	case c.CPUBelow < 0, c.KeyLoadMin < 1, c.KeyCap < 1, c.EdKeyCap < 1, c.CacheEntries < 0:
 		return fmt.Errorf("gpu-verify: negative or zero size in %+v", c)
+	case c.KeysWideQW != 0 && c.KeysWideQW != 9 && c.KeysWideQW != 11:
+		return fmt.Errorf("gpu-verify.keys-wide-qw must be 0, 9 or 11, got %d", c.KeysWideQW)
 	case c.CheckTxWindowTxs < 1 || c.CheckTxWindow < 0:
 		return fmt.Errorf("gpu-verify: bad CheckTx window (%d txs, %v)", c.CheckTxWindowTxs, c.CheckTxWindow)
 	}
@@ -116,6 +122,11 @@ keyed = {{ .GPUVerify.Keyed }}
 key-load-min = {{ .GPUVerify.KeyLoadMin }}
 key-cap = {{ .GPUVerify.KeyCap }}
 ed-key-cap = {{ .GPUVerify.EdKeyCap }}
+
+# Window width of the key arena's wide tables: 0 = 11-bit tables (768 / 384 KiB
+# per key), then 9-bit ones (240 / 128 KiB) when those no longer fit; 11 or 9 =
+# that width only.
+keys-wide-qw = {{ .GPUVerify.KeysWideQW }}
 
 # Verdict cache entries (0 disables it).
 cache-entries = {{ .GPUVerify.CacheEntries }}

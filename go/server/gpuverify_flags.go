@@ -64,6 +64,11 @@ func NewGPUVerifier(cfg config.GPUVerifyConfig, logger log.Logger) (gv.Verifier,
 	}
 	g.CPUBelow, g.Keyed, g.KeyLoadMin = cfg.CPUBelow, cfg.Keyed, cfg.KeyLoadMin
 	g.KeyCap, g.EdKeyCap = cfg.KeyCap, cfg.EdKeyCap
+	if err := g.SetOption("keys_wide_qw", int64(cfg.KeysWideQW)); err != nil {
+		logger.Error("gpu-verify: keys-wide-qw not applied", "err", err)
+	} else {
+		g.KeysWideQW = cfg.KeysWideQW
+	}
 	g.Logger = logger.With("module", "gpuverify")
 	logger.Info("gpu-verify enabled", "devices", cfg.Devices, "keyed", cfg.Keyed, "cpu-below", cfg.CPUBelow)
 	return g, g.Close

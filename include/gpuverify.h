@@ -324,17 +324,34 @@ int gv_verify_ed25519_msgs_keyed(gv_ctx* ctx, size_t n, const uint32_t* slot, co
  * tables -- and keyed throughput batches whose slots all have them run the
  * 6-doubling ladder; small keyed batches keep the k4 tables; same verdicts;
  * default 1, env GV_KEYS_K6; route counter GV_ROUTE_KN),
- * "keys_wide" (0/1/2: gv_keys_load also builds each key's 9-bit-window
- * tables of 256 entries on one Z -- 2 (default): one window per group, 15
- * tables (240 KB per key), no doublings and 30 Q additions per verify; 1: two
- * windows per group, 8 tables (128 KB), 9 doublings -- in an arena of their
- * own that grows by doubling while the HBM budget holds it and the device
- * keeps room for the k4 / k6 arena to reach key_cap; with 2, an arena that no
- * longer fits moves to the two-window layout (the loaded keys are read back
- * from the k4 tables and rebuilt); keyed throughput batches whose slots all
- * have them run that ladder (else the k6 one); same verdicts; the layout of
- * an arena is chosen when it starts from slot 0; env GV_KEYS_WIDE; route
- * counters GV_ROUTE_KW / GV_ROUTE_KW2),
+ * "keys_wide" (0/1/2: gv_keys_load also builds each key's wide-window tables
+ * on one Z, in an arena of their own that grows by doubling while the HBM
+ * budget holds it and the device keeps room for the k4 / k6 arena to reach
+ * key_cap.  The arena has one of four layouts, in order of falling memory per
+ * key:
+ *   A  11-bit windows, one per group: 12 tables of 1,024 entries, 768 KiB per
+ *      key, no doublings and 24 Q additions per verify;
+ *   B  11-bit, two per group: 6 tables, 384 KiB, 11 doublings;
+ *   C  9-bit, one per group: 15 tables of 256 entries, 240 KiB, no doublings
+ *      and 30 Q additions;
+ *   D  9-bit, two per group: 8 tables, 128 KiB, 9 doublings.
+ * 2 (default) starts an arena at A, 1 at B; an arena whose growth is refused
+ * moves as a whole to the next layout of the list (the loaded keys are read
+ * back from the k4 tables and rebuilt from slot 0), and only a refusal of D
+ * stops the wide tables until gv_keys_reset; an arena started from slot 0
+ * after gv_keys_reset starts at the top again.  Keyed throughput batches
+ * whose slots all have wide tables run that ladder (else the k6 one); same
+ * verdicts; the option takes effect for an arena started from slot 0, 0 at
+ * once; env GV_KEYS_WIDE; route counters GV_ROUTE_KW (one window per group,
+ * either width) / GV_ROUTE_KW2 (two)),
+ * "keys_wide_qw" (0/9/11: the widths the wide arena may take -- 0 (default):
+ * all four layouts; 11: A and B only, past B the k6 tables; 9: C and D only,
+ * "keys_wide" 2 starting at C and 1 at D; anything else is GV_EINVAL; takes
+ * effect for an arena started from slot 0; env GV_KEYS_WIDE_QW; the widths
+ * are the build's "kw_qw" / "kwn_qw"),
+ * "keys_wide_mb" (MiB: the wide arena is never allocated larger than this --
+ * a growth whose new arena would pass it is refused and the arena moves down
+ * the layouts as above; 0 = no limit, the default; env GV_KEYS_WIDE_MB),
  * "key_cap" / "ed_key_cap" (the callers' reset points of the secp256k1 /
  * ed25519 key arenas: an arena grows by doubling up to it and exactly past it;
  * defaults GV_KEY_CAP / GV_ED_KEY_CAP, env of the same names; the Go shim sets
@@ -352,10 +369,14 @@ int gv_verify_ed25519_msgs_keyed(gv_ctx* ctx, size_t n, const uint32_t* slot, co
 int gv_set_option(gv_ctx* ctx, const char* key, long long val);
 /* The current value of a schedule option set by gv_set_option or its
  * environment variable: "kg", "k6", "gfull", "keys_k6", "keys_wide",
- * "group_keys", "sort_keys", "pipeline_dev", "two_ladders", "key_cap",
- * "max_batch", "async_chunk", "async_growth", "async_whole", and (read
- * only) "kw_qw", the resident arena's wide-window width this library was
- * built with.  GV_EINVAL for any other key.  Instrumentation (bench route
+ * "keys_wide_qw", "keys_wide_mb", "group_keys", "sort_keys", "pipeline_dev",
+ * "two_ladders", "key_cap", "max_batch", "async_chunk", "async_growth",
+ * "async_whole", "lat_kw", and (read only) "kw_qw" / "kwn_qw", the wide and
+ * the narrow window width of the resident arena's wide tables this library
+ * was built with (11 / 9; "kwn_qw" 0: one width only), and "kw_arena_qw" /
+ * "kw_arena_ng", the window width and the group count of the first device's
+ * wide arena as the last gv_keys_load left it (both 0: no slot has wide
+ * tables).  GV_EINVAL for any other key.  Instrumentation (bench route
  * attribution). */
 int gv_get_option(gv_ctx* ctx, const char* key, long long* val);
 
@@ -429,9 +450,10 @@ int gv_group_stats(gv_ctx* ctx, int dev_slot, uint64_t* batches, uint64_t* keys)
  * batches on the resident arena's k6 tables: 11 groups of 6-bit windows, 6
  * doublings, option "keys_k6"), GV_ROUTE_ED_LAT (small uncached ed25519
  * host batches on k_ed_lat_unc, option "ed_unc_lat_max"), GV_ROUTE_KW (keyed
- * batches on the resident arena's wide-window tables, one 9-bit window per
- * group: 15 groups, no doublings, option "keys_wide"), GV_ROUTE_KW2 (the same
- * with two windows per group: 8 groups, 9 doublings), GV_ROUTE_KG (in-batch
+ * batches on the resident arena's wide-window tables, one window per group:
+ * 12 groups at 11 bits or 15 at 9, no doublings, option "keys_wide"),
+ * GV_ROUTE_KW2 (the same with two windows per group: 6 groups and 11
+ * doublings, or 8 and 9), GV_ROUTE_KG (in-batch
  * key grouping on the many-group 5-bit ladder, option "kg").  Instrumentation only (bench route
  * attribution, node metrics). */
 #define GV_ROUTE_PUB33 0
