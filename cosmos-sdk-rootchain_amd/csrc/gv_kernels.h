@@ -377,19 +377,19 @@ hipError_t gvk_gen_gtable6(uint32_t* gtab6, uint32_t* base_scratch, hipStream_t 
 // The resident arena's k6 tables (GV_KN_ARENA_NG groups of 32 entries) of n
 // keys (device pub33) into slots base..base+n-1 (rows of kqt6:
 // GV_K6_KEY_WORDS, kqt62: GV_KN_ARENA_NG - 1 per slot, kzq62:
-// (GV_KN_ARENA_NG - 1) x 8 rows); scratch as gvk_keys_build.
+// (GV_KN_ARENA_NG - 1) x 8 rows); scratch as gvk_keys_build.  slots as there.
 hipError_t gvk_keys_build6(const uint8_t* pub33, uint32_t n, uint32_t C, uint32_t* in_x, uint32_t* in_pfx,
                            uint32_t* in_r, uint32_t* in_s, uint32_t* in_e, uint32_t* scratch, int with_qe,
-                           uint32_t base, uint32_t* kqt6, uint32_t* kzq6, uint32_t kC, uint32_t* kok, uint32_t* kqt62,
-                           uint32_t* kzq62, hipStream_t st);
+                           uint32_t base, const uint32_t* slots, uint32_t* kqt6, uint32_t* kzq6, uint32_t kC,
+                           uint32_t* kok, uint32_t* kqt62, uint32_t* kzq62, hipStream_t st);
 // The resident arena's wide-window tables of width qw (GV_KW_QW or GV_KWN_QW)
 // in ng = gvk_kw_ng(qw, 1 or 2) groups of gvk_kw_nt(qw) entries, same
 // arguments as gvk_keys_build6 (kqtw: gvk_kw_key_words(qw) per slot, kqtw2:
 // ng - 1 rows per slot, kzqw2: (ng - 1) x 8 rows).
 hipError_t gvk_keys_build_wide(const uint8_t* pub33, uint32_t n, uint32_t C, uint32_t* in_x, uint32_t* in_pfx,
                            uint32_t* in_r, uint32_t* in_s, uint32_t* in_e, uint32_t* scratch, int with_qe,
-                           uint32_t base, uint32_t* kqtw, uint32_t* kzqw, uint32_t kC, uint32_t* kok, uint32_t* kqtw2,
-                           uint32_t* kzqw2, int qw, int ng, hipStream_t st);
+                           uint32_t base, const uint32_t* slots, uint32_t* kqtw, uint32_t* kzqw, uint32_t kC,
+                           uint32_t* kok, uint32_t* kqtw2, uint32_t* kzqw2, int qw, int ng, hipStream_t st);
 // the full-scalar G tables (GV_GF_WORDS words); base_scratch: 96 words
 hipError_t gvk_gen_gtablef(uint32_t* gtabf, uint32_t* base_scratch, hipStream_t st);
 // Key-table builds (k_keys_chain + k_keys_fwd + k_keys_back): scratch of
@@ -434,10 +434,14 @@ hipError_t gvk_keys_build_rows(uint32_t n, uint32_t C, const uint32_t* in_x, con
 // Parse n keys (device pub33) into arena slots base..base+n-1 (k4 tables).
 // Scratch: the batch rows in_x, in_pfx (and r, s, e as k_unpack targets) of
 // stride C and gvk_keys_scratch_words(n, 4, GV_QTAB_N, with_qe) words.
+// slots (device, n words; null: append at base): key i goes to slot slots[i]
+// instead of base + i (gv_keys_replace).  The kernels take the list as given:
+// the caller has bounded every entry by the arena's capacity and the entries
+// are distinct (two lanes would write one row).
 hipError_t gvk_keys_build(const uint8_t* pub33, uint32_t n, uint32_t C, uint32_t* in_x, uint32_t* in_pfx,
                           uint32_t* in_r, uint32_t* in_s, uint32_t* in_e, uint32_t* scratch, int with_qe,
-                          uint32_t base, uint32_t* kqt, uint32_t* kzq, uint32_t kC, uint32_t* kok, uint32_t* kqt2,
-                          uint32_t* kzq2, hipStream_t st);
+                          uint32_t base, const uint32_t* slots, uint32_t* kqt, uint32_t* kzq, uint32_t kC,
+                          uint32_t* kok, uint32_t* kqt2, uint32_t* kzq2, hipStream_t st);
 hipError_t gvk_keys_point(uint32_t n, const uint32_t* slots, const uint32_t* kqt, const uint32_t* kzq, uint32_t kC,
                           const uint32_t* kok, uint32_t kcount, uint8_t* out_xy, uint8_t* out_ok, hipStream_t st);
 hipError_t gvk_debug(int op, uint32_t n, const uint32_t* in, uint32_t* out, hipStream_t st);

@@ -24,6 +24,7 @@
 // of a wave is one coalesced 256-byte transaction.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 #include "secp_field.cuh"
 #include "secp_scalar.cuh"
 #include "secp_group.cuh"
@@ -868,8 +869,31 @@ GV_DEV void gej29_to_affine_words(fe& x8, fe& y8, const gej29& p) {
 #ifndef GV_CHAIN_SPLIT
 #define GV_CHAIN_SPLIT 0
 #endif
-template <int QW, int NG>
-__global__ __launch_bounds__(512) GV_FRONT_ATTR void k_keys_chain(u32 n, u32 C, const u32* in_x, const u32* in_pfx, u32 base,
+// Where a build lane's key lives in the arena: the kernels below take the
+// slot argument SL as u32 base (the append form: gv_keys_load and the
+// per-batch arenas; lane g -> slot base + g, the kernels' code as it was before
+// gv_keys_replace) or as const u32* slots (gv_keys_replace: lane g ->
+// slots[g], a device list whose entries the host has bounded by the arena's
+// capacity and checked for duplicates).  Only arena addresses (kqt / kqt2
+// rows, kzq / kzq2 / kok columns) go through it; the dense scratch rows stay
+// indexed by lane.
+// key_slot(...)() is the lane's slot: the append form adds at each use, as the
+// kernels always did (their code is unchanged); the list form loads once.
+// (after(x): x + the slot in 64 bits, the Z-column index as k_keys_chain forms it)
+struct KeySlotSum {
+  u32 base, g;
+  GV_DEV u32 operator()() const { return base + g; }
+  GV_DEV size_t after(size_t x) const { return x + base + g; }
+};
+struct KeySlotAt {
+  u32 slot;
+  GV_DEV u32 operator()() const { return slot; }
+  GV_DEV size_t after(size_t x) const { return x + slot; }
+};
+GV_DEV KeySlotSum key_slot(u32 base, u32 g) { return KeySlotSum{base, g}; }
+GV_DEV KeySlotAt key_slot(const u32* slots, u32 g) { return KeySlotAt{slots[g]}; }
+template <int QW, int NG, class SL = u32>
+__global__ __launch_bounds__(512) GV_FRONT_ATTR void k_keys_chain(u32 n, u32 C, const u32* in_x, const u32* in_pfx, SL base,
                                                      u32* kqt, u32 kC, u32* kok, u32* kqt2, u32* kzq2, u32* kzq) {
   using L = KLayout<QW, NG>;
 #if GV_CHAIN_SPLIT
@@ -879,6 +903,7 @@ __global__ __launch_bounds__(512) GV_FRONT_ATTR void k_keys_chain(u32 n, u32 C, 
   const u32 g = blockIdx.x * blockDim.x + threadIdx.x;
 #endif
   if (g >= n) return;                       // no cross-lane work
+  const auto slot = key_slot(base, g);
 #if !GV_CHAIN_SPLIT
   {
     fe x, y;
@@ -888,10 +913,10 @@ __global__ __launch_bounds__(512) GV_FRONT_ATTR void k_keys_chain(u32 n, u32 C, 
       fe_from_const(x, kGx);
       fe_from_const(y, kGy);
     }
-    kok[base + g] = ok ? 1u : 0u;
+    kok[slot()] = ok ? 1u : 0u;
 #pragma unroll
-    for (int i = 0; i < 8; ++i) kzq[(size_t)i * kC + base + g] = i == 0 ? 1u : 0u;   // u = 1: the chain runs on E
-    u32* p = kqt + (size_t)(base + g) * L::NT * L::EW;
+    for (int i = 0; i < 8; ++i) kzq[slot.after((size_t)i * kC)] = i == 0 ? 1u : 0u;   // u = 1: the chain runs on E
+    u32* p = kqt + (size_t)slot() * L::NT * L::EW;
 #pragma unroll
     for (int i = 0; i < 8; ++i) { p[i] = x.v[i]; p[8 + i] = y.v[i]; }
     gej29 q;
@@ -905,10 +930,10 @@ __global__ __launch_bounds__(512) GV_FRONT_ATTR void k_keys_chain(u32 n, u32 C, 
       u32 xw[8], yw[8];
       f29_to_words(xw, q.x);
       f29_to_words(yw, q.y);
-      u32* t = kqt2 + (size_t)((base + g) * (NG - 1) + (grp - 1)) * L::NT * L::EW;
+      u32* t = kqt2 + (size_t)(slot() * (NG - 1) + (grp - 1)) * L::NT * L::EW;
 #pragma unroll
       for (int i = 0; i < 8; ++i) { t[i] = xw[i]; t[8 + i] = yw[i]; }
-      store_f29(kzq2 + (size_t)(grp - 1) * 8 * kC, kC, base + g, q.z);
+      store_f29(kzq2 + (size_t)(grp - 1) * 8 * kC, kC, slot(), q.z);
     }
     return;
   }
@@ -942,9 +967,9 @@ __global__ __launch_bounds__(512) GV_FRONT_ATTR void k_keys_chain(u32 n, u32 C, 
     f29_to_words(y.v, y29);                 // canonical
     if ((y.v[0] & 1u) != (pre & 1u)) fe_neg(y, y);   // the prefix's parity (y != 0 always)
     fe_normalize(y);
-    kok[base + g] = ok ? 1u : 0u;
+    kok[slot()] = ok ? 1u : 0u;
 #pragma unroll
-    for (int i = 0; i < 8; ++i) kzq[(size_t)i * kC + base + g] = y.v[i];   // u, read by the table build
+    for (int i = 0; i < 8; ++i) kzq[slot.after((size_t)i * kC)] = y.v[i];   // u, read by the table build
     return;
   }
   auto park = [](u32* tab, u32 row, const u32* xw, const u32* yw) {
@@ -962,7 +987,7 @@ __global__ __launch_bounds__(512) GV_FRONT_ATTR void k_keys_chain(u32 n, u32 C, 
     f29_to_words(yw, q.y);
     f29_from_words(q.x, xw);
     f29_from_words(q.y, yw);
-    park(kqt, base + g, xw, yw);
+    park(kqt, slot(), xw, yw);
   }
 #pragma unroll 1
   for (int grp = 1; grp < NG; ++grp) {
@@ -971,8 +996,8 @@ __global__ __launch_bounds__(512) GV_FRONT_ATTR void k_keys_chain(u32 n, u32 C, 
     u32 xw[8], yw[8];
     f29_to_words(xw, q.x);
     f29_to_words(yw, q.y);
-    park(kqt2, (base + g) * (NG - 1) + (grp - 1), xw, yw);
-    store_f29(kzq2 + (size_t)(grp - 1) * 8 * kC, kC, base + g, q.z);
+    park(kqt2, slot() * (NG - 1) + (grp - 1), xw, yw);
+    store_f29(kzq2 + (size_t)(grp - 1) * 8 * kC, kC, slot(), q.z);
   }
 #endif
 }
@@ -1203,15 +1228,16 @@ GV_DEV void keys_get(const u32* qe, u32 CL, u32 L, const u32* tab, u32 row, int 
   }
 }
 
-template <int QW, int NG>
-__global__ __launch_bounds__(256) GV_FRONT_ATTR void k_keys_fwd(u32 n, u32 CL, u32 base, u32* kqt, u32 kC, u32* kqt2,
+template <int QW, int NG, class SL = u32>
+__global__ __launch_bounds__(256) GV_FRONT_ATTR void k_keys_fwd(u32 n, u32 CL, SL base, u32* kqt, u32 kC, u32* kqt2,
                                                    const u32* kzq2, u32* qr, u32* qe, u32* er, const u32* kzq) {
   constexpr int NT = KLayout<QW, NG>::NT;
   const u32 L = blockIdx.x * blockDim.x + threadIdx.x;
   const u32 key = L / NG, grp = L % NG;
   if (key >= n) return;
+  const auto slot = key_slot(base, key);
   u32* tab = grp == 0u ? kqt : kqt2;
-  const u32 row = grp == 0u ? base + key : (base + key) * (NG - 1) + (grp - 1u);
+  const u32 row = grp == 0u ? slot() : slot() * (NG - 1) + (grp - 1u);
   fe29 qx, qy, X1, Y1, X2, Y2, t, u, prod;
   {
     const u32* p = tab + (size_t)row * NT * KLayout<QW, NG>::EW;
@@ -1273,12 +1299,12 @@ __global__ __launch_bounds__(256) GV_FRONT_ATTR void k_keys_fwd(u32 n, u32 CL, u
   // ran on E', k_keys_chain; k_keys_back overwrites kzq only in a later launch)
   if (grp) {
     fe29 z;
-    load_f29(z, kzq2 + (size_t)(grp - 1u) * 8 * kC, kC, base + key);
+    load_f29(z, kzq2 + (size_t)(grp - 1u) * 8 * kC, kC, slot());
     f29x_mul(prod, prod, z);
   }
   {
     fe29 u;
-    load_f29(u, kzq, kC, base + key);
+    load_f29(u, kzq, kC, slot());
     f29x_mul(prod, prod, u);
   }
   store_ratio29(er, CL, L, 0, prod);
@@ -1289,16 +1315,17 @@ __global__ __launch_bounds__(256) GV_FRONT_ATTR void k_keys_fwd(u32 n, u32 CL, u
 // E_0 ... E_{NG-1} -- ONE accumulator takes entries of every group, with no
 // inversion -- then the back-propagation: entry m - 1 (on Z_{m-1}) times
 // (rho Z_last / Z_{m-1})^2 and ^3, each table entry written once.
-template <int QW, int NG>
-__global__ __launch_bounds__(256) GV_FRONT_ATTR void k_keys_back(u32 n, u32 CL, u32 base, u32* kqt, u32* kzq, u32 kC,
+template <int QW, int NG, class SL = u32>
+__global__ __launch_bounds__(256) GV_FRONT_ATTR void k_keys_back(u32 n, u32 CL, SL base, u32* kqt, u32* kzq, u32 kC,
                                                     u32* kqt2, u32* kzq2, const u32* qr, const u32* qe,
                                                     const u32* er) {
   constexpr int NT = KLayout<QW, NG>::NT;
   const u32 L = blockIdx.x * blockDim.x + threadIdx.x;
   const u32 key = L / NG, grp = L % NG;
   if (key >= n) return;
+  const auto slot = key_slot(base, key);
   u32* tab = grp == 0u ? kqt : kqt2;
-  const u32 row = grp == 0u ? base + key : (base + key) * (NG - 1) + (grp - 1u);
+  const u32 row = grp == 0u ? slot() : slot() * (NG - 1) + (grp - 1u);
   u32* zrow = grp == 0u ? kzq : kzq2 + (size_t)(grp - 1u) * 8 * kC;
   fe29 acc, zc, own;
   bool first = true;
@@ -1349,7 +1376,7 @@ __global__ __launch_bounds__(256) GV_FRONT_ATTR void k_keys_back(u32 n, u32 CL, 
     store_qent29<NT, KLayout<QW, NG>::EW>(tab, row, m - 1, x, y);
   }
 #endif
-  store_f29(zrow, kC, base + key, zc);
+  store_f29(zrow, kC, slot(), zc);
 }
 
 // Affine 2^35 G, 2^70 G, 2^100 G (16 words each) for the keyed ladder's G
@@ -2370,9 +2397,11 @@ hipError_t gvk_gen_glat(uint32_t* glat, hipStream_t st) {
 // whose rows in_x / in_pfx (stride C) are unpacked.  Scratch (gv_kernels.h
 // gvk_keys_scratch_words): ratio rows, the E rows, the forward entries.
 }  // extern "C"
-template <int QW, int NG>
+// SL: uint32_t base (append: key i to slot base + i) or const uint32_t*
+// slots (device list: key i to slot slots[i], gv_keys_replace).
+template <int QW, int NG, class SL = uint32_t>
 static hipError_t keys_tables_launch(uint32_t n, uint32_t C, const uint32_t* in_x, const uint32_t* in_pfx,
-                                     uint32_t* scratch, int with_qe, uint32_t base, uint32_t* kqt, uint32_t* kzq,
+                                     uint32_t* scratch, int with_qe, SL base, uint32_t* kqt, uint32_t* kzq,
                                      uint32_t kC, uint32_t* kok, uint32_t* kqt2, uint32_t* kzq2, hipStream_t st) {
   if (n == 0) return hipSuccess;
   constexpr int NT = gv::KLayout<QW, NG>::NT;
@@ -2380,18 +2409,22 @@ static hipError_t keys_tables_launch(uint32_t n, uint32_t C, const uint32_t* in_
   uint32_t* qr = scratch;
   uint32_t* er = qr + (size_t)(NT - 2) * 9 * CL;
   uint32_t* qe = with_qe ? er + (size_t)9 * CL : nullptr;
-  hipLaunchKernelGGL((gv::k_keys_chain<QW, NG>), dim3((n + 255) / 256), dim3(GV_CHAIN_SPLIT ? 512 : 256), 0, st, n, C,
-                     in_x, in_pfx, base, kqt, kC, kok, kqt2, kzq2, kzq);
-  if (NG == 4) {
-    // four groups: one launch, the quad trades its Zs by lane shuffles (the
-    // last entry stays in registers; the E rows are unused)
-    hipLaunchKernelGGL((gv::k_keys_tables<QW>), dim3(CL / 256), dim3(256), 0, st, n, CL, base, kqt, kzq, kC, kqt2, kzq2,
-                       qr, qe);
-    return hipGetLastError();
+  hipLaunchKernelGGL((gv::k_keys_chain<QW, NG, SL>), dim3((n + 255) / 256), dim3(GV_CHAIN_SPLIT ? 512 : 256), 0, st, n,
+                     C, in_x, in_pfx, base, kqt, kC, kok, kqt2, kzq2, kzq);
+  if constexpr (std::is_same<SL, uint32_t>::value) {
+    if (NG == 4) {
+      // four groups: one launch, the quad trades its Zs by lane shuffles (the
+      // last entry stays in registers; the E rows are unused).  Append form
+      // only: k_keys_tables spills at its four-wave register cap, so a
+      // four-group replace takes the two launches below, which hold no scratch.
+      hipLaunchKernelGGL((gv::k_keys_tables<QW>), dim3(CL / 256), dim3(256), 0, st, n, CL, base, kqt, kzq, kC, kqt2,
+                         kzq2, qr, qe);
+      return hipGetLastError();
+    }
   }
-  hipLaunchKernelGGL((gv::k_keys_fwd<QW, NG>), dim3(CL / 256), dim3(256), 0, st, n, CL, base, kqt, kC, kqt2,
+  hipLaunchKernelGGL((gv::k_keys_fwd<QW, NG, SL>), dim3(CL / 256), dim3(256), 0, st, n, CL, base, kqt, kC, kqt2,
                      (const uint32_t*)kzq2, qr, qe, er, (const uint32_t*)kzq);
-  hipLaunchKernelGGL((gv::k_keys_back<QW, NG>), dim3(CL / 256), dim3(256), 0, st, n, CL, base, kqt, kzq, kC, kqt2,
+  hipLaunchKernelGGL((gv::k_keys_back<QW, NG, SL>), dim3(CL / 256), dim3(256), 0, st, n, CL, base, kqt, kzq, kC, kqt2,
                      kzq2, (const uint32_t*)qr, (const uint32_t*)qe, (const uint32_t*)er);
   return hipGetLastError();
 }
@@ -2420,51 +2453,70 @@ hipError_t gvk_keys_build_rows_kg(uint32_t n, uint32_t C, const uint32_t* in_x, 
   }
 }
 
+}  // extern "C"
+template <class SL>
+static hipError_t keys_build_wide_launch(uint32_t n, uint32_t C, const uint32_t* in_x, const uint32_t* in_pfx,
+                                         uint32_t* scratch, int with_qe, SL base, uint32_t* kqtw, uint32_t* kzqw,
+                                         uint32_t kC, uint32_t* kok, uint32_t* kqtw2, uint32_t* kzqw2, int qw, int ng,
+                                         hipStream_t st) {
+#if GV_KWN
+  if (qw == GV_KWN_QW && ng == GV_KWN_NG1)
+    return keys_tables_launch<GV_KWN_QW, GV_KWN_NG1, SL>(n, C, in_x, in_pfx, scratch, with_qe, base, kqtw, kzqw, kC, kok,
+                                                     kqtw2, kzqw2, st);
+  if (qw == GV_KWN_QW)
+    return keys_tables_launch<GV_KWN_QW, GV_KWN_NG2, SL>(n, C, in_x, in_pfx, scratch, with_qe, base, kqtw, kzqw, kC, kok,
+                                                     kqtw2, kzqw2, st);
+#endif
+  if (ng == GV_KW_NG1)
+    return keys_tables_launch<GV_KW_QW, GV_KW_NG1, SL>(n, C, in_x, in_pfx, scratch, with_qe, base, kqtw, kzqw, kC, kok,
+                                                   kqtw2, kzqw2, st);
+  return keys_tables_launch<GV_KW_QW, GV_KW_NG2, SL>(n, C, in_x, in_pfx, scratch, with_qe, base, kqtw, kzqw, kC, kok,
+                                                 kqtw2, kzqw2, st);
+}
+extern "C" {
+
 hipError_t gvk_keys_build_wide(const uint8_t* pub33, uint32_t n, uint32_t C, uint32_t* in_x, uint32_t* in_pfx,
                                uint32_t* in_r, uint32_t* in_s, uint32_t* in_e, uint32_t* scratch, int with_qe,
-                               uint32_t base, uint32_t* kqtw, uint32_t* kzqw, uint32_t kC, uint32_t* kok,
-                               uint32_t* kqtw2, uint32_t* kzqw2, int qw, int ng, hipStream_t st) {
+                               uint32_t base, const uint32_t* slots, uint32_t* kqtw, uint32_t* kzqw, uint32_t kC,
+                               uint32_t* kok, uint32_t* kqtw2, uint32_t* kzqw2, int qw, int ng, hipStream_t st) {
   if (n == 0) return hipSuccess;
   if (!gvk_kw_width_ok(qw) || (ng != gvk_kw_ng(qw, 1) && ng != gvk_kw_ng(qw, 2))) return hipErrorInvalidValue;
   const dim3 blk(256), grd(C / 256);
   hipLaunchKernelGGL(gv::k_unpack, grd, blk, 0, st, pub33, (const uint8_t*)nullptr, (const uint8_t*)nullptr, n, C,
                      in_x, in_pfx, in_r, in_s, in_e);
-#if GV_KWN
-  if (qw == GV_KWN_QW && ng == GV_KWN_NG1)
-    return keys_tables_launch<GV_KWN_QW, GV_KWN_NG1>(n, C, in_x, in_pfx, scratch, with_qe, base, kqtw, kzqw, kC, kok,
-                                                     kqtw2, kzqw2, st);
-  if (qw == GV_KWN_QW)
-    return keys_tables_launch<GV_KWN_QW, GV_KWN_NG2>(n, C, in_x, in_pfx, scratch, with_qe, base, kqtw, kzqw, kC, kok,
-                                                     kqtw2, kzqw2, st);
-#endif
-  if (ng == GV_KW_NG1)
-    return keys_tables_launch<GV_KW_QW, GV_KW_NG1>(n, C, in_x, in_pfx, scratch, with_qe, base, kqtw, kzqw, kC, kok,
-                                                   kqtw2, kzqw2, st);
-  return keys_tables_launch<GV_KW_QW, GV_KW_NG2>(n, C, in_x, in_pfx, scratch, with_qe, base, kqtw, kzqw, kC, kok,
-                                                 kqtw2, kzqw2, st);
+  return slots ? keys_build_wide_launch(n, C, in_x, in_pfx, scratch, with_qe, slots, kqtw, kzqw, kC, kok,
+                                        kqtw2, kzqw2, qw, ng, st)
+               : keys_build_wide_launch(n, C, in_x, in_pfx, scratch, with_qe, base, kqtw, kzqw, kC, kok,
+                                        kqtw2, kzqw2, qw, ng, st);
 }
 
 hipError_t gvk_keys_build(const uint8_t* pub33, uint32_t n, uint32_t C, uint32_t* in_x, uint32_t* in_pfx,
                           uint32_t* in_r, uint32_t* in_s, uint32_t* in_e, uint32_t* scratch, int with_qe,
-                          uint32_t base, uint32_t* kqt, uint32_t* kzq, uint32_t kC, uint32_t* kok, uint32_t* kqt2,
-                          uint32_t* kzq2, hipStream_t st) {
+                          uint32_t base, const uint32_t* slots, uint32_t* kqt, uint32_t* kzq, uint32_t kC,
+                          uint32_t* kok, uint32_t* kqt2, uint32_t* kzq2, hipStream_t st) {
   const dim3 blk(256), grd(C / 256);
   hipLaunchKernelGGL(gv::k_unpack, grd, blk, 0, st, pub33, (const uint8_t*)nullptr, (const uint8_t*)nullptr, n, C,
                      in_x, in_pfx, in_r, in_s, in_e);
-  return keys_tables_launch<GV_QW, GV_LGRP>(n, C, in_x, in_pfx, scratch, with_qe, base, kqt, kzq, kC, kok, kqt2, kzq2,
-                                            st);
+  if (slots)
+    return keys_tables_launch<GV_QW, GV_LGRP>(n, C, in_x, in_pfx, scratch, with_qe, slots, kqt, kzq, kC,
+                                              kok, kqt2, kzq2, st);
+  return keys_tables_launch<GV_QW, GV_LGRP>(n, C, in_x, in_pfx, scratch, with_qe, base, kqt, kzq, kC, kok,
+                                            kqt2, kzq2, st);
 }
 
 hipError_t gvk_keys_build6(const uint8_t* pub33, uint32_t n, uint32_t C, uint32_t* in_x, uint32_t* in_pfx,
                            uint32_t* in_r, uint32_t* in_s, uint32_t* in_e, uint32_t* scratch, int with_qe,
-                           uint32_t base, uint32_t* kqt6, uint32_t* kzq6, uint32_t kC, uint32_t* kok, uint32_t* kqt62,
-                           uint32_t* kzq62, hipStream_t st) {
+                           uint32_t base, const uint32_t* slots, uint32_t* kqt6, uint32_t* kzq6, uint32_t kC,
+                           uint32_t* kok, uint32_t* kqt62, uint32_t* kzq62, hipStream_t st) {
   if (n == 0) return hipSuccess;
   const dim3 blk(256), grd(C / 256);
   hipLaunchKernelGGL(gv::k_unpack, grd, blk, 0, st, pub33, (const uint8_t*)nullptr, (const uint8_t*)nullptr, n, C,
                      in_x, in_pfx, in_r, in_s, in_e);
-  return keys_tables_launch<GV_K6_QW, GV_KN_ARENA_NG>(n, C, in_x, in_pfx, scratch, with_qe, base, kqt6, kzq6, kC, kok,
-                                                       kqt62, kzq62, st);
+  if (slots)
+    return keys_tables_launch<GV_K6_QW, GV_KN_ARENA_NG>(n, C, in_x, in_pfx, scratch, with_qe, slots, kqt6,
+                                                        kzq6, kC, kok, kqt62, kzq62, st);
+  return keys_tables_launch<GV_K6_QW, GV_KN_ARENA_NG>(n, C, in_x, in_pfx, scratch, with_qe, base, kqt6,
+                                                       kzq6, kC, kok, kqt62, kzq62, st);
 }
 
 hipError_t gvk_keys_point(uint32_t n, const uint32_t* slots, const uint32_t* kqt, const uint32_t* kzq, uint32_t kC,

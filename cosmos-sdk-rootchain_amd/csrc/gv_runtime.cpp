@@ -756,6 +756,7 @@ struct gv_ctx {
                                 // a key build ~18 ns vs ~4 ns saved per item, profiles/r03/group_ab)
   size_t keys = 0;              // key-arena slots in use (same on every device)
   std::atomic<uint64_t> keys_gen{0};  // gv_keys_reset calls
+  std::atomic<uint64_t> keys_replaced{0};   // slots gv_keys_replace rewrote since gv_open ("keys_replaced")
   std::mutex keys_mu;
   // ed25519 key arena (gv_ed_keys_load), same on every device
   size_t ed_keys = 0;
@@ -2366,10 +2367,22 @@ int gv_dev_verify_ed25519_msgs(gv_ctx* ctx, int dev_slot, size_t n, const void* 
 
 // ---- key arena
 namespace {
+// A replace chunk's slot list (host, cn entries) to the device: behind the
+// chunk's pub33 in the set's staged-input region (the signature part of
+// in_layout, which a key-table build leaves unused).
+hipError_t stage_slots(Set* s, size_t C, const uint32_t* slots, size_t cn, hipStream_t st, const uint32_t** d_slots) {
+  uint8_t* p = s->d_in + in_layout(C, false, false).sig;
+  *d_slots = (const uint32_t*)p;
+  return hipMemcpyAsync(p, slots, cn * 4, hipMemcpyHostToDevice, st);
+}
+
 // The wide-window tables (layout d->kw_qw / d->kw_ng) of the n keys pub33 (host) into
 // slots base.. of the wide arena, in chunks whose build scratch stays within
-// what the k6 build's chunks take.  The caller holds d->mu.
-int build_wide(gv_ctx* ctx, Dev* d, Set* s, hipStream_t st, const uint8_t* pub33, size_t n, size_t base) {
+// what the k6 build's chunks take.  slots (host, n entries; null: append):
+// key i goes to slot slots[i] instead (gv_keys_replace; each chunk's list
+// rides behind its pub33 in the staged-input region).  The caller holds d->mu.
+int build_wide(gv_ctx* ctx, Dev* d, Set* s, hipStream_t st, const uint8_t* pub33, size_t n, size_t base,
+               const uint32_t* slots = nullptr) {
   const size_t stepw = std::min<size_t>(ctx->max_batch, std::max<size_t>(256, 32768 / (size_t)d->kw_ng / 256 * 256));
   int rc;
   for (size_t c0 = 0; c0 < n; c0 += stepw) {
@@ -2381,8 +2394,10 @@ int build_wide(gv_ctx* ctx, Dev* d, Set* s, hipStream_t st, const uint8_t* pub33
     if ((rc = ensure_cap(s, Cs))) return rc;
     if ((rc = set_acquire(s, st))) return rc;
     CK(hipMemcpyAsync(s->d_in, pub33 + c0 * 33, cn * 33, hipMemcpyHostToDevice, st));
+    const uint32_t* d_slots = nullptr;
+    if (slots) CK(stage_slots(s, C, slots + c0, cn, st, &d_slots));
     CK(gvk_keys_build_wide(s->d_in, (uint32_t)cn, (uint32_t)C, s->in_x, s->in_pfx, s->in_r, s->in_s, s->in_e, s->qtab,
-                           qew, (uint32_t)(base + c0), d->kqtw, d->kzqw, (uint32_t)d->kcapw, d->kok, d->kqtw2,
+                           qew, (uint32_t)(base + c0), d_slots, d->kqtw, d->kzqw, (uint32_t)d->kcapw, d->kok, d->kqtw2,
                            d->kzqw2, d->kw_qw, d->kw_ng, st));
     if ((rc = set_release(s, st))) return rc;
     CK(hipStreamSynchronize(st));
@@ -2463,11 +2478,11 @@ int gv_keys_load(gv_ctx* ctx, size_t n, const uint8_t* pub33, uint32_t* slot_out
       const size_t room = (size_t)GV_QTAB_WORDS * s->cap;
       const int qe4 = ctx->keys_scratch && gvk_keys_scratch_words((uint32_t)cn, GV_LGRP, GV_QTAB_N, 1) <= room;
       CK(gvk_keys_build(s->d_in, (uint32_t)cn, (uint32_t)C, s->in_x, s->in_pfx, s->in_r, s->in_s, s->in_e,
-                        s->qtab, qe4, (uint32_t)(base + c0), d->kqt, d->kzq,
+                        s->qtab, qe4, (uint32_t)(base + c0), nullptr, d->kqt, d->kzq,
                         (uint32_t)d->kcap, d->kok, d->kqt2, d->kzq2, st));
       if (k6)
         CK(gvk_keys_build6(s->d_in, (uint32_t)cn, (uint32_t)C, s->in_x, s->in_pfx, s->in_r, s->in_s, s->in_e,
-                           s->qtab, ctx->keys_scratch ? 1 : 0, (uint32_t)(base + c0), d->kqt6, d->kzq6,
+                           s->qtab, ctx->keys_scratch ? 1 : 0, (uint32_t)(base + c0), nullptr, d->kqt6, d->kzq6,
                            (uint32_t)d->kcap, d->kok, d->kqt62, d->kzq62, st));
       if ((rc = set_release(s, st))) return rc;
       CK(hipStreamSynchronize(st));            // the caller's pub33 chunk is read by then
@@ -2526,6 +2541,90 @@ int gv_keys_load(gv_ctx* ctx, size_t n, const uint8_t* pub33, uint32_t* slot_out
   }
   ctx->keys = base + n;
   for (size_t i = 0; i < n; ++i) slot_out[i] = (uint32_t)(base + i);
+  return GV_OK;
+}
+
+int gv_keys_replace(gv_ctx* ctx, size_t n, const uint32_t* slots, const uint8_t* pub33) {
+  if (!ctx) return GV_EINVAL;
+  if (n == 0) return GV_OK;
+  if (!slots || !pub33) return GV_EINVAL;
+  AsyncQuiesce q(ctx);                          // a batch already submitted runs against the old keys
+  std::lock_guard<std::mutex> kl(ctx->keys_mu);
+  // every check before the first device write: each slot loaded, none twice
+  // (two lanes would write one row; k_keys_tables reads a kzq column before
+  // lane 0 overwrites it)
+  const size_t count = ctx->keys;
+  if (n > count) return GV_EINVAL;
+  {
+    std::vector<uint64_t> seen((count + 63) / 64, 0);
+    for (size_t i = 0; i < n; ++i) {
+      const size_t sl = slots[i];
+      if (sl >= count || (seen[sl >> 6] >> (sl & 63) & 1)) return GV_EINVAL;
+      seen[sl >> 6] |= (uint64_t)1 << (sl & 63);
+    }
+  }
+  std::vector<uint32_t> fs;                     // the slots (and their keys) below a table set's built prefix
+  std::vector<uint8_t> fp;
+  for (Dev* d : ctx->devs) {                    // every device holds every key
+    std::lock_guard<std::mutex> lk(d->mu);
+    CK(hipSetDevice(d->id));
+    Set* s = &d->set[0];
+    hipStream_t st = s->st;
+    for (hipStream_t t : d->hi_st) CK(hipStreamSynchronize(t));   // no pipelined ladder reads a row being rewritten
+    if (count > d->kcap || d->keys6 > d->kcap || d->keysw > d->kcapw) return GV_EINVAL;   // (never: the arenas hold their slots)
+    int rc;
+    // which: 0 the k4 tables (every slot), 1 the k6 tables (slots below keys6),
+    // 2 the wide tables in the arena's layout (slots below keysw); the chunks of gv_keys_load
+    for (int which = 0; which < 3; ++which) {
+      const size_t lim = which == 0 ? count : which == 1 ? (d->kqt6 ? d->keys6 : 0) : (d->kqtw ? d->keysw : 0);
+      if (lim == 0) continue;
+      const uint32_t* sl = slots;
+      const uint8_t* pb = pub33;
+      size_t m = n;
+      if (lim < count) {
+        fs.clear();
+        fp.clear();
+        for (size_t i = 0; i < n; ++i)
+          if (slots[i] < lim) {
+            fs.push_back(slots[i]);
+            fp.insert(fp.end(), pub33 + i * 33, pub33 + (i + 1) * 33);
+          }
+        sl = fs.data();
+        pb = fp.data();
+        m = fs.size();
+      }
+      if (which == 2) {
+        if ((rc = build_wide(ctx, d, s, st, pb, m, 0, sl))) return rc;
+        continue;
+      }
+      const size_t step = which == 1 ? std::min<size_t>(ctx->max_batch, 32768) : ctx->max_batch;
+      for (size_t c0 = 0; c0 < m; c0 += step) {
+        const size_t cn = std::min(step, m - c0);
+        const size_t C = round_up(cn, 256);
+        const size_t ww = which == 1 ? gvk_keys_scratch_words((uint32_t)cn, GV_KN_ARENA_NG, GV_K6_NT, 1)
+                                     : gvk_keys_scratch_words((uint32_t)cn, GV_LGRP, GV_QTAB_N, 0);
+        const size_t Cs = std::max(C, round_up(ww / GV_QTAB_WORDS + 1, 256));
+        if ((rc = ensure_cap(s, Cs))) return rc;
+        if ((rc = set_acquire(s, st))) return rc;
+        CK(hipMemcpyAsync(s->d_in, pb + c0 * 33, cn * 33, hipMemcpyHostToDevice, st));
+        const uint32_t* d_slots = nullptr;
+        CK(stage_slots(s, C, sl + c0, cn, st, &d_slots));
+        if (which == 0) {
+          const size_t room = (size_t)GV_QTAB_WORDS * s->cap;
+          const int qe4 = ctx->keys_scratch && gvk_keys_scratch_words((uint32_t)cn, GV_LGRP, GV_QTAB_N, 1) <= room;
+          CK(gvk_keys_build(s->d_in, (uint32_t)cn, (uint32_t)C, s->in_x, s->in_pfx, s->in_r, s->in_s, s->in_e, s->qtab,
+                            qe4, 0u, d_slots, d->kqt, d->kzq, (uint32_t)d->kcap, d->kok, d->kqt2, d->kzq2, st));
+        } else {
+          CK(gvk_keys_build6(s->d_in, (uint32_t)cn, (uint32_t)C, s->in_x, s->in_pfx, s->in_r, s->in_s, s->in_e, s->qtab,
+                             ctx->keys_scratch ? 1 : 0, 0u, d_slots, d->kqt6, d->kzq6, (uint32_t)d->kcap, d->kok,
+                             d->kqt62, d->kzq62, st));
+        }
+        if ((rc = set_release(s, st))) return rc;
+        CK(hipStreamSynchronize(st));            // the caller's chunk is read by then
+      }
+    }
+  }
+  ctx->keys_replaced.fetch_add(n);
   return GV_OK;
 }
 
@@ -2921,6 +3020,7 @@ int gv_get_option(gv_ctx* ctx, const char* key, long long* val) {
               {"lat_kw", ctx->lat_kw},
               {"keys_wide_qw", ctx->keys_wide_qw},
               {"keys_wide_mb", (long long)(ctx->keys_wide_bytes >> 20)},
+              {"keys_replaced", (long long)ctx->keys_replaced.load()},   // read-only: gv_keys_replace's slots so far
               {"kw_qw", GV_KW_QW},                   // read-only: the wide arena's window width (build)
               {"kwn_qw", GV_KWN ? GV_KWN_QW : 0}};   // read-only: its narrow width (build; 0: not compiled)
   // read-only: the first device's wide arena as gv_keys_load left it -- its

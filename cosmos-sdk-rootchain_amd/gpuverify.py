@@ -43,7 +43,7 @@ EXPORTED_SYMBOLS = (
     "gv_set_option", "gv_get_option", "gv_last_stage_ms", "gv_strerror", "gv_debug_op", "gv_dev_alloc", "gv_dev_free",
     "gv_dev_copy", "gv_dev_sync", "gv_stage_stats", "gv_keys_load", "gv_keys_reset", "gv_keys_count", "gv_keys_generation",
     "gv_verify_digests_keyed", "gv_verify_msgs_keyed", "gv_dev_verify_digests_keyed", "gv_stage_stats4",
-    "gv_keys_point", "gv_dev_stream_create", "gv_dev_stream_sync", "gv_dev_stream_destroy",
+    "gv_keys_point", "gv_keys_replace", "gv_dev_stream_create", "gv_dev_stream_sync", "gv_dev_stream_destroy",
     "gv_verify_ed25519_msgs", "gv_dev_verify_ed25519_msgs", "gv_last_slices", "gv_group_stats", "gv_route_stats", "gv_host_alloc", "gv_host_free",
     "gv_ed_keys_load", "gv_ed_keys_reset", "gv_ed_keys_count", "gv_ed_keys_generation", "gv_verify_ed25519_msgs_keyed",
     "gv_submit_digests", "gv_submit_digests_keyed", "gv_submit_msgs", "gv_submit_msgs_keyed", "gv_wait",
@@ -154,6 +154,8 @@ def load(path: str = LIB_PATH):
     L.gv_keys_generation.restype = ctypes.c_uint64
     L.gv_keys_point.argtypes = [vp, sz, vp, vp, vp]
     L.gv_keys_point.restype = i32
+    L.gv_keys_replace.argtypes = [vp, sz, vp, vp]
+    L.gv_keys_replace.restype = i32
     L.gv_verify_digests_keyed.argtypes = [vp, sz, vp, vp, vp, vp]
     L.gv_verify_digests_keyed.restype = i32
     L.gv_verify_msgs_keyed.argtypes = [vp, sz, vp, vp, vp, vp, vp, vp]
@@ -359,12 +361,32 @@ class Verifier:
             _check(self._L.gv_keys_point(self._ctx, n, _ptr(slots), _ptr(xy), _ptr(ok)), "gv_keys_point")
         return xy, ok
 
+    def keys_replace(self, slots: np.ndarray, pub33: np.ndarray):
+        """Rebuild loaded slots in place: slot slots[i] then holds key pub33[i] as if it had been
+        loaded there (keys_count, keys_generation and the arena's layout do not move: the caller
+        keeps its own pubkey -> slot map right).  Slots must be loaded and distinct."""
+        slots = np.ascontiguousarray(slots)
+        pub33 = np.ascontiguousarray(pub33)
+        if slots.ndim != 1 or slots.dtype.kind not in "ui" or (slots.size and (slots.min() < 0 or slots.max() >= 2 ** 32)):
+            raise ValueError("keys_replace: slots must be a 1-d array of u32 slot numbers")
+        if pub33.dtype != np.uint8 or pub33.ndim != 2 or pub33.shape[1] != 33:
+            raise ValueError("keys_replace: pub33 must be an (n, 33) uint8 array")
+        if pub33.shape[0] != slots.shape[0]:
+            raise ValueError(f"keys_replace: {slots.shape[0]} slots for {pub33.shape[0]} keys")
+        slots = np.ascontiguousarray(slots, dtype=np.uint32)
+        n = slots.shape[0]
+        if n:
+            _check(self._L.gv_keys_replace(self._ctx, n, _ptr(slots), _ptr(pub33)), "gv_keys_replace")
+
     def keys_reset(self):
         _check(self._L.gv_keys_reset(self._ctx), "gv_keys_reset")
 
     @property
     def keys_count(self) -> int:
         return self._L.gv_keys_count(self._ctx)
+
+    def keys_generation(self) -> int:
+        return self._L.gv_keys_generation(self._ctx)
 
     def verify_batch_digests_keyed(self, slots: np.ndarray, sig64: np.ndarray, dig32: np.ndarray) -> np.ndarray:
         slots = np.ascontiguousarray(slots, dtype=np.uint32)

@@ -80,6 +80,10 @@ def lib():
         L.gvh_cache_clear.argtypes = [vp]
         L.gvh_set_threads.argtypes = [vp, ctypes.c_int]
         L.gvh_set_keyed.argtypes = [vp, ctypes.c_int, ctypes.c_size_t]
+        L.gvh_set_key_resident.argtypes = [vp, ctypes.c_size_t]
+        L.gvh_set_key_resident.restype = None
+        L.gvh_get_key_stats.argtypes = [vp, ctypes.POINTER(sz), ctypes.POINTER(u64), ctypes.POINTER(u64)]
+        L.gvh_get_key_stats.restype = None
         L.gvh_set_gpu_hash.argtypes = [vp, ctypes.c_int]
         L.gvh_get_gpu_hash.argtypes = [vp]
         L.gvh_get_keyed.argtypes = [vp, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(sz), ctypes.POINTER(sz)]
@@ -336,6 +340,17 @@ class HostApp:
         """secp256k1 leaves through the GPU context's key arena (default; keys loaded by
         batches of >= load_min leaves) or as pub33 batches."""
         self._L.gvh_set_keyed(self._app, 1 if keyed else 0, load_min)
+
+    def set_key_resident(self, resident: int):
+        """Keep the key arena at `resident` slots: fresh keys past it replace the victims of a
+        second-chance clock (gv_keys_replace); 0 (default): off."""
+        self._L.gvh_set_key_resident(self._app, resident)
+
+    def key_stats(self):
+        """(resident size in force, slots replaced, arena resets)"""
+        r, rep, rs = ctypes.c_size_t(), ctypes.c_uint64(), ctypes.c_uint64()
+        self._L.gvh_get_key_stats(self._app, ctypes.byref(r), ctypes.byref(rep), ctypes.byref(rs))
+        return r.value, rep.value, rs.value
 
     def set_gpu_hash(self, on: bool):
         """delivered blocks with an empty verdict cache: secp256k1 sign bytes hashed

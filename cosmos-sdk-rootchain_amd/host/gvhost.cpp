@@ -38,6 +38,10 @@
 #include <unordered_map>
 #include <vector>
 
+// gv_keys_replace through a weak reference: a library that does not define
+// it (the sanitizer harness' CPU stand-in) leaves eviction off.
+extern "C" int gv_keys_replace(gv_ctx* ctx, size_t n, const uint32_t* slots, const uint8_t* pub33) __attribute__((weak));
+
 namespace {
 
 using Bytes = std::vector<uint8_t>;
@@ -1523,6 +1527,26 @@ struct gvh_app {
   size_t key_cap = GV_KEY_CAP;                 // arena reset past this many keys (5.4 KB of HBM each)
   size_t key_load_min = GV_KEY_LOAD_MIN;       // smaller batches never load keys (k_keys_build's ~ms latency):
                                                // keyed only when all their keys are resident
+  // Eviction (gvh_set_key_resident; 0 = off): the arena is never loaded past
+  // key_resident slots -- a block's fresh keys beyond the free slots replace
+  // victims of a second-chance clock (gv_keys_replace).  Per slot: the key it
+  // holds (the map's reverse), a reference bit set by every batch that names
+  // the slot, and the stamp of the last such batch (a slot named by the batch
+  // in hand is never a victim).  key_epoch moves with every replacement: a
+  // batch packed before it looks its slots up again.  All under key_mu.
+  size_t key_resident = 0;
+  std::vector<std::array<uint8_t, 33>> slot_key;
+  std::vector<uint8_t> slot_ref;
+  std::vector<uint64_t> slot_stamp;
+  size_t clock_hand = 0;
+  uint64_t batch_stamp = 0, key_epoch = 0;
+  uint64_t keys_replaced = 0, key_resets = 0;
+  void clock_clear() {
+    slot_key.clear();
+    slot_ref.clear();
+    slot_stamp.clear();
+    clock_hand = 0;
+  }
   int threads = std::max(1, std::min(16, (int)std::thread::hardware_concurrency()));
   std::unique_ptr<Pool> pool{new Pool(threads - 1)};
   std::mutex pool_mu;                          // guards replacing the pool (gvh_set_threads)
@@ -1883,8 +1907,8 @@ struct GpuBatch {
   uint8_t* blob = nullptr;
   uint64_t* moff = nullptr;
   uint32_t* mlen = nullptr;
-  bool looked_up = false;                      // slots filled against arena generation `gen`
-  uint64_t gen = 0;
+  bool looked_up = false;                      // slots filled against arena generation `gen`, eviction epoch `epoch`
+  uint64_t gen = 0, epoch = 0;
   std::vector<uint8_t> epub, esig, eok, eblob;
   std::vector<uint64_t> eoff;
   std::vector<uint32_t> elen;
@@ -1954,6 +1978,7 @@ void batch_pack(gvh_app* app, GpuBatch& b) {
     std::shared_lock<std::shared_mutex> rk(app->key_mu);
     const bool look = app->keyed && app->gpu && gv_keys_generation(app->gpu) == app->key_gen;
     b.gen = app->key_gen;
+    b.epoch = app->key_epoch;
     b.looked_up = look;
     auto& map = app->key_slots;
     parallel_for(app, m, [&](size_t k) {
@@ -1997,6 +2022,10 @@ void batch_pack(gvh_app* app, GpuBatch& b) {
 // (a key ParsePubKey rejects keeps a false slot), without the per-item
 // decompression and Q-table build, on the 4-group ladder.  Any arena problem
 // (cap reached, load error) falls back to the pub33 batch for this call.
+// With a resident size (gvh_set_key_resident) the arena stops growing there:
+// a block's fresh keys take the free slots, the rest replace the clock's
+// victims with one gv_keys_replace; when the sweep finds too few victims the
+// batch takes the pub33 path and nothing changes.
 // ticket: queue the batch (gv_submit_*) instead of verifying it; the caller
 // waits for *ticket (gv_wait) before it reads b.ok.  A batch queued keyed
 // stays valid across a later gv_keys_load / gv_keys_reset: the library runs
@@ -2017,13 +2046,36 @@ int verify_secp(gvh_app* app, GpuBatch& b, uint64_t* ticket = nullptr) {
   const uint64_t gen = gv_keys_generation(app->gpu);
   if (gen != app->key_gen) {                      // the arena was reset (here or by another user)
     map.clear();
+    app->clock_clear();
     app->key_gen = gen;
   }
-  if (!b.looked_up || b.gen != gen)               // packed against another arena: look up again
-    for (size_t k = 0; k < m; ++k) {
+  if (!b.looked_up || b.gen != gen || b.epoch != app->key_epoch)   // packed against another arena, or slots
+    for (size_t k = 0; k < m; ++k) {                                // have changed hands since: look up again
       const uint32_t* v = map.find(b.pub + 33 * k);
       b.slots[k] = v ? *v : UINT32_MAX;
     }
+  const bool evict = app->key_resident > 0 && gv_keys_replace != nullptr;
+  uint64_t stamp = 0;
+  auto touch = [&](uint32_t slot) {               // this batch names the slot
+    if (slot >= app->slot_ref.size()) return;
+    app->slot_ref[slot] = 1;
+    app->slot_stamp[slot] = stamp;
+  };
+  auto holds = [&](uint32_t slot, const uint8_t* key) {   // the slot now holds key (map and reverse array together)
+    if (slot >= app->slot_key.size()) {
+      app->slot_key.resize(slot + 1, {});
+      app->slot_ref.resize(slot + 1, 0);
+      app->slot_stamp.resize(slot + 1, 0);
+    }
+    memcpy(app->slot_key[slot].data(), key, 33);
+    map.set(key, slot);
+    touch(slot);
+  };
+  if (evict) {
+    stamp = ++app->batch_stamp;
+    for (size_t k = 0; k < m; ++k)
+      if (b.slots[k] != UINT32_MAX) touch(b.slots[k]);
+  }
   if (m < app->key_load_min) {                    // small batch (CheckTx window, per-tx ante)
     bool all = true;
     for (size_t k = 0; k < m && all; ++k) all = b.slots[k] != UINT32_MAX;
@@ -2045,18 +2097,80 @@ int verify_secp(gvh_app* app, GpuBatch& b, uint64_t* ticket = nullptr) {
   if (!fresh_keys.empty()) {
     const size_t nf = fresh_keys.size();
     std::vector<uint32_t> got(nf);
-    const bool room = gv_keys_count(app->gpu) + nf <= app->key_cap;
-    if (!room || gv_keys_load(app->gpu, nf, fresh.data(), got.data()) != GV_OK) {
+    const size_t count = gv_keys_count(app->gpu);
+    const size_t free_slots = !evict ? nf : count < app->key_resident ? app->key_resident - count : 0;
+    const size_t nl = std::min(nf, free_slots), nv = nf - nl;   // loaded into free slots / put into victims' slots
+    auto drop_pending = [&] {
+      for (auto& key : fresh_keys) map.erase(key.data());
+    };
+    std::vector<uint32_t> victims, cleared;
+    if (nv) {
+      // second-chance sweep from the persistent hand over the loaded slots:
+      // two turns at most (the first clears reference bits, the second takes)
+      const size_t span = std::min(count, app->slot_key.size());
+      const size_t hand0 = app->clock_hand;
+      size_t h = span ? hand0 % span : 0;
+      for (size_t step = 0; step < 2 * span && victims.size() < nv; ++step, h = (h + 1) % span) {
+        if (app->slot_stamp[h] == stamp) continue;   // named by the batch in hand
+        if (app->slot_ref[h]) {
+          app->slot_ref[h] = 0;
+          cleared.push_back((uint32_t)h);
+        } else {
+          victims.push_back((uint32_t)h);
+          app->slot_stamp[h] = stamp;                // (taken: not twice in one sweep)
+        }
+      }
+      if (victims.size() < nv) {                     // too few evictable slots: nothing changes
+        for (uint32_t v : victims) app->slot_stamp[v] = 0;
+        for (uint32_t c : cleared) app->slot_ref[c] = 1;
+        app->clock_hand = hand0;
+        drop_pending();
+        return plain();
+      }
+      app->clock_hand = h;
+#ifdef GVH_EVICT_AUDIT
+      for (size_t k = 0; k < m; ++k)                 // no slot the batch names is a victim
+        for (uint32_t v : victims)
+          if (b.slots[k] == v) abort();
+#endif
+    }
+    const bool room = count + nl <= app->key_cap;
+    if (!room || (nl && gv_keys_load(app->gpu, nl, fresh.data(), got.data()) != GV_OK)) {
       if (!room) {                                  // start the arena over; this call takes the pub33 path
         gv_keys_reset(app->gpu);
         map.clear();
+        app->clock_clear();
+        app->key_resets++;
         app->key_gen = gv_keys_generation(app->gpu);
       } else {
-        for (auto& key : fresh_keys) map.erase(key.data());
+        for (uint32_t v : victims) app->slot_stamp[v] = 0;
+        for (uint32_t c : cleared) app->slot_ref[c] = 1;
+        drop_pending();
       }
       return plain();
     }
-    for (size_t i = 0; i < nf; ++i) map.set(fresh_keys[i].data(), got[i]);
+    if (nv && gv_keys_replace(app->gpu, nv, victims.data(), fresh.data() + 33 * nl) != GV_OK) {
+      gv_keys_reset(app->gpu);                      // no slot named in a failed replacement is trusted
+      map.clear();
+      app->clock_clear();
+      app->key_resets++;
+      app->key_gen = gv_keys_generation(app->gpu);
+      return plain();
+    }
+    if (evict) {
+      for (size_t i = 0; i < nl; ++i) holds(got[i], fresh_keys[i].data());
+      for (size_t i = 0; i < nv; ++i) {             // erase the victim's key, set the fresh key
+        map.erase(app->slot_key[victims[i]].data());
+        got[nl + i] = victims[i];
+        holds(victims[i], fresh_keys[nl + i].data());
+      }
+      if (nv) {
+        app->key_epoch++;
+        app->keys_replaced += nv;
+      }
+    } else {
+      for (size_t i = 0; i < nf; ++i) map.set(fresh_keys[i].data(), got[i]);
+    }
     for (size_t k = 0; k < m; ++k)
       if (b.slots[k] >= kPending) b.slots[k] = got[b.slots[k] - kPending];
   }
@@ -3167,6 +3281,28 @@ void gvh_set_keyed(gvh_app* app, int keyed, size_t load_min) {
   std::unique_lock<std::shared_mutex> wk(app->key_mu);
   app->keyed = keyed != 0;
   app->key_load_min = load_min;
+}
+
+void gvh_set_key_resident(gvh_app* app, size_t resident) {
+  std::lock_guard<std::mutex> g(app->gpu_mu);
+  std::unique_lock<std::shared_mutex> wk(app->key_mu);
+  if (!gv_keys_replace) resident = 0;             // a library without gv_keys_replace: eviction stays off
+  if (resident == app->key_resident) return;
+  // the clock starts from an empty arena: slots loaded before carry no reverse entry
+  if (resident && app->gpu && app->keyed && gv_keys_count(app->gpu)) {
+    gv_keys_reset(app->gpu);
+    app->key_slots.clear();
+    app->key_gen = gv_keys_generation(app->gpu);
+  }
+  app->clock_clear();
+  app->key_resident = resident;
+}
+void gvh_get_key_stats(gvh_app* app, size_t* resident, uint64_t* replaced, uint64_t* resets) {
+  std::lock_guard<std::mutex> g(app->gpu_mu);
+  std::shared_lock<std::shared_mutex> rk(app->key_mu);
+  if (resident) *resident = app->key_resident;
+  if (replaced) *replaced = app->keys_replaced;
+  if (resets) *resets = app->key_resets;
 }
 
 void gvh_set_gpu_hash(gvh_app* app, int on) {

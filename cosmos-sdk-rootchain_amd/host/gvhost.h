@@ -170,6 +170,21 @@ void gvh_set_threads(gvh_app* app, int threads);
  * verdicts either way.  While keyed, the app owns the context's key arena
  * (a gv_keys_reset elsewhere is detected by gv_keys_generation). */
 void gvh_set_keyed(gvh_app* app, int keyed, size_t load_min);
+/* resident > 0: the keyed path never loads the arena past `resident` slots.
+ * When a block-sized batch brings more fresh keys than free slots remain, the
+ * rest replace victims of a second-chance clock over the slots with one
+ * gv_keys_replace (a slot named by the batch in hand is never a victim; the
+ * hand persists across batches); a batch whose fresh keys outnumber the
+ * evictable slots takes the pub33 path and changes nothing.  The arena then
+ * keeps the wide-table layout it has at `resident` keys whatever the number
+ * of accounts seen.  0 (default): off -- the arena grows to key_cap and is
+ * reset there.  Changing the size while keys are resident starts the arena
+ * over.  Same verdicts either way.  Against a library without
+ * gv_keys_replace the setting stays 0. */
+void gvh_set_key_resident(gvh_app* app, size_t resident);
+/* The resident size in force, the slots replaced and the arena resets (cap
+ * reached, failed replacement) since the app was made. */
+void gvh_get_key_stats(gvh_app* app, size_t* resident, uint64_t* replaced, uint64_t* resets);
 /* gpu_hash = 1: PreVerifyTxs of a block being delivered, with an empty
  * verdict cache, hands the secp256k1 leaves' sign bytes to the GPU
  * (gv_verify_msgs / gv_verify_msgs_keyed, SHA-256 in the batch) instead of

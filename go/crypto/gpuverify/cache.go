@@ -4,6 +4,8 @@ import (
 	"container/list"
 	"crypto/sha256"
 	"sync"
+
+	"github.com/tendermint/tendermint/crypto/secp256k1"
 )
 
 // Leaf kinds in a verdict-cache key.
@@ -82,4 +84,84 @@ func (c *VerdictCache) Len() int {
 	c.mu.Lock()
 	defer c.mu.Unlock()
 	return c.ll.Len()
+}
+
+// slotClock is the second-chance clock over the key arena's slots (GPU
+// KeyResident; the C++ mirror's rule, host/gvhost.cpp verify_secp): per slot
+// the key it holds (the slot map's reverse), a reference bit set by every
+// batch that names the slot, and the stamp of the last such batch.  The hand
+// persists across batches.  Guarded by GPU.mu.
+type slotClock struct {
+	keys  []secp256k1.PubKeySecp256k1
+	ref   []bool
+	stamp []uint64
+	hand  int
+	batch uint64
+}
+
+func (c *slotClock) reset() { c.keys, c.ref, c.stamp, c.hand = nil, nil, nil, 0 }
+
+// begin starts a batch: the slots it touches are never its victims.
+func (c *slotClock) begin() { c.batch++ }
+
+func (c *slotClock) touch(slot uint32) {
+	if int(slot) < len(c.ref) {
+		c.ref[slot], c.stamp[slot] = true, c.batch
+	}
+}
+
+// hold records that slot now holds key, named by the batch in hand.
+func (c *slotClock) hold(slot uint32, key secp256k1.PubKeySecp256k1) {
+	for int(slot) >= len(c.keys) {
+		c.keys = append(c.keys, secp256k1.PubKeySecp256k1{})
+		c.ref = append(c.ref, false)
+		c.stamp = append(c.stamp, 0)
+	}
+	c.keys[slot] = key
+	c.touch(slot)
+}
+
+// victims sweeps from the hand over the first count slots -- two turns at
+// most: the first clears reference bits, the second takes -- for need slots
+// the batch in hand does not name.  nil when there are too few (nothing
+// changed); undo puts the sweep back when the caller cannot use the victims.
+func (c *slotClock) victims(count, need int) (v []uint32, undo func()) {
+	if need == 0 {
+		return nil, func() {}
+	}
+	span := count
+	if span > len(c.keys) {
+		span = len(c.keys)
+	}
+	hand0, h := c.hand, 0
+	if span > 0 {
+		h = c.hand % span
+	}
+	var cleared []uint32
+	for step := 0; step < 2*span && len(v) < need; step, h = step+1, (h+1)%span {
+		switch {
+		case c.stamp[h] == c.batch:
+		case c.ref[h]:
+			c.ref[h] = false
+			cleared = append(cleared, uint32(h))
+		default:
+			v = append(v, uint32(h))
+			c.stamp[h] = c.batch
+		}
+	}
+	undo = func() {
+		for _, s := range v {
+			c.stamp[s] = 0
+		}
+		for _, s := range cleared {
+			c.ref[s] = true
+		}
+		c.hand = hand0
+	}
+	if len(v) < need {
+		undo()
+		return nil, func() {}
+	}
+	c.hand = h
+	return v, undo
 }

@@ -26,6 +26,7 @@ import "C"
 
 import (
 	"errors"
+	"fmt"
 	"math/bits"
 	"os"
 	"strconv"
@@ -132,13 +133,14 @@ type Stats struct {
 	FallbackCalls, FallbackLeaves   uint64 // library errors: leaves re-verified on the CPU (fail closed)
 	KeyedCalls, Pub33Calls, EdCalls uint64
 	KeyLoads, KeyResets             uint64
+	KeyReplaced                     uint64 // slots rewritten by gv_keys_replace (KeyResident)
 	BatchLog2                       [24]uint64
 	LatencyUsLog2                   [24]uint64
 }
 
 type counters struct {
 	gpuCalls, gpuLeaves, cpuRouted, cpuRoutedLeaves, fbCalls, fbLeaves uint64
-	keyed, pub33, ed, keyLoads, keyResets                             uint64
+	keyed, pub33, ed, keyLoads, keyResets, keyReplaced                uint64
 	batch, lat                                                        [24]uint64
 }
 
@@ -181,7 +183,7 @@ func (g *GPU) Stats() Stats {
 		FallbackCalls: atomic.LoadUint64(&c.fbCalls), FallbackLeaves: atomic.LoadUint64(&c.fbLeaves),
 		KeyedCalls: atomic.LoadUint64(&c.keyed), Pub33Calls: atomic.LoadUint64(&c.pub33),
 		EdCalls: atomic.LoadUint64(&c.ed), KeyLoads: atomic.LoadUint64(&c.keyLoads),
-		KeyResets: atomic.LoadUint64(&c.keyResets),
+		KeyResets: atomic.LoadUint64(&c.keyResets), KeyReplaced: atomic.LoadUint64(&c.keyReplaced),
 	}
 	for k := range s.BatchLog2 {
 		s.BatchLog2[k] = atomic.LoadUint64(&c.batch[k])
@@ -216,6 +218,12 @@ type GPU struct {
 	KeyLoadMin int
 	// KeyCap: the arena is reset when a load would take it past this many keys.
 	KeyCap int
+	// KeyResident: keep the arena at this many slots (0 = off, the default):
+	// a block's fresh keys beyond the free slots replace the victims of a
+	// second-chance clock over the slots (gv_keys_replace), so the arena keeps
+	// the wide-table layout it has at that size whatever the number of
+	// accounts seen.  Set before the first keyed batch.
+	KeyResident int
 	// EdKeyCap: the same for the ed25519 key arena (72 KB of HBM per key;
 	// default GV_ED_KEY_CAP, env GV_ED_KEY_CAP).
 	EdKeyCap int
@@ -233,6 +241,7 @@ type GPU struct {
 	mu      sync.Mutex                           // the slot maps AND every keyed call (no reset in between)
 	slots   map[secp256k1.PubKeySecp256k1]uint32 // key -> key-arena slot (gv_keys_load)
 	slotGen uint64                               // gv_keys_generation the slot map belongs to
+	clock   slotClock                            // KeyResident: the slots' keys, reference bits and the hand
 	edSlots map[ed25519.PubKeyEd25519]uint32     // ed25519 key -> ed25519 key-arena slot (gv_ed_keys_load)
 	edGen   uint64                               // gv_ed_keys_generation the ed25519 map belongs to
 }
@@ -685,15 +694,22 @@ func (g *GPU) slotsLocked(pubs []secp256k1.PubKeySecp256k1, load bool) (slots []
 	if gen := uint64(C.gv_keys_generation(g.ctx)); gen != g.slotGen {
 		// the arena was reset elsewhere: every cached slot may name another key now
 		g.slots = map[secp256k1.PubKeySecp256k1]uint32{}
+		g.clock.reset()
 		g.slotGen = gen
 	}
 	slots = make([]uint32, len(pubs))
 	loaded = make([]bool, len(pubs))
 	var fresh []secp256k1.PubKeySecp256k1
 	seen := map[secp256k1.PubKeySecp256k1]bool{}
+	if g.KeyResident > 0 {
+		g.clock.begin()
+	}
 	for i, p := range pubs {
 		if s, ok := g.slots[p]; ok {
 			slots[i], loaded[i] = s, true
+			if g.KeyResident > 0 {
+				g.clock.touch(s)
+			}
 		} else if !seen[p] {
 			seen[p] = true
 			fresh = append(fresh, p)
@@ -704,6 +720,9 @@ func (g *GPU) slotsLocked(pubs []secp256k1.PubKeySecp256k1, load bool) (slots []
 	}
 	if !load {
 		return slots, loaded, false
+	}
+	if g.KeyResident > 0 {
+		return g.slotsEvictLocked(pubs, fresh, slots, loaded)
 	}
 	if int(C.gv_keys_count(g.ctx))+len(fresh) > g.KeyCap { // start the arena over (the C++ mirror's rule)
 		atomic.AddUint64(&g.cnt.keyResets, 1)
@@ -736,6 +755,93 @@ func (g *GPU) slotsLocked(pubs []secp256k1.PubKeySecp256k1, load bool) (slots []
 	return slots, loaded, all
 }
 
+// slotsEvictLocked is the load step of slotsLocked under KeyResident (g.mu
+// held; the C++ mirror's rule, host/gvhost.cpp verify_secp): the fresh keys
+// take the free slots up to KeyResident with one gv_keys_load, the rest
+// replace the clock's victims with one gv_keys_replace -- a slot named by
+// this batch is never a victim.  When the sweep finds too few victims nothing
+// changes and the fresh keys' leaves go by pub33.  The slot map and the
+// clock's slot -> key array move together; g.mu covers every keyed verify, so
+// no batch runs against a slot that changes hands under it.
+func (g *GPU) slotsEvictLocked(pubs, fresh []secp256k1.PubKeySecp256k1, slots []uint32, loaded []bool) ([]uint32, []bool, bool) {
+	count := int(C.gv_keys_count(g.ctx))
+	free := 0
+	if count < g.KeyResident {
+		free = g.KeyResident - count
+	}
+	nl := len(fresh)
+	if nl > free {
+		nl = free
+	}
+	victims, undo := g.clock.victims(count, len(fresh)-nl)
+	if victims == nil && len(fresh) > nl {
+		return slots, loaded, false
+	}
+	buf := g.newCBuf(33 * len(fresh))
+	out := g.newCBuf(4 * len(fresh))
+	defer func() { buf.free(); out.free() }()
+	for k, p := range fresh {
+		copy(buf.b[33*k:], p[:])
+	}
+	got := (*[maxBatchBytes / 4]uint32)(out.p)[:len(fresh):len(fresh)]
+	if nl > 0 {
+		atomic.AddUint64(&g.cnt.keyLoads, 1)
+		if C.gv_keys_load(g.ctx, C.size_t(nl), (*C.uint8_t)(buf.p), (*C.uint32_t)(out.p)) != 0 {
+			undo()
+			return slots, loaded, false
+		}
+	}
+	if len(victims) > 0 {
+		copy(got[nl:], victims)
+		if g.KeysReplace(got[nl:], buf.b[33*nl:]) != nil {
+			// no slot named in a failed replacement is trusted: start the arena over
+			atomic.AddUint64(&g.cnt.keyResets, 1)
+			C.gv_keys_reset(g.ctx)
+			g.slots = map[secp256k1.PubKeySecp256k1]uint32{}
+			g.clock.reset()
+			g.slotGen = uint64(C.gv_keys_generation(g.ctx))
+			for i := range loaded {
+				loaded[i] = false
+			}
+			return slots, loaded, false
+		}
+		atomic.AddUint64(&g.cnt.keyReplaced, uint64(len(victims)))
+	}
+	for k, p := range fresh {
+		if k >= nl { // erase the victim's key, set the fresh key
+			delete(g.slots, g.clock.keys[got[k]])
+		}
+		g.slots[p] = got[k]
+		g.clock.hold(got[k], p)
+	}
+	for i, p := range pubs {
+		slots[i], loaded[i] = g.slots[p], true
+	}
+	return slots, loaded, true
+}
+
+// KeysReplace rebuilds loaded arena slots in place (gv_keys_replace): slot
+// slots[i] then holds the key pub33[33*i:], as if it had been loaded there.
+// The arena's count, generation and layout do not move, so the caller keeps
+// its own key -> slot map right.  Slots must be loaded and distinct.
+func (g *GPU) KeysReplace(slots []uint32, pub33 []byte) error {
+	if len(pub33) != 33*len(slots) {
+		return fmt.Errorf("gpuverify: KeysReplace: %d slots for %d key bytes", len(slots), len(pub33))
+	}
+	if len(slots) == 0 {
+		return nil
+	}
+	sb := g.newCBuf(4 * len(slots))
+	pb := g.newCBuf(len(pub33))
+	defer func() { sb.free(); pb.free() }()
+	copy((*[maxBatchBytes / 4]uint32)(sb.p)[:len(slots):len(slots)], slots)
+	copy(pb.b, pub33)
+	if rc := C.gv_keys_replace(g.ctx, C.size_t(len(slots)), (*C.uint32_t)(sb.p), (*C.uint8_t)(pb.p)); rc != 0 {
+		return fmt.Errorf("gpuverify: gv_keys_replace: %d", int(rc))
+	}
+	return nil
+}
+
 // ResetKeys empties the key arena and the slot map together (a slot number
 // must never outlive the arena row it names).
 func (g *GPU) ResetKeys() {
@@ -743,6 +849,7 @@ func (g *GPU) ResetKeys() {
 	defer g.mu.Unlock()
 	C.gv_keys_reset(g.ctx)
 	g.slots = map[secp256k1.PubKeySecp256k1]uint32{}
+	g.clock.reset()
 	g.slotGen = uint64(C.gv_keys_generation(g.ctx))
 }
 

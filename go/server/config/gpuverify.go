@@ -36,6 +36,9 @@ type GPUVerifyConfig struct {
 	// KeyCap, EdKeyCap: arena sizes at which the arenas are reset.
 	KeyCap   int `mapstructure:"key-cap"`
 	EdKeyCap int `mapstructure:"ed-key-cap"`
+	// KeyResident: keep the secp256k1 arena at this many slots by replacing
+	// the least recently used keys (gv_keys_replace); 0 = off.
+	KeyResident int `mapstructure:"key-resident"`
 	// KeysWideQW: window widths of the key arena's wide tables (gv_set_option
 	// keys_wide_qw): 0 = 11-bit, then 9-bit when those no longer fit; 11 or 9
 	// = that width only.
@@ -58,7 +61,7 @@ type GPUVerifyConfig struct {
 func DefaultGPUVerifyConfig() GPUVerifyConfig {
 	return GPUVerifyConfig{
 		Enable: false, Devices: "", MaxBatch: 1 << 20, CPUBelow: 4, Keyed: true, KeyLoadMin: 4096,
-		KeyCap: 1 << 22, EdKeyCap: 1 << 16, KeysWideQW: 0, CacheEntries: 1 << 20, CheckTxWindowTxs: 64,
+		KeyCap: 1 << 22, EdKeyCap: 1 << 16, KeyResident: 0, KeysWideQW: 0, CacheEntries: 1 << 20, CheckTxWindowTxs: 64,
 		CheckTxWindow: 200 * time.Microsecond, PreVerifyBlocks: true,
 	}
 }
@@ -89,6 +92,8 @@ func (c GPUVerifyConfig) Validate() error {
 		return fmt.Errorf("gpu-verify.max-batch must be >= 256, got %d", c.MaxBatch)
 	case c.CPUBelow < 0, c.KeyLoadMin < 1, c.KeyCap < 1, c.EdKeyCap < 1, c.CacheEntries < 0:
 		return fmt.Errorf("gpu-verify: negative or zero size in %+v", c)
+	case c.KeyResident < 0 || c.KeyResident > c.KeyCap:
+		return fmt.Errorf("gpu-verify.key-resident must be 0 (off) or at most key-cap, got %d", c.KeyResident)
 	case c.KeysWideQW != 0 && c.KeysWideQW != 9 && c.KeysWideQW != 11:
 		return fmt.Errorf("gpu-verify.keys-wide-qw must be 0, 9 or 11, got %d", c.KeysWideQW)
 	case c.CheckTxWindowTxs < 1 || c.CheckTxWindow < 0:
@@ -122,6 +127,11 @@ keyed = {{ .GPUVerify.Keyed }}
 key-load-min = {{ .GPUVerify.KeyLoadMin }}
 key-cap = {{ .GPUVerify.KeyCap }}
 ed-key-cap = {{ .GPUVerify.EdKeyCap }}
+
+# Keep the account-key arena at this many keys, replacing the least recently
+# used ones (0 = off: the arena grows to key-cap and is reset there).  65536
+# keeps the fastest wide-table layout whatever the number of accounts seen.
+key-resident = {{ .GPUVerify.KeyResident }}
 
 # Window width of the key arena's wide tables: 0 = 11-bit tables (768 / 384 KiB
 # per key), then 9-bit ones (240 / 128 KiB) when those no longer fit; 11 or 9 =

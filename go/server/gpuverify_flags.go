@@ -23,6 +23,7 @@ const (
 	FlagGPUVerifyCPUBelow = "gpu-verify.cpu-below"
 	FlagGPUVerifyKeyed    = "gpu-verify.keyed"
 	FlagGPUVerifyWindow   = "gpu-verify.checktx-window"
+	FlagGPUVerifyResident = "gpu-verify.key-resident"
 )
 
 // AddGPUVerifyFlags registers the flags that override app.toml.
@@ -34,8 +35,9 @@ func AddGPUVerifyFlags(cmd *cobra.Command) {
 	cmd.Flags().Int(FlagGPUVerifyCPUBelow, d.CPUBelow, "Signature batches below this size verify on the CPU")
 	cmd.Flags().Bool(FlagGPUVerifyKeyed, d.Keyed, "Keep account keys parsed in GPU memory")
 	cmd.Flags().Duration(FlagGPUVerifyWindow, d.CheckTxWindow, "Concurrent CheckTx accumulation window")
+	cmd.Flags().Int(FlagGPUVerifyResident, d.KeyResident, "Keep the account-key arena at this many keys (0 = off)")
 	for _, f := range []string{FlagGPUVerify, FlagGPUVerifyDevices, FlagGPUVerifyMaxBatch, FlagGPUVerifyCPUBelow,
-		FlagGPUVerifyKeyed, FlagGPUVerifyWindow} {
+		FlagGPUVerifyKeyed, FlagGPUVerifyWindow, FlagGPUVerifyResident} {
 		_ = viper.BindPFlag(f, cmd.Flags().Lookup(f))
 	}
 }
@@ -63,7 +65,7 @@ func NewGPUVerifier(cfg config.GPUVerifyConfig, logger log.Logger) (gv.Verifier,
 		logger.Error("gpu-verify: max-batch not applied", "err", err)
 	}
 	g.CPUBelow, g.Keyed, g.KeyLoadMin = cfg.CPUBelow, cfg.Keyed, cfg.KeyLoadMin
-	g.KeyCap, g.EdKeyCap = cfg.KeyCap, cfg.EdKeyCap
+	g.KeyCap, g.EdKeyCap, g.KeyResident = cfg.KeyCap, cfg.EdKeyCap, cfg.KeyResident
 	if err := g.SetOption("keys_wide_qw", int64(cfg.KeysWideQW)); err != nil {
 		logger.Error("gpu-verify: keys-wide-qw not applied", "err", err)
 	} else {

@@ -119,11 +119,31 @@ int gv_dev_stream_destroy(gv_ctx* ctx, int dev_slot, void* stream);
  * per key: 1M accounts = 34 GB of the 288 GB); slot_out[i] receives key i's
  * slot.
  * A key that ParsePubKey rejects gets a slot too, and every verify against it
- * is false.  Slots are assigned in load order and stay valid until
- * gv_keys_reset.  Loading must not race keyed verifies of the same context. */
+ * is false.  Slots are assigned in load order and name their key until
+ * gv_keys_reset, or until gv_keys_replace puts another key into them.
+ * Loading must not race keyed verifies of the same context. */
 int gv_keys_load(gv_ctx* ctx, size_t n, const uint8_t* pub33, uint32_t* slot_out);
 int gv_keys_reset(gv_ctx* ctx);
 size_t gv_keys_count(const gv_ctx* ctx);
+/* Replacement: after GV_OK slot slots[i] behaves in every respect -- every
+ * keyed entry point on every schedule, the gv_submit_*_keyed lanes,
+ * gv_keys_point -- as if pub33 + 33*i had been loaded into it (a key
+ * ParsePubKey rejects gives a false slot; a key equal to one resident in
+ * another slot is fine, the two slots are independent).  Every table set the
+ * slot already has is rebuilt on every device of the context: the k4 tables,
+ * the k6 tables, the wide tables in the arena's current layout.  Nothing is
+ * allocated, grown or moved: gv_keys_count, gv_keys_generation and the
+ * arena's layout ("kw_arena_qw" / "kw_arena_ng") do not change, so a caller
+ * that replaces a slot keeps its own pubkey -> slot map right (drop the old
+ * key's entry; the generation does not tell).  Like gv_keys_load it waits
+ * for every submitted batch first: a batch submitted before the call runs
+ * against the old keys.
+ * GV_EINVAL, and nothing changed, when a slot is >= gv_keys_count() or
+ * appears twice (ctx, slots or pub33 NULL with n > 0 too); n == 0 is GV_OK.
+ * On GV_EHIP no slot named in the call is trusted: the caller must
+ * gv_keys_reset.  Option "keys_replaced" (read-only) counts the slots
+ * replaced since gv_open. */
+int gv_keys_replace(gv_ctx* ctx, size_t n, const uint32_t* slots, const uint8_t* pub33);
 /* Number of gv_keys_reset calls on ctx so far: a caller that keeps a
  * pubkey -> slot map drops it when the generation moved (slots of an older
  * generation may name other keys). */
@@ -142,7 +162,10 @@ uint64_t gv_keys_generation(const gv_ctx* ctx);
  *                     resident, else pub33 (loading per
  *                     CheckTx window cost 35.8k -> 5.1k tx/s);
  *   GV_KEY_CAP        arena size at which the caller resets the arena
- *                     (5.4 KB of HBM per key). */
+ *                     (5.4 KB of HBM per key), unless it keeps the arena
+ *                     at a resident size below this by replacing slots
+ *                     (gv_keys_replace; gvh_set_key_resident, the shim's
+ *                     KeyResident). */
 #define GV_CPU_CROSSOVER 4
 #define GV_KEY_LOAD_MIN 4096
 #define GV_KEY_CAP (1u << 22)
@@ -376,7 +399,8 @@ int gv_set_option(gv_ctx* ctx, const char* key, long long val);
  * was built with (11 / 9; "kwn_qw" 0: one width only), and "kw_arena_qw" /
  * "kw_arena_ng", the window width and the group count of the first device's
  * wide arena as the last gv_keys_load left it (both 0: no slot has wide
- * tables).  GV_EINVAL for any other key.  Instrumentation (bench route
+ * tables), and "keys_replaced", the slots gv_keys_replace has rewritten
+ * since gv_open.  GV_EINVAL for any other key.  Instrumentation (bench route
  * attribution). */
 int gv_get_option(gv_ctx* ctx, const char* key, long long* val);
 

@@ -1,0 +1,222 @@
+// evict_harness.cpp -- the host mirror's clock eviction (gvh_set_key_resident)
+// under ASan + UBSan or TSan (tests/test_key_evict_host.py), over the CPU fake
+// with gv_keys_replace (evict_fake.cpp).  host/gvhost.cpp is compiled into
+// this file so that the checks below can read the app's key-slot bookkeeping.
+// Reads the fixture format of tests/sanitize/harness.cpp: accounts, blocks
+// (signers rotating over more accounts than the resident size), CheckTx txs
+// per thread.
+//   1. gvh_deliver_blocks over all blocks at once (block b+1's batch on the
+//      helper thread under block b's DeliverTx pool) while 8 threads call
+//      gvh_checktx for accounts of their own, resident = R;
+//   2. the blocks one gvh_deliver_blocks call each, resident = R, with the
+//      bookkeeping checked after every block: every slot's stored key is the
+//      key the app's reverse array names, the map sends that key to that slot,
+//      the map holds nothing else, and the arena never passes R slots
+//      (GVH_EVICT_AUDIT: verify_secp aborts if a slot named by the batch in
+//      hand is among the victims);
+//   3. the same with resident = 0, and gvh_ante tx by tx.
+// All codes and final accounts must agree.  Prints {"blocks": [...],
+// "check": [...], "replaced": n, "resets": n, "count": n} and exits 0, or
+// exits 1 with the first difference.
+#define GVH_EVICT_AUDIT 1
+#include "../../cosmos-sdk-rootchain_amd/host/gvhost.cpp"
+
+#include <stdio.h>
+
+extern "C" gv_ctx* gvfake_open(void);
+extern "C" void gvfake_close(gv_ctx*);
+extern "C" int gvfake_key(gv_ctx*, uint32_t slot, uint8_t out33[33]);
+
+struct FixtureReader {
+  std::vector<uint8_t> b;
+  size_t o = 0;
+  uint32_t u32() { uint32_t v; memcpy(&v, &b.at(o), 4); o += 4; return v; }
+  uint64_t u64() { uint64_t v; memcpy(&v, &b.at(o), 8); o += 8; return v; }
+  std::vector<uint8_t> bytes() {
+    const uint32_t n = u32();
+    std::vector<uint8_t> v(b.begin() + o, b.begin() + o + n);
+    o += n;
+    return v;
+  }
+};
+
+struct FixAcc { uint8_t addr[20]; uint64_t number, seq; std::vector<uint8_t> pub; };
+
+static std::string chain;
+static int64_t height;
+static std::vector<FixAcc> accs;
+
+static gvh_app* fresh(gv_ctx* ctx, size_t resident) {
+  gvh_app* app = gvh_app_new(ctx);
+  gvh_set_context(app, chain.c_str(), height, 0, 0);
+  gvh_set_threads(app, 8);
+  gvh_set_keyed(app, 1, 64);
+  gvh_set_key_resident(app, resident);
+  for (const FixAcc& a : accs)
+    gvh_set_account(app, a.addr, a.number, a.seq, a.pub.empty() ? nullptr : a.pub.data(), a.pub.size());
+  return app;
+}
+
+static std::vector<std::vector<uint8_t>> state(gvh_app* app) {
+  std::vector<std::vector<uint8_t>> out;
+  for (const FixAcc& a : accs) {
+    uint64_t num = 0, seq = 0;
+    size_t pl = 0;
+    std::vector<uint8_t> pub(512);
+    gvh_get_account(app, a.addr, &num, &seq, pub.data(), &pl);
+    pub.resize(pl);
+    pub.insert(pub.end(), (uint8_t*)&num, (uint8_t*)&num + 8);
+    pub.insert(pub.end(), (uint8_t*)&seq, (uint8_t*)&seq + 8);
+    out.push_back(pub);
+  }
+  return out;
+}
+
+static int fail(const char* what) {
+  fprintf(stderr, "evict_harness: %s\n", what);
+  return 1;
+}
+
+// The bookkeeping of app against the fake's key store; nullptr when consistent.
+static const char* audit(gvh_app* app, gv_ctx* ctx, size_t resident) {
+  std::lock_guard<std::mutex> g(app->gpu_mu);
+  std::unique_lock<std::shared_mutex> wk(app->key_mu);
+  const size_t count = gv_keys_count(ctx);
+  if (count > resident) return "arena past the resident size";
+  if (app->slot_key.size() != count) return "reverse array and arena differ in size";
+  if (app->slot_ref.size() != count || app->slot_stamp.size() != count) return "clock arrays differ in size";
+  if (app->key_slots.size() != count) return "map holds a key no slot holds";
+  for (size_t s = 0; s < count; ++s) {
+    uint8_t k[33];
+    if (!gvfake_key(ctx, (uint32_t)s, k)) return "slot not in the store";
+    if (memcmp(k, app->slot_key[s].data(), 33)) return "reverse array names another key than the store holds";
+    const uint32_t* v = app->key_slots.find(k);
+    if (!v || *v != s) return "map does not send a slot's key to that slot";
+  }
+  return nullptr;
+}
+
+int main(int argc, char** argv) {
+  if (argc != 3) return fail("usage: evict_harness fixture.bin resident");
+  const size_t resident = (size_t)atol(argv[2]);
+  FixtureReader r;
+  {
+    FILE* f = fopen(argv[1], "rb");
+    if (!f) return fail("cannot open fixture");
+    uint8_t buf[1 << 16];
+    size_t k;
+    while ((k = fread(buf, 1, sizeof buf, f)) > 0) r.b.insert(r.b.end(), buf, buf + k);
+    fclose(f);
+  }
+  if (r.b.size() < 6 || memcmp(r.b.data(), "GVSAN1", 6)) return fail("bad magic");
+  r.o = 6;
+  {
+    auto c = r.bytes();
+    chain.assign(c.begin(), c.end());
+  }
+  height = (int64_t)r.u64();
+  for (uint32_t n = r.u32(); n; --n) {
+    FixAcc a;
+    memcpy(a.addr, &r.b.at(r.o), 20);
+    r.o += 20;
+    a.number = r.u64();
+    a.seq = r.u64();
+    a.pub = r.bytes();
+    accs.push_back(a);
+  }
+  std::vector<std::vector<std::vector<uint8_t>>> blocks(r.u32());
+  for (auto& bl : blocks)
+    for (uint32_t n = r.u32(); n; --n) bl.push_back(r.bytes());
+  std::vector<std::vector<std::vector<uint8_t>>> check(r.u32());   // per thread
+  for (auto& th : check)
+    for (uint32_t n = r.u32(); n; --n) th.push_back(r.bytes());
+
+  std::vector<const uint8_t*> ptr;
+  std::vector<size_t> len, ntx;
+  for (auto& bl : blocks) {
+    ntx.push_back(bl.size());
+    for (auto& t : bl) { ptr.push_back(t.data()); len.push_back(t.size()); }
+  }
+
+  // 1. pipelined replay with concurrent CheckTx, eviction on
+  gv_ctx* c1 = gvfake_open();
+  gvh_app* a1 = fresh(c1, resident);
+  {
+    size_t got = 0;
+    gvh_get_key_stats(a1, &got, nullptr, nullptr);
+    if (got != resident) return fail("gvh_set_key_resident did not take (gv_keys_replace not linked?)");
+  }
+  gvh_set_window(a1, 64, 200);
+  std::vector<std::vector<uint32_t>> cgot(check.size());
+  std::vector<int> rcs(check.size(), GVH_OK);
+  std::vector<std::thread> th;
+  for (size_t t = 0; t < check.size(); ++t)
+    th.emplace_back([&, t]() {
+      for (auto& tx : check[t]) {
+        gvh_result res;
+        const int rc = gvh_checktx(a1, tx.data(), tx.size(), &res);
+        if (rc != GVH_OK) rcs[t] = rc;
+        cgot[t].push_back(res.code);
+      }
+    });
+  std::vector<uint32_t> piped(ptr.size());
+  const int drc = gvh_deliver_blocks(a1, blocks.size(), ntx.data(), ptr.data(), len.data(), piped.data());
+  for (auto& x : th) x.join();
+  if (drc != GVH_OK) return fail("gvh_deliver_blocks");
+  for (int rc : rcs)
+    if (rc != GVH_OK) return fail("gvh_checktx");
+  if (const char* e = audit(a1, c1, resident)) return fail(e);
+
+  // 2. block by block with the bookkeeping checked after every block
+  gv_ctx* c2 = gvfake_open();
+  gvh_app* a2 = fresh(c2, resident);
+  std::vector<uint32_t> one(ptr.size());
+  size_t o = 0;
+  for (size_t b = 0; b < blocks.size(); ++b) {
+    if (gvh_deliver_blocks(a2, 1, &ntx[b], ptr.data() + o, len.data() + o, one.data() + o) != GVH_OK)
+      return fail("gvh_deliver_blocks (one block)");
+    o += ntx[b];
+    if (const char* e = audit(a2, c2, resident)) return fail(e);
+  }
+  uint64_t replaced = 0, resets = 0;
+  gvh_get_key_stats(a2, nullptr, &replaced, &resets);
+
+  // 3. eviction off, and tx by tx
+  gv_ctx* c3 = gvfake_open();
+  gvh_app* a3 = fresh(c3, 0);
+  std::vector<uint32_t> off(ptr.size());
+  if (gvh_deliver_blocks(a3, blocks.size(), ntx.data(), ptr.data(), len.data(), off.data()) != GVH_OK)
+    return fail("gvh_deliver_blocks (resident 0)");
+  if (gv_keys_count(c3) <= resident) return fail("the workload does not pass the resident size");
+  gvh_app* a4 = fresh(c3, 0);
+  std::vector<uint32_t> serial, cflat, sflat;
+  for (size_t i = 0; i < ptr.size(); ++i) {
+    gvh_result res;
+    if (gvh_ante(a4, ptr[i], len[i], 0, &res) != GVH_OK) return fail("gvh_ante");
+    serial.push_back(res.code);
+  }
+  for (size_t t = 0; t < check.size(); ++t)
+    for (size_t i = 0; i < check[t].size(); ++i) {
+      gvh_result res;
+      if (gvh_ante(a4, check[t][i].data(), check[t][i].size(), 0, &res) != GVH_OK) return fail("gvh_ante (check)");
+      sflat.push_back(res.code);
+      cflat.push_back(cgot[t][i]);
+    }
+  if (piped != off) return fail("pipelined codes with eviction != resident 0");
+  if (one != off) return fail("block-by-block codes with eviction != resident 0");
+  if (off != serial) return fail("resident 0 codes != serial ante");
+  if (cflat != sflat) return fail("concurrent CheckTx codes != serial ante");
+  if (state(a2) != state(a3)) return fail("final accounts differ (eviction on / off)");
+  if (state(a1) != state(a4)) return fail("final accounts differ (pipelined + CheckTx / serial)");
+  const size_t count = gv_keys_count(c2);
+  // freed together at the end (tests/sanitize/harness.cpp: TSan and reused mutex words)
+  for (gvh_app* a : {a1, a2, a3, a4}) gvh_app_free(a);
+  printf("{\"blocks\": [");
+  for (size_t i = 0; i < serial.size(); ++i) printf("%s%u", i ? ", " : "", serial[i]);
+  printf("], \"check\": [");
+  for (size_t i = 0; i < cflat.size(); ++i) printf("%s%u", i ? ", " : "", cflat[i]);
+  printf("], \"replaced\": %llu, \"resets\": %llu, \"count\": %zu}\n", (unsigned long long)replaced,
+         (unsigned long long)resets, count);
+  for (gv_ctx* c : {c1, c2, c3}) gvfake_close(c);
+  return 0;
+}
