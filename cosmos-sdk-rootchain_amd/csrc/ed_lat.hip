@@ -40,22 +40,23 @@ namespace ed {
 
 static_assert(GV_EDK_WORDS == 64 * 8 * ED_CACHED_WORDS, "key table size");
 
-__global__ __launch_bounds__(64) void k_ed_keys(const uint8_t* pub32, uint32_t n, uint32_t base, uint32_t* ktab,
-                                                uint32_t* kpub, uint32_t* kok) {
+__global__ __launch_bounds__(64) void k_ed_keys(const uint8_t* pub32, uint32_t n, uint32_t base, const uint32_t* slots,
+                                                uint32_t* ktab, uint32_t* kpub, uint32_t* kok) {
   const uint32_t g = blockIdx.x * 64 + threadIdx.x;
   if (g >= n) return;
+  const uint32_t row = slots ? slots[g] : base + g;   // gv_ed_keys_replace: a loaded slot, bounded and distinct
   u32 pw[8];
 #pragma unroll
   for (int i = 0; i < 8; ++i) {
     const uint8_t* p = pub32 + (size_t)g * 32 + 4 * i;
     pw[i] = (u32)p[0] | ((u32)p[1] << 8) | ((u32)p[2] << 16) | ((u32)p[3] << 24);
-    kpub[(size_t)(base + g) * 8 + i] = pw[i];
+    kpub[(size_t)row * 8 + i] = pw[i];
   }
   ge_ext a, P;
   const bool ok = ge_frombytes(a, pw);
-  kok[base + g] = ok ? 1u : 0u;
+  kok[row] = ok ? 1u : 0u;
   ge_neg(P, a);
-  u32* tab = ktab + (size_t)(base + g) * GV_EDK_WORDS;
+  u32* tab = ktab + (size_t)row * GV_EDK_WORDS;
 #pragma unroll 1
   for (int w = 0; w < 64; ++w) {
     if (w) {
@@ -82,7 +83,9 @@ __global__ __launch_bounds__(64) void k_ed_keys(const uint8_t* pub32, uint32_t n
 // doublings and parks the 64 window bases 16^w (-A) (extended coordinates,
 // 36 words each, in scratch); k_ed_keys_tab (lane = key x window) adds each
 // base to itself seven times into the table -- the same operations on the
-// same values as k_ed_keys, so the same table words.
+// same values as k_ed_keys, so the same table words.  With a slot list
+// (device memory, n words; gv_ed_keys_replace) key g goes to row slots[g] of
+// ktab / kpub / kok instead of base + g; the scratch rows stay indexed by g.
 GV_DEV void ext_store(u32* p, const ge_ext& a) {
 #pragma unroll
   for (int i = 0; i < 9; ++i) { p[i] = a.X.n[i]; p[9 + i] = a.Y.n[i]; p[18 + i] = a.Z.n[i]; p[27 + i] = a.T.n[i]; }
@@ -103,20 +106,21 @@ struct EdComb {
 static_assert(EdComb<4>::WORDS == GV_EDK_WORDS && EdComb<6>::WORDS == GV_EDK64_WORDS, "comb table sizes");
 
 template <int RB>
-__global__ __launch_bounds__(64) void k_ed_keys_chain(const uint8_t* pub32, uint32_t n, uint32_t base, uint32_t* kpub,
-                                                      uint32_t* kok, uint32_t* wbase) {
+__global__ __launch_bounds__(64) void k_ed_keys_chain(const uint8_t* pub32, uint32_t n, uint32_t base, const uint32_t* slots,
+                                                      uint32_t* kpub, uint32_t* kok, uint32_t* wbase) {
   const uint32_t g = blockIdx.x * 64 + threadIdx.x;
   if (g >= n) return;
+  const uint32_t row = slots ? slots[g] : base + g;
   u32 pw[8];
 #pragma unroll
   for (int i = 0; i < 8; ++i) {
     const uint8_t* p = pub32 + (size_t)g * 32 + 4 * i;
     pw[i] = (u32)p[0] | ((u32)p[1] << 8) | ((u32)p[2] << 16) | ((u32)p[3] << 24);
-    kpub[(size_t)(base + g) * 8 + i] = pw[i];
+    kpub[(size_t)row * 8 + i] = pw[i];
   }
   ge_ext a, P;
   const bool ok = ge_frombytes(a, pw);
-  kok[base + g] = ok ? 1u : 0u;
+  kok[row] = ok ? 1u : 0u;
   ge_neg(P, a);
   using L = EdComb<RB>;
   u32* wb = wbase + (size_t)g * L::NW * ED_CACHED_WORDS;
@@ -131,14 +135,15 @@ __global__ __launch_bounds__(64) void k_ed_keys_chain(const uint8_t* pub32, uint
   }
 }
 template <int RB>
-__global__ __launch_bounds__(256) void k_ed_keys_tab(uint32_t n, uint32_t base, uint32_t* ktab, const uint32_t* wbase) {
+__global__ __launch_bounds__(256) void k_ed_keys_tab(uint32_t n, uint32_t base, const uint32_t* slots, uint32_t* ktab,
+                                                     const uint32_t* wbase) {
   using L = EdComb<RB>;
   const uint32_t t = blockIdx.x * 256 + threadIdx.x;
   if (t >= n * (uint32_t)L::NW) return;
   const uint32_t g = t / (uint32_t)L::NW, w = t % (uint32_t)L::NW;
   ge_ext P;
   ext_load(P, wbase + (size_t)t * ED_CACHED_WORDS);
-  u32* tab = ktab + (size_t)(base + g) * L::WORDS;
+  u32* tab = ktab + (size_t)(slots ? slots[g] : base + g) * L::WORDS;
   ge_cached c1, c;
   ge_to_cached(c1, P);
   atab_store(tab + (size_t)(w * L::NE) * ED_CACHED_WORDS, 1, 0, c1);
@@ -827,8 +832,53 @@ __global__ __launch_bounds__(256) void k_ed_pack_bits(u32 n, const uint8_t* out8
   if ((threadIdx.x & 63u) == 0 && g < n) bits[g >> 6] = m;
 }
 
+// Read arena slots back (gv_ed_keys_point), one lane per item: entry (w, j)
+// of the slot's table, j * 16^w * (-A) in cached form, rebuilt as the
+// projective point (Y+X) - (Y-X) : (Y+X) + (Y-X) : 2Z = (2X : 2Y : 2Z) and
+// encoded canonically; the raw key bytes and the decode verdict beside it.
+// Slots at or past kcount give zeros and 0, a rejected key a zero encoding.
+__global__ __launch_bounds__(256) void k_ed_keys_point(u32 n, const u32* slots, u32 w, u32 j, const u32* ktab,
+                                                       const u32* kpub, const u32* kok, u32 kcount, u32* out_enc,
+                                                       u32* out_pub, uint8_t* out_ok) {
+  const u32 g = blockIdx.x * 256 + threadIdx.x;
+  if (g >= n) return;
+  const u32 sl = slots[g];
+  const bool in = sl < kcount;
+  const bool ok = in && kok[sl] != 0u;
+  u32 ew[8];
+#pragma unroll
+  for (int i = 0; i < 8; ++i) ew[i] = 0;
+  if (ok) {
+    ge_cached c;
+    atab_load(c, ktab + (size_t)sl * GV_EDK_WORDS + (size_t)(w * 8 + j - 1) * ED_CACHED_WORDS, 1, 0);
+    ge_ext p;
+    e29_sub_norm<1>(p.X, c.ypx, c.ymx);
+    e29_add_norm(p.Y, c.ypx, c.ymx);
+    p.Z = c.z2;
+    f29_set_zero(p.T);                      // ToBytes reads X, Y, Z
+    ge_tobytes(ew, p);
+  }
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    out_enc[(size_t)g * 8 + i] = ew[i];
+    out_pub[(size_t)g * 8 + i] = in ? kpub[(size_t)sl * 8 + i] : 0u;
+  }
+  out_ok[g] = ok ? 1u : 0u;
+}
+
 }  // namespace ed
 }  // namespace gv
+
+extern "C" hipError_t gvk_ed_keys_point(uint32_t n, const uint32_t* slots, uint32_t w, uint32_t j,
+                                        const uint32_t* ktab, const uint32_t* kpub, const uint32_t* kok,
+                                        uint32_t kcount, uint8_t* out_enc32, uint8_t* out_pub32, uint8_t* out_ok,
+                                        hipStream_t st) {
+  if (n == 0) return hipSuccess;
+  if (w >= 64 || j < 1 || j > 8) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(gv::ed::k_ed_keys_point, dim3((n + 255) / 256), dim3(256), 0, st, n, slots, w, j, ktab, kpub, kok,
+                     kcount, (uint32_t*)out_enc32, (uint32_t*)out_pub32, out_ok);
+  return hipGetLastError();
+}
 
 extern "C" hipError_t gvk_ed_group(uint32_t n, const uint8_t* pub32, uint32_t* table, uint32_t tslots, uint32_t* rep,
                                    uint32_t* uid, uint32_t* count, uint32_t capU, uint8_t* kpub32, uint32_t* slot,
@@ -855,22 +905,24 @@ extern "C" hipError_t gvk_ed_keyed(const gvk_edk* b, hipStream_t st) {
   return hipGetLastError();
 }
 
-extern "C" hipError_t gvk_ed_keys(const uint8_t* pub32, uint32_t n, uint32_t base, uint32_t* ktab, uint32_t* kpub,
-                                  uint32_t* kok, uint32_t* wbase, int rb, hipStream_t st) {
+extern "C" hipError_t gvk_ed_keys(const uint8_t* pub32, uint32_t n, uint32_t base, const uint32_t* slots,
+                                  uint32_t* ktab, uint32_t* kpub, uint32_t* kok, uint32_t* wbase, int rb,
+                                  hipStream_t st) {
   if (n == 0) return hipSuccess;
   if (rb == 6 && !wbase) return hipErrorInvalidValue;     // the radix-64 tables: the split build only
   if (wbase && rb == 6) {                   // chain + table launches (scratch: n * 64 * 36 words)
-    hipLaunchKernelGGL(gv::ed::k_ed_keys_chain<6>, dim3((n + 63) / 64), dim3(64), 0, st, pub32, n, base, kpub, kok,
-                       wbase);
+    hipLaunchKernelGGL(gv::ed::k_ed_keys_chain<6>, dim3((n + 63) / 64), dim3(64), 0, st, pub32, n, base, slots, kpub,
+                       kok, wbase);
     hipLaunchKernelGGL(gv::ed::k_ed_keys_tab<6>, dim3((n * gv::ed::EdComb<6>::NW + 255) / 256), dim3(256), 0, st, n,
-                       base, ktab, (const uint32_t*)wbase);
+                       base, slots, ktab, (const uint32_t*)wbase);
   } else if (wbase) {
-    hipLaunchKernelGGL(gv::ed::k_ed_keys_chain<4>, dim3((n + 63) / 64), dim3(64), 0, st, pub32, n, base, kpub, kok,
-                       wbase);
-    hipLaunchKernelGGL(gv::ed::k_ed_keys_tab<4>, dim3((n * 64 + 255) / 256), dim3(256), 0, st, n, base, ktab,
+    hipLaunchKernelGGL(gv::ed::k_ed_keys_chain<4>, dim3((n + 63) / 64), dim3(64), 0, st, pub32, n, base, slots, kpub,
+                       kok, wbase);
+    hipLaunchKernelGGL(gv::ed::k_ed_keys_tab<4>, dim3((n * 64 + 255) / 256), dim3(256), 0, st, n, base, slots, ktab,
                        (const uint32_t*)wbase);
   } else {
-    hipLaunchKernelGGL(gv::ed::k_ed_keys, dim3((n + 63) / 64), dim3(64), 0, st, pub32, n, base, ktab, kpub, kok);
+    hipLaunchKernelGGL(gv::ed::k_ed_keys, dim3((n + 63) / 64), dim3(64), 0, st, pub32, n, base, slots, ktab, kpub,
+                       kok);
   }
   return hipGetLastError();
 }

@@ -335,8 +335,19 @@ typedef struct gvk_edl {
 // scratch for the window bases -- the chain and the table adds then run as
 // two launches (k_ed_keys_chain, k_ed_keys_tab), same table words.  rb: the
 // comb radix bits, 4 (GV_EDK_WORDS per key) or 6 (GV_EDK64_WORDS; needs wbase).
-hipError_t gvk_ed_keys(const uint8_t* pub32, uint32_t n, uint32_t base, uint32_t* ktab, uint32_t* kpub, uint32_t* kok,
-                       uint32_t* wbase, int rb, hipStream_t st);
+// slots (device memory, n words, or null): key g goes to row slots[g] of
+// ktab / kpub / kok instead of base + g (gv_ed_keys_replace; the caller has
+// bounded every entry and made them distinct).  The scratch stays per g.
+hipError_t gvk_ed_keys(const uint8_t* pub32, uint32_t n, uint32_t base, const uint32_t* slots, uint32_t* ktab,
+                       uint32_t* kpub, uint32_t* kok, uint32_t* wbase, int rb, hipStream_t st);
+// Read arena slots back (k_ed_keys_point, one lane per item): the canonical
+// encoding of table entry (w, j) = j * 16^w * (-A) (w < 64, 1 <= j <= 8), the
+// raw key bytes and the decode verdict.  A slot at or past kcount: zeros, 0.
+// A rejected key: its bytes, 0 and a zero encoding.  The outputs are device
+// memory, out_enc32 and out_pub32 4-byte aligned.
+hipError_t gvk_ed_keys_point(uint32_t n, const uint32_t* slots, uint32_t w, uint32_t j, const uint32_t* ktab,
+                             const uint32_t* kpub, const uint32_t* kok, uint32_t kcount, uint8_t* out_enc32,
+                             uint8_t* out_pub32, uint8_t* out_ok, hipStream_t st);
 hipError_t gvk_ed_lat(const gvk_edl* b, hipStream_t st);
 // Small ed25519 batches against uncached keys (k_ed_lat_unc): b->pub32 per item.
 hipError_t gvk_ed_lat_unc(const gvk_edl* b, hipStream_t st);

@@ -593,7 +593,7 @@ int ed_grouped(Dev* d, size_t n, const uint8_t* pub, const uint8_t* sig, const u
   const int rb = gc.r64 && wb ? 6 : 4;
   int rc = ensure_edg(d, U, rb == 6 ? (size_t)GV_EDK64_WORDS : (size_t)GV_EDK_WORDS);
   if (rc) return rc == GV_ENOMEM ? GV_OK : rc;
-  CK(gvk_ed_keys(kpub32, (uint32_t)U, 0u, d->edg_ktab, d->edg_kpub, d->edg_kok, wb, rb, st));
+  CK(gvk_ed_keys(kpub32, (uint32_t)U, 0u, nullptr, d->edg_ktab, d->edg_kpub, d->edg_kok, wb, rb, st));
   if (gc.sorted) CK(gvk_sort_slots(&so, (uint32_t)n, slot, (uint32_t)U, st));
   gvk_edk b;
   memset(&b, 0, sizeof b);
@@ -761,6 +761,7 @@ struct gv_ctx {
   // ed25519 key arena (gv_ed_keys_load), same on every device
   size_t ed_keys = 0;
   std::atomic<uint64_t> ed_keys_gen{0};
+  std::atomic<uint64_t> ed_keys_replaced{0};   // slots gv_ed_keys_replace rewrote since gv_open ("ed_keys_replaced")
   std::mutex ed_keys_mu;
   std::vector<uint8_t> ed_kpub;  // the raw keys per slot (large keyed batches run the throughput kernels on them)
   bool ed_group = true;          // ed25519 throughput batches: in-batch key grouping + k_ed_keyed (GV_ED_GROUP=0: A/B)
@@ -2688,7 +2689,7 @@ int gv_ed_keys_load(gv_ctx* ctx, size_t n, const uint8_t* pub32, uint32_t* slot_
     const bool split = ctx->ed_keys_split && wb_bytes <= ((size_t)1 << 30);
     if (hipMalloc(&dp, o_wb + (split ? wb_bytes : 0)) != hipSuccess) return GV_ENOMEM;
     if (hipMemcpyAsync(dp, pub32, n * 32, hipMemcpyHostToDevice, st) != hipSuccess ||
-        gvk_ed_keys(dp, (uint32_t)n, (uint32_t)base, d->ektab, d->ekpub, d->ekok,
+        gvk_ed_keys(dp, (uint32_t)n, (uint32_t)base, nullptr, d->ektab, d->ekpub, d->ekok,
                     split ? (uint32_t*)(dp + o_wb) : nullptr, 4, st) != hipSuccess ||
         hipStreamSynchronize(st) != hipSuccess) {
       (void)hipFree(dp);
@@ -2700,6 +2701,79 @@ int gv_ed_keys_load(gv_ctx* ctx, size_t n, const uint8_t* pub32, uint32_t* slot_
   ctx->ed_keys = base + n;
   for (size_t i = 0; i < n; ++i) slot_out[i] = (uint32_t)(base + i);
   return GV_OK;
+}
+
+int gv_ed_keys_replace(gv_ctx* ctx, size_t n, const uint32_t* slots, const uint8_t* pub32) {
+  if (!ctx) return GV_EINVAL;
+  if (n == 0) return GV_OK;
+  if (!slots || !pub32) return GV_EINVAL;
+  // keyed verifies hold ed_keys_mu for the whole call: none runs under a replacement
+  std::lock_guard<std::mutex> kl(ctx->ed_keys_mu);
+  // every check before the first device write: each slot loaded, none twice
+  // (two lanes would write one row)
+  const size_t count = ctx->ed_keys;
+  if (n > count) return GV_EINVAL;
+  {
+    std::vector<uint64_t> seen((count + 63) / 64, 0);
+    for (size_t i = 0; i < n; ++i) {
+      const size_t sl = slots[i];
+      if (sl >= count || (seen[sl >> 6] >> (sl & 63) & 1)) return GV_EINVAL;
+      seen[sl >> 6] |= (uint64_t)1 << (sl & 63);
+    }
+  }
+  for (Dev* d : ctx->devs) {                    // every device holds every key
+    std::lock_guard<std::mutex> lk(d->mu);
+    CK(hipSetDevice(d->id));
+    hipStream_t st = d->set[0].st;
+    if (count > d->ekcap) return GV_EINVAL;     // (never: the arena holds its slots)
+    // the scratch of gv_ed_keys_load (keys, then the window bases) and the slot list; nothing in the arena moves
+    uint8_t* dp = nullptr;
+    const size_t o_sl = round_up(n * 32, 256), o_wb = o_sl + round_up(n * 4, 256), wb_bytes = n * 64 * 36 * 4;
+    const bool split = ctx->ed_keys_split && wb_bytes <= ((size_t)1 << 30);
+    if (hipMalloc(&dp, o_wb + (split ? wb_bytes : 0)) != hipSuccess) return GV_ENOMEM;
+    if (hipMemcpyAsync(dp, pub32, n * 32, hipMemcpyHostToDevice, st) != hipSuccess ||
+        hipMemcpyAsync(dp + o_sl, slots, n * 4, hipMemcpyHostToDevice, st) != hipSuccess ||
+        gvk_ed_keys(dp, (uint32_t)n, 0u, (const uint32_t*)(dp + o_sl), d->ektab, d->ekpub, d->ekok,
+                    split ? (uint32_t*)(dp + o_wb) : nullptr, 4, st) != hipSuccess ||
+        hipStreamSynchronize(st) != hipSuccess) {
+      (void)hipFree(dp);
+      return GV_EHIP;
+    }
+    (void)hipFree(dp);
+  }
+  // the host copy (large batches with ed_keyed 0 read it) only after every device has succeeded
+  for (size_t i = 0; i < n; ++i) memcpy(&ctx->ed_kpub[(size_t)slots[i] * 32], pub32 + i * 32, 32);
+  ctx->ed_keys_replaced.fetch_add(n);
+  return GV_OK;
+}
+
+int gv_ed_keys_point(gv_ctx* ctx, size_t n, const uint32_t* slots, uint32_t w, uint32_t j, uint8_t* out_enc32,
+                     uint8_t* out_pub32, uint8_t* out_ok) {
+  if (!ctx) return GV_EINVAL;
+  if (w >= 64 || j < 1 || j > 8) return GV_EINVAL;
+  if (n == 0) return GV_OK;
+  if (!slots || !out_enc32 || !out_pub32 || !out_ok || n > kMaxItems) return GV_EINVAL;
+  std::lock_guard<std::mutex> kl(ctx->ed_keys_mu);
+  Dev* d = ctx->devs[0];
+  std::lock_guard<std::mutex> lk(d->mu);
+  CK(hipSetDevice(d->id));
+  hipStream_t st = d->set[0].st;
+  // an arena never allocated (or smaller than the count: never) reads as empty
+  const size_t kcount = std::min(ctx->ed_keys, d->ekcap);
+  uint8_t* buf = nullptr;
+  const size_t sb = round_up(n * 4, 256), eb = round_up(n * 32, 256);
+  if (hipMalloc(&buf, sb + 2 * eb + n) != hipSuccess) return GV_ENOMEM;
+  int rc = GV_OK;
+  if (hipMemcpyAsync(buf, slots, n * 4, hipMemcpyHostToDevice, st) != hipSuccess ||
+      gvk_ed_keys_point((uint32_t)n, (const uint32_t*)buf, w, j, d->ektab, d->ekpub, d->ekok, (uint32_t)kcount,
+                        buf + sb, buf + sb + eb, buf + sb + 2 * eb, st) != hipSuccess ||
+      hipMemcpyAsync(out_enc32, buf + sb, n * 32, hipMemcpyDeviceToHost, st) != hipSuccess ||
+      hipMemcpyAsync(out_pub32, buf + sb + eb, n * 32, hipMemcpyDeviceToHost, st) != hipSuccess ||
+      hipMemcpyAsync(out_ok, buf + sb + 2 * eb, n, hipMemcpyDeviceToHost, st) != hipSuccess ||
+      hipStreamSynchronize(st) != hipSuccess)
+    rc = GV_EHIP;
+  (void)hipFree(buf);
+  return rc;
 }
 
 int gv_ed_keys_reset(gv_ctx* ctx) {
@@ -3021,6 +3095,7 @@ int gv_get_option(gv_ctx* ctx, const char* key, long long* val) {
               {"keys_wide_qw", ctx->keys_wide_qw},
               {"keys_wide_mb", (long long)(ctx->keys_wide_bytes >> 20)},
               {"keys_replaced", (long long)ctx->keys_replaced.load()},   // read-only: gv_keys_replace's slots so far
+              {"ed_keys_replaced", (long long)ctx->ed_keys_replaced.load()},   // the same for gv_ed_keys_replace
               {"kw_qw", GV_KW_QW},                   // read-only: the wide arena's window width (build)
               {"kwn_qw", GV_KWN ? GV_KWN_QW : 0}};   // read-only: its narrow width (build; 0: not compiled)
   // read-only: the first device's wide arena as gv_keys_load left it -- its

@@ -46,6 +46,7 @@ EXPORTED_SYMBOLS = (
     "gv_keys_point", "gv_keys_replace", "gv_dev_stream_create", "gv_dev_stream_sync", "gv_dev_stream_destroy",
     "gv_verify_ed25519_msgs", "gv_dev_verify_ed25519_msgs", "gv_last_slices", "gv_group_stats", "gv_route_stats", "gv_host_alloc", "gv_host_free",
     "gv_ed_keys_load", "gv_ed_keys_reset", "gv_ed_keys_count", "gv_ed_keys_generation", "gv_verify_ed25519_msgs_keyed",
+    "gv_ed_keys_replace", "gv_ed_keys_point",
     "gv_submit_digests", "gv_submit_digests_keyed", "gv_submit_msgs", "gv_submit_msgs_keyed", "gv_wait",
 )
 
@@ -104,6 +105,10 @@ def load(path: str = LIB_PATH):
     L.gv_ed_keys_count.restype = sz
     L.gv_ed_keys_generation.argtypes = [vp]
     L.gv_ed_keys_generation.restype = ctypes.c_uint64
+    L.gv_ed_keys_replace.argtypes = [vp, sz, vp, vp]
+    L.gv_ed_keys_replace.restype = i32
+    L.gv_ed_keys_point.argtypes = [vp, sz, vp, ctypes.c_uint32, ctypes.c_uint32, vp, vp, vp]
+    L.gv_ed_keys_point.restype = i32
     L.gv_verify_ed25519_msgs_keyed.argtypes = [vp, sz, vp, vp, vp, vp, vp, vp]
     L.gv_verify_ed25519_msgs_keyed.restype = i32
     L.gv_set_option.argtypes = [vp, ctypes.c_char_p, ctypes.c_longlong]
@@ -455,6 +460,36 @@ class Verifier:
         if n:
             _check(self._L.gv_ed_keys_load(self._ctx, n, _ptr(pub32), _ptr(slots)), "gv_ed_keys_load")
         return slots
+
+    def ed_keys_replace(self, slots: np.ndarray, pub32: np.ndarray):
+        """Rebuild loaded ed25519 slots in place: slot slots[i] then holds key pub32[i] as if it had
+        been loaded there (ed_keys_count and ed_keys_generation do not move: the caller keeps its
+        own pubkey -> slot map right).  Slots must be loaded and distinct."""
+        slots = np.ascontiguousarray(slots)
+        pub32 = np.ascontiguousarray(pub32)
+        if slots.ndim != 1 or slots.dtype.kind not in "ui" or (slots.size and (slots.min() < 0 or slots.max() >= 2 ** 32)):
+            raise ValueError("ed_keys_replace: slots must be a 1-d array of u32 slot numbers")
+        if pub32.dtype != np.uint8 or pub32.ndim != 2 or pub32.shape[1] != 32:
+            raise ValueError("ed_keys_replace: pub32 must be an (n, 32) uint8 array")
+        if pub32.shape[0] != slots.shape[0]:
+            raise ValueError(f"ed_keys_replace: {slots.shape[0]} slots for {pub32.shape[0]} keys")
+        slots = np.ascontiguousarray(slots, dtype=np.uint32)
+        n = slots.shape[0]
+        if n:
+            _check(self._L.gv_ed_keys_replace(self._ctx, n, _ptr(slots), _ptr(pub32)), "gv_ed_keys_replace")
+
+    def ed_keys_point(self, slots: np.ndarray, w: int = 0, j: int = 1):
+        """For `slots` of the ed25519 key arena: the encoding of table entry j * 16^w * (-A)
+        (n x 32 bytes), the raw key bytes (n x 32) and the FromBytes verdicts."""
+        slots = np.ascontiguousarray(slots, dtype=np.uint32)
+        n = slots.shape[0]
+        enc = np.zeros((n, 32), dtype=np.uint8)
+        pub = np.zeros((n, 32), dtype=np.uint8)
+        ok = np.zeros(n, dtype=np.uint8)
+        if n:
+            _check(self._L.gv_ed_keys_point(self._ctx, n, _ptr(slots), w, j, _ptr(enc), _ptr(pub), _ptr(ok)),
+                   "gv_ed_keys_point")
+        return enc, pub, ok
 
     def ed_keys_reset(self):
         _check(self._L.gv_ed_keys_reset(self._ctx), "gv_ed_keys_reset")

@@ -84,6 +84,10 @@ def lib():
         L.gvh_set_key_resident.restype = None
         L.gvh_get_key_stats.argtypes = [vp, ctypes.POINTER(sz), ctypes.POINTER(u64), ctypes.POINTER(u64)]
         L.gvh_get_key_stats.restype = None
+        L.gvh_set_ed_key_resident.argtypes = [vp, ctypes.c_size_t]
+        L.gvh_set_ed_key_resident.restype = None
+        L.gvh_get_ed_key_stats.argtypes = [vp, ctypes.POINTER(sz), ctypes.POINTER(u64), ctypes.POINTER(u64)]
+        L.gvh_get_ed_key_stats.restype = None
         L.gvh_set_gpu_hash.argtypes = [vp, ctypes.c_int]
         L.gvh_get_gpu_hash.argtypes = [vp]
         L.gvh_get_keyed.argtypes = [vp, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(sz), ctypes.POINTER(sz)]
@@ -350,6 +354,17 @@ class HostApp:
         """(resident size in force, slots replaced, arena resets)"""
         r, rep, rs = ctypes.c_size_t(), ctypes.c_uint64(), ctypes.c_uint64()
         self._L.gvh_get_key_stats(self._app, ctypes.byref(r), ctypes.byref(rep), ctypes.byref(rs))
+        return r.value, rep.value, rs.value
+
+    def set_ed_key_resident(self, resident: int):
+        """Keep the ed25519 key arena at `resident` slots: fresh keys past it replace the victims
+        of a second-chance clock (gv_ed_keys_replace); 0 (default): off."""
+        self._L.gvh_set_ed_key_resident(self._app, resident)
+
+    def ed_key_stats(self):
+        """(ed25519 resident size in force, slots replaced, arena resets)"""
+        r, rep, rs = ctypes.c_size_t(), ctypes.c_uint64(), ctypes.c_uint64()
+        self._L.gvh_get_ed_key_stats(self._app, ctypes.byref(r), ctypes.byref(rep), ctypes.byref(rs))
         return r.value, rep.value, rs.value
 
     def set_gpu_hash(self, on: bool):

@@ -41,6 +41,7 @@
 // gv_keys_replace through a weak reference: a library that does not define
 // it (the sanitizer harness' CPU stand-in) leaves eviction off.
 extern "C" int gv_keys_replace(gv_ctx* ctx, size_t n, const uint32_t* slots, const uint8_t* pub33) __attribute__((weak));
+extern "C" int gv_ed_keys_replace(gv_ctx* ctx, size_t n, const uint32_t* slots, const uint8_t* pub32) __attribute__((weak));
 
 namespace {
 
@@ -1276,6 +1277,80 @@ class FlatSlotMap {
   const uint64_t seed_ = ((uint64_t)std::random_device{}() << 32) ^ std::random_device{}();
 };
 
+// Second-chance clock over the slots of a key arena kept at a resident size
+// (the ed25519 arena, gvh_set_ed_key_resident; verify_secp keeps the same
+// state in gvh_app's slot_* members).  Per slot: the K-byte key it holds (the
+// map's reverse), a reference bit set by every batch that names the slot, and
+// the stamp of the last such batch -- a slot named by the batch in hand is
+// never a victim.  The hand persists across batches.  Not thread-safe.
+template <size_t K>
+struct SlotClock {
+  std::vector<std::array<uint8_t, K>> key;
+  std::vector<uint8_t> ref;
+  std::vector<uint64_t> stamp;
+  size_t hand = 0;
+  void clear() {
+    key.clear();
+    ref.clear();
+    stamp.clear();
+    hand = 0;
+    taken_.clear();
+    cleared_.clear();
+  }
+  void touch(uint32_t slot, uint64_t st) {        // the batch with stamp st names the slot
+    if (slot >= ref.size()) return;
+    ref[slot] = 1;
+    stamp[slot] = st;
+  }
+  void holds(uint32_t slot, const uint8_t* k, uint64_t st) {   // the slot now holds key k
+    if (slot >= key.size()) {
+      key.resize(slot + 1, {});
+      ref.resize(slot + 1, 0);
+      stamp.resize(slot + 1, 0);
+    }
+    memcpy(key[slot].data(), k, K);
+    touch(slot, st);
+  }
+  // nv victims among the first `count` slots, from the hand: two turns at most
+  // (the first clears reference bits, the second takes).  False, and nothing
+  // changed, when there are too few evictable slots.
+  bool sweep(size_t count, size_t nv, uint64_t st, std::vector<uint32_t>& victims) {
+    taken_.clear();
+    cleared_.clear();
+    hand0_ = hand;
+    const size_t span = std::min(count, key.size());
+    size_t h = span ? hand % span : 0;
+    for (size_t step = 0; step < 2 * span && taken_.size() < nv; ++step, h = (h + 1) % span) {
+      if (stamp[h] == st) continue;               // named by the batch in hand
+      if (ref[h]) {
+        ref[h] = 0;
+        cleared_.push_back((uint32_t)h);
+      } else {
+        taken_.push_back((uint32_t)h);
+        stamp[h] = st;                            // (taken: not twice in one sweep)
+      }
+    }
+    if (taken_.size() < nv) {
+      undo();
+      return false;
+    }
+    hand = h;
+    victims = taken_;
+    return true;
+  }
+  void undo() {                                   // the last sweep never happened
+    for (uint32_t v : taken_) stamp[v] = 0;
+    for (uint32_t c : cleared_) ref[c] = 1;
+    hand = hand0_;
+    taken_.clear();
+    cleared_.clear();
+  }
+
+ private:
+  std::vector<uint32_t> taken_, cleared_;
+  size_t hand0_ = 0;
+};
+
 // A decoded amino pubkey with its canonical bytes (pk.Bytes()), address and
 // CountSubKeys -- pure functions of the amino bytes, shared by every tx and
 // account that carries the same key.
@@ -1547,6 +1622,11 @@ struct gvh_app {
     slot_stamp.clear();
     clock_hand = 0;
   }
+  // the same for the ed25519 arena (gvh_set_ed_key_resident, gv_ed_keys_replace); under gpu_mu
+  size_t ed_key_resident = 0;
+  SlotClock<32> ed_clock;
+  uint64_t ed_batch_stamp = 0;
+  uint64_t ed_keys_replaced = 0, ed_key_resets = 0;
   int threads = std::max(1, std::min(16, (int)std::thread::hardware_concurrency()));
   std::unique_ptr<Pool> pool{new Pool(threads - 1)};
   std::mutex pool_mu;                          // guards replacing the pool (gvh_set_threads)
@@ -2186,15 +2266,25 @@ int verify_secp(gvh_app* app, GpuBatch& b, uint64_t* ticket = nullptr) {
 // a block-sized batch) -- the missing keys are then loaded with one
 // gv_ed_keys_load; otherwise, or on any arena problem, the unkeyed batch.
 // Same verdicts either way (gv_verify_ed25519_msgs_keyed's contract).
+// With a resident size (gvh_set_ed_key_resident) the arena stops growing
+// there, by verify_secp's rule: fresh keys take the free slots with one
+// gv_ed_keys_load, the rest replace the clock's victims with one
+// gv_ed_keys_replace; a batch with too few evictable slots runs unkeyed and
+// changes nothing.  Resident size 0: the arena starts over at GV_ED_KEY_CAP.
 int verify_ed(gvh_app* app, size_t m, const uint8_t* pub, const uint8_t* sig, const uint8_t* blob, const uint64_t* off,
               const uint32_t* len, uint8_t* ok, bool load) {
   if (!app->keyed) return gv_verify_ed25519_msgs(app->gpu, m, pub, sig, blob, off, len, ok);
+  auto plain = [&] { return gv_verify_ed25519_msgs(app->gpu, m, pub, sig, blob, off, len, ok); };
   auto& map = app->ed_slots;
+  auto& clk = app->ed_clock;
   const uint64_t gen = gv_ed_keys_generation(app->gpu);
   if (gen != app->ed_key_gen) {                   // the arena was reset (here or by another user)
     map.clear();
+    clk.clear();
     app->ed_key_gen = gen;
   }
+  const bool evict = app->ed_key_resident > 0 && gv_ed_keys_replace != nullptr;
+  const uint64_t stamp = evict ? ++app->ed_batch_stamp : 0;
   std::vector<uint32_t> slots(m);
   std::vector<uint8_t> fresh;
   std::vector<std::array<uint8_t, 32>> fresh_keys;
@@ -2202,8 +2292,12 @@ int verify_ed(gvh_app* app, size_t m, const uint8_t* pub, const uint8_t* sig, co
   for (size_t k = 0; k < m; ++k) {
     std::array<uint8_t, 32> key;
     memcpy(key.data(), pub + 32 * k, 32);
-    if (const uint32_t* v = map.find(key.data())) { slots[k] = *v; continue; }
-    if (!load) return gv_verify_ed25519_msgs(app->gpu, m, pub, sig, blob, off, len, ok);
+    if (const uint32_t* v = map.find(key.data())) {
+      slots[k] = *v;
+      if (evict && *v < kPending) clk.touch(*v, stamp);   // this batch names the slot
+      continue;
+    }
+    if (!load) return plain();
     auto ins = map.emplace(key.data(), kPending + (uint32_t)fresh_keys.size());
     if (ins.second) {
       fresh.insert(fresh.end(), key.begin(), key.end());
@@ -2214,18 +2308,60 @@ int verify_ed(gvh_app* app, size_t m, const uint8_t* pub, const uint8_t* sig, co
   if (!fresh_keys.empty()) {
     const size_t nf = fresh_keys.size();
     std::vector<uint32_t> got(nf);
-    const bool room = gv_ed_keys_count(app->gpu) + nf <= GV_ED_KEY_CAP;
-    if (!room || gv_ed_keys_load(app->gpu, nf, fresh.data(), got.data()) != GV_OK) {
-      if (!room) {
-        gv_ed_keys_reset(app->gpu);
-        map.clear();
-        app->ed_key_gen = gv_ed_keys_generation(app->gpu);
-      } else {
-        for (auto& key : fresh_keys) map.erase(key.data());
-      }
-      return gv_verify_ed25519_msgs(app->gpu, m, pub, sig, blob, off, len, ok);
+    const size_t count = gv_ed_keys_count(app->gpu);
+    // resident size: the fresh keys take the free slots up to it, the rest
+    // replace the clock's victims; 0: every fresh key is loaded
+    const size_t free_slots = !evict ? nf : count < app->ed_key_resident ? app->ed_key_resident - count : 0;
+    const size_t nl = std::min(nf, free_slots), nv = nf - nl;
+    auto drop_pending = [&] {
+      for (auto& key : fresh_keys) map.erase(key.data());
+    };
+    auto start_over = [&] {
+      gv_ed_keys_reset(app->gpu);
+      map.clear();
+      clk.clear();
+      app->ed_key_gen = gv_ed_keys_generation(app->gpu);
+    };
+    std::vector<uint32_t> victims;
+    if (nv && !clk.sweep(count, nv, stamp, victims)) {   // too few evictable slots: nothing changes
+      drop_pending();
+      return plain();
     }
-    for (size_t i = 0; i < nf; ++i) map.set(fresh_keys[i].data(), got[i]);
+#ifdef GVH_EVICT_AUDIT
+    for (size_t k = 0; k < m; ++k)                 // no slot the batch names is a victim
+      for (uint32_t v : victims)
+        if (slots[k] == v) abort();
+#endif
+    const bool room = count + nl <= GV_ED_KEY_CAP;
+    if (!room || (nl && gv_ed_keys_load(app->gpu, nl, fresh.data(), got.data()) != GV_OK)) {
+      if (!room) {
+        start_over();
+      } else {
+        clk.undo();
+        drop_pending();
+      }
+      return plain();
+    }
+    if (nv && gv_ed_keys_replace(app->gpu, nv, victims.data(), fresh.data() + 32 * nl) != GV_OK) {
+      start_over();                                // no slot named in a failed replacement is trusted
+      app->ed_key_resets++;
+      return plain();
+    }
+    if (evict) {
+      for (size_t i = 0; i < nl; ++i) {
+        map.set(fresh_keys[i].data(), got[i]);
+        clk.holds(got[i], fresh_keys[i].data(), stamp);
+      }
+      for (size_t i = 0; i < nv; ++i) {             // erase the victim's key, set the fresh key
+        map.erase(clk.key[victims[i]].data());
+        got[nl + i] = victims[i];
+        map.set(fresh_keys[nl + i].data(), victims[i]);
+        clk.holds(victims[i], fresh_keys[nl + i].data(), stamp);
+      }
+      app->ed_keys_replaced += nv;
+    } else {
+      for (size_t i = 0; i < nf; ++i) map.set(fresh_keys[i].data(), got[i]);
+    }
     for (size_t k = 0; k < m; ++k)
       if (slots[k] >= kPending) slots[k] = got[slots[k] - kPending];
   }
@@ -3303,6 +3439,27 @@ void gvh_get_key_stats(gvh_app* app, size_t* resident, uint64_t* replaced, uint6
   if (resident) *resident = app->key_resident;
   if (replaced) *replaced = app->keys_replaced;
   if (resets) *resets = app->key_resets;
+}
+
+void gvh_set_ed_key_resident(gvh_app* app, size_t resident) {
+  std::lock_guard<std::mutex> g(app->gpu_mu);
+  if (!gv_ed_keys_replace) resident = 0;          // a library without gv_ed_keys_replace: eviction stays off
+  resident = std::min<size_t>(resident, GV_ED_KEY_CAP);
+  if (resident == app->ed_key_resident) return;
+  // the clock starts from an empty arena: slots loaded before carry no reverse entry
+  if (resident && app->gpu && app->keyed && gv_ed_keys_count(app->gpu)) {
+    gv_ed_keys_reset(app->gpu);
+    app->ed_slots.clear();
+    app->ed_key_gen = gv_ed_keys_generation(app->gpu);
+  }
+  app->ed_clock.clear();
+  app->ed_key_resident = resident;
+}
+void gvh_get_ed_key_stats(gvh_app* app, size_t* resident, uint64_t* replaced, uint64_t* resets) {
+  std::lock_guard<std::mutex> g(app->gpu_mu);
+  if (resident) *resident = app->ed_key_resident;
+  if (replaced) *replaced = app->ed_keys_replaced;
+  if (resets) *resets = app->ed_key_resets;
 }
 
 void gvh_set_gpu_hash(gvh_app* app, int on) {

@@ -185,6 +185,24 @@ void gvh_set_key_resident(gvh_app* app, size_t resident);
 /* The resident size in force, the slots replaced and the arena resets (cap
  * reached, failed replacement) since the app was made. */
 void gvh_get_key_stats(gvh_app* app, size_t* resident, uint64_t* replaced, uint64_t* resets);
+/* The same for the ed25519 key arena (IBC validator sets, multisig ed25519
+ * sub-keys; 72 KB of HBM per key).  resident > 0: a batch that loads keys (a
+ * trusted commit's validator set, a block-sized batch) puts its fresh keys
+ * into the free slots up to `resident` with one gv_ed_keys_load and the rest
+ * into the slots of second-chance victims with one gv_ed_keys_replace (a slot
+ * named by the batch in hand is never a victim; the hand persists across
+ * batches); a batch with too few evictable slots runs unkeyed and changes
+ * nothing; a failed replacement resets the arena and counts a reset.  A
+ * batch that does not load still goes keyed only when every key is resident,
+ * and sets the reference bits of the slots it names.  0 (default): off -- the
+ * arena grows to GV_ED_KEY_CAP and starts over there.  A size above
+ * GV_ED_KEY_CAP is clamped to it.  Changing the size while keys are resident
+ * starts the arena over.  Same verdicts either way.  Against a library
+ * without gv_ed_keys_replace the setting stays 0. */
+void gvh_set_ed_key_resident(gvh_app* app, size_t resident);
+/* The ed25519 resident size in force, the slots replaced and the arena resets
+ * after a failed replacement since the app was made. */
+void gvh_get_ed_key_stats(gvh_app* app, size_t* resident, uint64_t* replaced, uint64_t* resets);
 /* gpu_hash = 1: PreVerifyTxs of a block being delivered, with an empty
  * verdict cache, hands the secp256k1 leaves' sign bytes to the GPU
  * (gv_verify_msgs / gv_verify_msgs_keyed, SHA-256 in the batch) instead of

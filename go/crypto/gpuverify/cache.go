@@ -5,6 +5,7 @@ import (
 	"crypto/sha256"
 	"sync"
 
+	"github.com/tendermint/tendermint/crypto/ed25519"
 	"github.com/tendermint/tendermint/crypto/secp256k1"
 )
 
@@ -164,4 +165,24 @@ func (c *slotClock) victims(count, need int) (v []uint32, undo func()) {
 	}
 	c.hand = h
 	return v, undo
+}
+
+// edSlotClock is the same clock over the ed25519 key arena's slots (GPU
+// EdKeyResident; host/gvhost.cpp verify_ed).  The reference bits, stamps and
+// the hand are slotClock's; its key array only counts the slots here, and the
+// ed25519 keys the slots hold stand beside it.
+type edSlotClock struct {
+	slotClock
+	edKeys []ed25519.PubKeyEd25519
+}
+
+func (c *edSlotClock) reset() { c.slotClock.reset(); c.edKeys = nil }
+
+// hold records that slot now holds key, named by the batch in hand.
+func (c *edSlotClock) hold(slot uint32, key ed25519.PubKeyEd25519) {
+	c.slotClock.hold(slot, secp256k1.PubKeySecp256k1{})
+	for int(slot) >= len(c.edKeys) {
+		c.edKeys = append(c.edKeys, ed25519.PubKeyEd25519{})
+	}
+	c.edKeys[slot] = key
 }

@@ -134,6 +134,7 @@ type Stats struct {
 	KeyedCalls, Pub33Calls, EdCalls uint64
 	KeyLoads, KeyResets             uint64
 	KeyReplaced                     uint64 // slots rewritten by gv_keys_replace (KeyResident)
+	EdKeyReplaced                   uint64 // slots rewritten by gv_ed_keys_replace (EdKeyResident)
 	BatchLog2                       [24]uint64
 	LatencyUsLog2                   [24]uint64
 }
@@ -141,6 +142,7 @@ type Stats struct {
 type counters struct {
 	gpuCalls, gpuLeaves, cpuRouted, cpuRoutedLeaves, fbCalls, fbLeaves uint64
 	keyed, pub33, ed, keyLoads, keyResets, keyReplaced                uint64
+	edKeyReplaced                                                     uint64
 	batch, lat                                                        [24]uint64
 }
 
@@ -184,6 +186,7 @@ func (g *GPU) Stats() Stats {
 		KeyedCalls: atomic.LoadUint64(&c.keyed), Pub33Calls: atomic.LoadUint64(&c.pub33),
 		EdCalls: atomic.LoadUint64(&c.ed), KeyLoads: atomic.LoadUint64(&c.keyLoads),
 		KeyResets: atomic.LoadUint64(&c.keyResets), KeyReplaced: atomic.LoadUint64(&c.keyReplaced),
+		EdKeyReplaced: atomic.LoadUint64(&c.edKeyReplaced),
 	}
 	for k := range s.BatchLog2 {
 		s.BatchLog2[k] = atomic.LoadUint64(&c.batch[k])
@@ -227,6 +230,12 @@ type GPU struct {
 	// EdKeyCap: the same for the ed25519 key arena (72 KB of HBM per key;
 	// default GV_ED_KEY_CAP, env GV_ED_KEY_CAP).
 	EdKeyCap int
+	// EdKeyResident: keep the ed25519 arena at this many slots (0 = off, the
+	// default; at most EdKeyCap): a validator set's fresh keys beyond the free
+	// slots replace the victims of a second-chance clock (gv_ed_keys_replace)
+	// instead of the arena starting over at EdKeyCap with every chain's keys
+	// dropped together.  Set before the first keyed ed25519 batch.
+	EdKeyResident int
 	// KeysWideQW: the window widths the key arena's wide tables may take
 	// (gv_set_option "keys_wide_qw"): 0 = 11-bit tables, then 9-bit ones when
 	// those no longer fit; 11 or 9 = that width only.  Applies to an arena
@@ -244,6 +253,7 @@ type GPU struct {
 	clock   slotClock                            // KeyResident: the slots' keys, reference bits and the hand
 	edSlots map[ed25519.PubKeyEd25519]uint32     // ed25519 key -> ed25519 key-arena slot (gv_ed_keys_load)
 	edGen   uint64                               // gv_ed_keys_generation the ed25519 map belongs to
+	edClock edSlotClock                          // EdKeyResident: the same clock over the ed25519 slots
 }
 
 var (
@@ -946,18 +956,34 @@ func (g *GPU) VerifyBatchKeyed(pubs []secp256k1.PubKeySecp256k1, msgs, sigs [][]
 
 // edSlotsLocked returns each key's ed25519 arena slot (g.mu held), loading
 // the keys not resident with ONE gv_ed_keys_load when load is true; all is
-// false when some key is not resident afterwards.
+// false when some key is not resident afterwards.  Under EdKeyResident the
+// arena stops growing there (the C++ mirror's rule, host/gvhost.cpp
+// verify_ed): the fresh keys take the free slots up to it, the rest replace
+// the clock's victims with one gv_ed_keys_replace -- a slot named by this
+// batch is never a victim --, and a batch with too few evictable slots goes
+// unkeyed and changes nothing.
 func (g *GPU) edSlotsLocked(pubs []ed25519.PubKeyEd25519, load bool) (slots []uint32, all bool) {
 	if gen := uint64(C.gv_ed_keys_generation(g.ctx)); gen != g.edGen {
 		g.edSlots = map[ed25519.PubKeyEd25519]uint32{}
+		g.edClock.reset()
 		g.edGen = gen
+	}
+	resident := g.EdKeyResident
+	if resident > g.EdKeyCap {
+		resident = g.EdKeyCap
 	}
 	slots = make([]uint32, len(pubs))
 	var fresh []ed25519.PubKeyEd25519
 	seen := map[ed25519.PubKeyEd25519]bool{}
+	if resident > 0 {
+		g.edClock.begin()
+	}
 	for i, p := range pubs {
 		if s, ok := g.edSlots[p]; ok {
 			slots[i] = s
+			if resident > 0 {
+				g.edClock.touch(s)
+			}
 		} else if !seen[p] {
 			seen[p] = true
 			fresh = append(fresh, p)
@@ -969,7 +995,23 @@ func (g *GPU) edSlotsLocked(pubs []ed25519.PubKeyEd25519, load bool) (slots []ui
 	if !load || len(fresh) > g.EdKeyCap {
 		return slots, false
 	}
-	if int(C.gv_ed_keys_count(g.ctx))+len(fresh) > g.EdKeyCap { // start the arena over (the C++ mirror's rule)
+	count := int(C.gv_ed_keys_count(g.ctx))
+	nl := len(fresh) // loaded into free slots; the rest go into victims' slots
+	var victims []uint32
+	undo := func() {}
+	if resident > 0 {
+		free := 0
+		if count < resident {
+			free = resident - count
+		}
+		if nl > free {
+			nl = free
+		}
+		victims, undo = g.edClock.victims(count, len(fresh)-nl)
+		if victims == nil && len(fresh) > nl {
+			return slots, false
+		}
+	} else if count+len(fresh) > g.EdKeyCap { // start the arena over (the C++ mirror's rule)
 		atomic.AddUint64(&g.cnt.keyResets, 1)
 		C.gv_ed_keys_reset(g.ctx)
 		g.edSlots = map[ed25519.PubKeyEd25519]uint32{}
@@ -982,13 +1024,37 @@ func (g *GPU) edSlotsLocked(pubs []ed25519.PubKeyEd25519, load bool) (slots []ui
 	for k, p := range fresh {
 		copy(buf.b[32*k:], p[:])
 	}
-	atomic.AddUint64(&g.cnt.keyLoads, 1)
-	if C.gv_ed_keys_load(g.ctx, C.size_t(len(fresh)), (*C.uint8_t)(buf.p), (*C.uint32_t)(out.p)) != 0 {
-		return slots, false
+	got := (*[maxBatchBytes / 4]uint32)(out.p)[:len(fresh):len(fresh)]
+	if nl > 0 {
+		atomic.AddUint64(&g.cnt.keyLoads, 1)
+		if C.gv_ed_keys_load(g.ctx, C.size_t(nl), (*C.uint8_t)(buf.p), (*C.uint32_t)(out.p)) != 0 {
+			undo()
+			return slots, false
+		}
 	}
-	s := (*[maxBatchBytes / 4]uint32)(out.p)[:len(fresh):len(fresh)]
+	if len(victims) > 0 {
+		copy(got[nl:], victims)
+		vb := unsafe.Pointer(&got[nl])
+		kb := unsafe.Pointer(&buf.b[32*nl])
+		if C.gv_ed_keys_replace(g.ctx, C.size_t(len(victims)), (*C.uint32_t)(vb), (*C.uint8_t)(kb)) != 0 {
+			// no slot named in a failed replacement is trusted: start the arena over
+			atomic.AddUint64(&g.cnt.keyResets, 1)
+			C.gv_ed_keys_reset(g.ctx)
+			g.edSlots = map[ed25519.PubKeyEd25519]uint32{}
+			g.edClock.reset()
+			g.edGen = uint64(C.gv_ed_keys_generation(g.ctx))
+			return slots, false
+		}
+		atomic.AddUint64(&g.cnt.edKeyReplaced, uint64(len(victims)))
+	}
 	for k, p := range fresh {
-		g.edSlots[p] = s[k]
+		if k >= nl { // erase the victim's key, set the fresh key
+			delete(g.edSlots, g.edClock.edKeys[got[k]])
+		}
+		g.edSlots[p] = got[k]
+		if resident > 0 {
+			g.edClock.hold(got[k], p)
+		}
 	}
 	for i, p := range pubs {
 		slots[i] = g.edSlots[p]

@@ -39,6 +39,9 @@ type GPUVerifyConfig struct {
 	// KeyResident: keep the secp256k1 arena at this many slots by replacing
 	// the least recently used keys (gv_keys_replace); 0 = off.
 	KeyResident int `mapstructure:"key-resident"`
+	// EdKeyResident: the same for the ed25519 arena (gv_ed_keys_replace);
+	// 0 = off, at most EdKeyCap.
+	EdKeyResident int `mapstructure:"ed-key-resident"`
 	// KeysWideQW: window widths of the key arena's wide tables (gv_set_option
 	// keys_wide_qw): 0 = 11-bit, then 9-bit when those no longer fit; 11 or 9
 	// = that width only.
@@ -61,8 +64,8 @@ type GPUVerifyConfig struct {
 func DefaultGPUVerifyConfig() GPUVerifyConfig {
 	return GPUVerifyConfig{
 		Enable: false, Devices: "", MaxBatch: 1 << 20, CPUBelow: 4, Keyed: true, KeyLoadMin: 4096,
-		KeyCap: 1 << 22, EdKeyCap: 1 << 16, KeyResident: 0, KeysWideQW: 0, CacheEntries: 1 << 20, CheckTxWindowTxs: 64,
-		CheckTxWindow: 200 * time.Microsecond, PreVerifyBlocks: true,
+		KeyCap: 1 << 22, EdKeyCap: 1 << 16, KeyResident: 0, EdKeyResident: 0, KeysWideQW: 0, CacheEntries: 1 << 20,
+		CheckTxWindowTxs: 64, CheckTxWindow: 200 * time.Microsecond, PreVerifyBlocks: true,
 	}
 }
 
@@ -94,6 +97,8 @@ func (c GPUVerifyConfig) Validate() error {
 		return fmt.Errorf("gpu-verify: negative or zero size in %+v", c)
 	case c.KeyResident < 0 || c.KeyResident > c.KeyCap:
 		return fmt.Errorf("gpu-verify.key-resident must be 0 (off) or at most key-cap, got %d", c.KeyResident)
+	case c.EdKeyResident < 0 || c.EdKeyResident > c.EdKeyCap:
+		return fmt.Errorf("gpu-verify.ed-key-resident must be 0 (off) or at most ed-key-cap, got %d", c.EdKeyResident)
 	case c.KeysWideQW != 0 && c.KeysWideQW != 9 && c.KeysWideQW != 11:
 		return fmt.Errorf("gpu-verify.keys-wide-qw must be 0, 9 or 11, got %d", c.KeysWideQW)
 	case c.CheckTxWindowTxs < 1 || c.CheckTxWindow < 0:
@@ -132,6 +137,11 @@ ed-key-cap = {{ .GPUVerify.EdKeyCap }}
 # used ones (0 = off: the arena grows to key-cap and is reset there).  65536
 # keeps the fastest wide-table layout whatever the number of accounts seen.
 key-resident = {{ .GPUVerify.KeyResident }}
+
+# The same for the ed25519 arena (IBC validator sets, multisig ed25519
+# sub-keys; 72 KiB of GPU memory per key): 0 = off, the arena grows to
+# ed-key-cap and starts over there with every chain's keys dropped together.
+ed-key-resident = {{ .GPUVerify.EdKeyResident }}
 
 # Window width of the key arena's wide tables: 0 = 11-bit tables (768 / 384 KiB
 # per key), then 9-bit ones (240 / 128 KiB) when those no longer fit; 11 or 9 =

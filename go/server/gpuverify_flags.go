@@ -24,6 +24,7 @@ const (
 	FlagGPUVerifyKeyed    = "gpu-verify.keyed"
 	FlagGPUVerifyWindow   = "gpu-verify.checktx-window"
 	FlagGPUVerifyResident = "gpu-verify.key-resident"
+	FlagGPUVerifyEdRes    = "gpu-verify.ed-key-resident"
 )
 
 // AddGPUVerifyFlags registers the flags that override app.toml.
@@ -36,8 +37,9 @@ func AddGPUVerifyFlags(cmd *cobra.Command) {
 	cmd.Flags().Bool(FlagGPUVerifyKeyed, d.Keyed, "Keep account keys parsed in GPU memory")
 	cmd.Flags().Duration(FlagGPUVerifyWindow, d.CheckTxWindow, "Concurrent CheckTx accumulation window")
 	cmd.Flags().Int(FlagGPUVerifyResident, d.KeyResident, "Keep the account-key arena at this many keys (0 = off)")
+	cmd.Flags().Int(FlagGPUVerifyEdRes, d.EdKeyResident, "Keep the ed25519 key arena at this many keys (0 = off)")
 	for _, f := range []string{FlagGPUVerify, FlagGPUVerifyDevices, FlagGPUVerifyMaxBatch, FlagGPUVerifyCPUBelow,
-		FlagGPUVerifyKeyed, FlagGPUVerifyWindow, FlagGPUVerifyResident} {
+		FlagGPUVerifyKeyed, FlagGPUVerifyWindow, FlagGPUVerifyResident, FlagGPUVerifyEdRes} {
 		_ = viper.BindPFlag(f, cmd.Flags().Lookup(f))
 	}
 }
@@ -66,6 +68,7 @@ func NewGPUVerifier(cfg config.GPUVerifyConfig, logger log.Logger) (gv.Verifier,
 	}
 	g.CPUBelow, g.Keyed, g.KeyLoadMin = cfg.CPUBelow, cfg.Keyed, cfg.KeyLoadMin
 	g.KeyCap, g.EdKeyCap, g.KeyResident = cfg.KeyCap, cfg.EdKeyCap, cfg.KeyResident
+	g.EdKeyResident = cfg.EdKeyResident
 	if err := g.SetOption("keys_wide_qw", int64(cfg.KeysWideQW)); err != nil {
 		logger.Error("gpu-verify: keys-wide-qw not applied", "err", err)
 	} else {

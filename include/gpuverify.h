@@ -169,7 +169,10 @@ uint64_t gv_keys_generation(const gv_ctx* ctx);
 #define GV_CPU_CROSSOVER 4
 #define GV_KEY_LOAD_MIN 4096
 #define GV_KEY_CAP (1u << 22)
-/* ... and the ed25519 key arena's (gv_ed_keys_load: 72 KB of HBM per key). */
+/* ... and the ed25519 key arena's (gv_ed_keys_load: 72 KB of HBM per key),
+ * unless the caller keeps it at a resident size below this by replacing
+ * slots (gv_ed_keys_replace; gvh_set_ed_key_resident, the shim's
+ * EdKeyResident). */
 #define GV_ED_KEY_CAP (1u << 16)
 
 /* Key-arena readback (tests, tools): for each slot, the affine point the
@@ -229,6 +232,35 @@ int gv_ed_keys_load(gv_ctx* ctx, size_t n, const uint8_t* pub32, uint32_t* slot_
 int gv_ed_keys_reset(gv_ctx* ctx);
 size_t gv_ed_keys_count(const gv_ctx* ctx);
 uint64_t gv_ed_keys_generation(const gv_ctx* ctx);
+/* Replacement: after GV_OK slot slots[i] behaves on every ed25519 keyed
+ * route -- k_ed_lat_sl up to "ed_lat_max", k_ed_keyed past it, with
+ * "ed_keyed" 0 the throughput kernels over the slot's raw key -- and in
+ * gv_ed_keys_point as if pub32 + 32*i had been loaded into it (a key
+ * FromBytes rejects gives a false slot; a key equal to one resident in
+ * another slot is fine, the two slots are independent).  The table, the raw
+ * bytes and the verdict are rebuilt on every device of the context, by the
+ * kernels of gv_ed_keys_load ("ed_keys_split" picks the same pair), and the
+ * host copy of the raw bytes follows once every device has succeeded.
+ * Nothing is allocated in the arena, grown or moved: gv_ed_keys_count and
+ * gv_ed_keys_generation do not change, so a caller that replaces a slot keeps
+ * its own pubkey -> slot map right (drop the old key's entry; the generation
+ * does not tell).  It takes the locks of gv_ed_keys_load (the arena's, then
+ * each device's); keyed verifies hold the arena's lock for the whole call,
+ * so a replacement never runs under one.
+ * GV_EINVAL, and nothing changed, when a slot is >= gv_ed_keys_count() or
+ * appears twice (ctx, slots or pub32 NULL with n > 0 too); n == 0 is GV_OK.
+ * On GV_EHIP, or GV_ENOMEM from the scratch allocation, no slot named in the
+ * call is trusted: the caller must gv_ed_keys_reset.  Option
+ * "ed_keys_replaced" (read-only) counts the slots replaced since gv_open. */
+int gv_ed_keys_replace(gv_ctx* ctx, size_t n, const uint32_t* slots, const uint8_t* pub32);
+/* ed25519 key-arena readback (tests, tools): for each slot, out_enc32 + 32*i
+ * = the canonical encoding of entry (w, j) of its table, j * 16^w * (-A)
+ * (w < 64, 1 <= j <= 8, else GV_EINVAL); out_pub32 + 32*i = the raw key bytes
+ * Verify hashes; out_ok[i] = its FromBytes verdict.  A slot >=
+ * gv_ed_keys_count(): zeros and 0; a rejected key: its bytes, 0 and a zero
+ * encoding.  Reads the first device's arena under gv_ed_keys_load's locks. */
+int gv_ed_keys_point(gv_ctx* ctx, size_t n, const uint32_t* slots, uint32_t w, uint32_t j, uint8_t* out_enc32,
+                     uint8_t* out_pub32, uint8_t* out_ok);
 int gv_verify_ed25519_msgs_keyed(gv_ctx* ctx, size_t n, const uint32_t* slot, const uint8_t* sig64,
                                  const uint8_t* msg_blob, const uint64_t* msg_off, const uint32_t* msg_len,
                                  uint8_t* out_ok);
@@ -399,8 +431,8 @@ int gv_set_option(gv_ctx* ctx, const char* key, long long val);
  * was built with (11 / 9; "kwn_qw" 0: one width only), and "kw_arena_qw" /
  * "kw_arena_ng", the window width and the group count of the first device's
  * wide arena as the last gv_keys_load left it (both 0: no slot has wide
- * tables), and "keys_replaced", the slots gv_keys_replace has rewritten
- * since gv_open.  GV_EINVAL for any other key.  Instrumentation (bench route
+ * tables), and "keys_replaced" / "ed_keys_replaced", the slots
+ * gv_keys_replace / gv_ed_keys_replace have rewritten since gv_open.  GV_EINVAL for any other key.  Instrumentation (bench route
  * attribution). */
 int gv_get_option(gv_ctx* ctx, const char* key, long long* val);
 
