@@ -2377,6 +2377,44 @@ hipError_t stage_slots(Set* s, size_t C, const uint32_t* slots, size_t cn, hipSt
   return hipMemcpyAsync(p, slots, cn * 4, hipMemcpyHostToDevice, st);
 }
 
+// The k4 and / or the resident k6 tables of the n keys pub33 (host) into slots
+// base.. (slots: as build_wide's), one pub33 upload per chunk for both builds.
+// The k4 build takes max_batch keys at a time; the k6 tables' scratch rows per
+// key are ~12x its (GV_KN_ARENA_NG groups of 32 entries): smaller chunks.
+int build_k4k6(gv_ctx* ctx, Dev* d, Set* s, hipStream_t st, const uint8_t* pub33, size_t n, size_t base,
+               const uint32_t* slots, bool k4, bool k6) {
+  const size_t step = k6 ? std::min<size_t>(ctx->max_batch, 32768) : ctx->max_batch;
+  int rc;
+  for (size_t c0 = 0; c0 < n; c0 += step) {
+    const size_t cn = std::min(step, n - c0);
+    const size_t C = round_up(cn, 256);
+    // scratch: the key-table build's rows (ratios, E, and when they fit the
+    // forward-pass entries) from the start of the set's Q-table region
+    const size_t w4 = k4 ? gvk_keys_scratch_words((uint32_t)cn, GV_LGRP, GV_QTAB_N, 0) : 0;
+    const size_t w6 = k6 ? gvk_keys_scratch_words((uint32_t)cn, GV_KN_ARENA_NG, GV_K6_NT, 1) : 0;
+    const size_t Cs = std::max(C, round_up(std::max(w4, w6) / GV_QTAB_WORDS + 1, 256));
+    if ((rc = ensure_cap(s, Cs))) return rc;
+    if ((rc = set_acquire(s, st))) return rc;
+    CK(hipMemcpyAsync(s->d_in, pub33 + c0 * 33, cn * 33, hipMemcpyHostToDevice, st));
+    const uint32_t* d_slots = nullptr;
+    if (slots) CK(stage_slots(s, C, slots + c0, cn, st, &d_slots));
+    const uint32_t b0 = slots ? 0u : (uint32_t)(base + c0);
+    if (k4) {
+      const size_t room = (size_t)GV_QTAB_WORDS * s->cap;
+      const int qe4 = ctx->keys_scratch && gvk_keys_scratch_words((uint32_t)cn, GV_LGRP, GV_QTAB_N, 1) <= room;
+      CK(gvk_keys_build(s->d_in, (uint32_t)cn, (uint32_t)C, s->in_x, s->in_pfx, s->in_r, s->in_s, s->in_e, s->qtab,
+                        qe4, b0, d_slots, d->kqt, d->kzq, (uint32_t)d->kcap, d->kok, d->kqt2, d->kzq2, st));
+    }
+    if (k6)
+      CK(gvk_keys_build6(s->d_in, (uint32_t)cn, (uint32_t)C, s->in_x, s->in_pfx, s->in_r, s->in_s, s->in_e, s->qtab,
+                         ctx->keys_scratch ? 1 : 0, b0, d_slots, d->kqt6, d->kzq6, (uint32_t)d->kcap, d->kok,
+                         d->kqt62, d->kzq62, st));
+    if ((rc = set_release(s, st))) return rc;
+    CK(hipStreamSynchronize(st));              // the caller's pub33 chunk is read by then
+  }
+  return GV_OK;
+}
+
 // The wide-window tables (layout d->kw_qw / d->kw_ng) of the n keys pub33 (host) into
 // slots base.. of the wide arena, in chunks whose build scratch stays within
 // what the k6 build's chunks take.  slots (host, n entries; null: append):
@@ -2434,6 +2472,19 @@ int read_back_pub33(gv_ctx* ctx, Dev* d, hipStream_t st, size_t n, std::vector<u
   }
   return GV_OK;
 }
+
+// A replacement's slot list against an arena of `count` slots: each slot
+// loaded, none twice (two lanes would write one row).
+bool check_slots(size_t count, size_t n, const uint32_t* slots) {
+  if (n > count) return false;
+  std::vector<uint64_t> seen((count + 63) / 64, 0);
+  for (size_t i = 0; i < n; ++i) {
+    const size_t sl = slots[i];
+    if (sl >= count || (seen[sl >> 6] >> (sl & 63) & 1)) return false;
+    seen[sl >> 6] |= (uint64_t)1 << (sl & 63);
+  }
+  return true;
+}
 }  // namespace
 
 int gv_keys_load(gv_ctx* ctx, size_t n, const uint8_t* pub33, uint32_t* slot_out) {
@@ -2461,33 +2512,7 @@ int gv_keys_load(gv_ctx* ctx, size_t n, const uint8_t* pub33, uint32_t* slot_out
     if (rc) return rc;
     bool k6 = ctx->keys_k6 && d->gtab6 && d->keys6 == base;
     if ((rc = ensure_keys(d, base + n, base, st, ctx->key_cap, ctx->hbm_budget, &k6))) return rc;
-    // chunks: the k4 build takes max_batch keys at a time; the resident k6
-    // tables have GV_KN_ARENA_NG groups of 32 entries (scratch rows per key
-    // ~12x the k4 build's), so those chunks are smaller
-    const size_t step = k6 ? std::min<size_t>(ctx->max_batch, 32768) : ctx->max_batch;
-    for (size_t c0 = 0; c0 < n; c0 += step) {
-      const size_t cn = std::min(step, n - c0);
-      const size_t C = round_up(cn, 256);
-      // scratch: the key-table build's rows (ratios, E, and when they fit the
-      // forward-pass entries) from the start of the set's Q-table region
-      const size_t w4 = gvk_keys_scratch_words((uint32_t)cn, GV_LGRP, GV_QTAB_N, 0);
-      const size_t w6 = k6 ? gvk_keys_scratch_words((uint32_t)cn, GV_KN_ARENA_NG, GV_K6_NT, 1) : 0;
-      const size_t Cs = std::max(C, round_up(std::max(w4, w6) / GV_QTAB_WORDS + 1, 256));
-      if ((rc = ensure_cap(s, Cs))) return rc;
-      if ((rc = set_acquire(s, st))) return rc;
-      CK(hipMemcpyAsync(s->d_in, pub33 + c0 * 33, cn * 33, hipMemcpyHostToDevice, st));
-      const size_t room = (size_t)GV_QTAB_WORDS * s->cap;
-      const int qe4 = ctx->keys_scratch && gvk_keys_scratch_words((uint32_t)cn, GV_LGRP, GV_QTAB_N, 1) <= room;
-      CK(gvk_keys_build(s->d_in, (uint32_t)cn, (uint32_t)C, s->in_x, s->in_pfx, s->in_r, s->in_s, s->in_e,
-                        s->qtab, qe4, (uint32_t)(base + c0), nullptr, d->kqt, d->kzq,
-                        (uint32_t)d->kcap, d->kok, d->kqt2, d->kzq2, st));
-      if (k6)
-        CK(gvk_keys_build6(s->d_in, (uint32_t)cn, (uint32_t)C, s->in_x, s->in_pfx, s->in_r, s->in_s, s->in_e,
-                           s->qtab, ctx->keys_scratch ? 1 : 0, (uint32_t)(base + c0), nullptr, d->kqt6, d->kzq6,
-                           (uint32_t)d->kcap, d->kok, d->kqt62, d->kzq62, st));
-      if ((rc = set_release(s, st))) return rc;
-      CK(hipStreamSynchronize(st));            // the caller's pub33 chunk is read by then
-    }
+    if ((rc = build_k4k6(ctx, d, s, st, pub33, n, base, nullptr, true, k6))) return rc;
     if (k6) d->keys6 = base + n;
     // the wide-window tables: while every earlier slot has them and memory
     // holds the grown arena (a refusal of the last layout stops them until
@@ -2551,20 +2576,11 @@ int gv_keys_replace(gv_ctx* ctx, size_t n, const uint32_t* slots, const uint8_t*
   if (!slots || !pub33) return GV_EINVAL;
   AsyncQuiesce q(ctx);                          // a batch already submitted runs against the old keys
   std::lock_guard<std::mutex> kl(ctx->keys_mu);
-  // every check before the first device write: each slot loaded, none twice
-  // (two lanes would write one row; k_keys_tables reads a kzq column before
-  // lane 0 overwrites it)
+  // every check before the first device write (k_keys_tables reads a kzq
+  // column before lane 0 overwrites it)
   const size_t count = ctx->keys;
-  if (n > count) return GV_EINVAL;
-  {
-    std::vector<uint64_t> seen((count + 63) / 64, 0);
-    for (size_t i = 0; i < n; ++i) {
-      const size_t sl = slots[i];
-      if (sl >= count || (seen[sl >> 6] >> (sl & 63) & 1)) return GV_EINVAL;
-      seen[sl >> 6] |= (uint64_t)1 << (sl & 63);
-    }
-  }
-  std::vector<uint32_t> fs;                     // the slots (and their keys) below a table set's built prefix
+  if (!check_slots(count, n, slots)) return GV_EINVAL;
+  std::vector<uint32_t> fs;                    // the slots (and their keys) below a table set's built prefix
   std::vector<uint8_t> fp;
   for (Dev* d : ctx->devs) {                    // every device holds every key
     std::lock_guard<std::mutex> lk(d->mu);
@@ -2575,7 +2591,8 @@ int gv_keys_replace(gv_ctx* ctx, size_t n, const uint32_t* slots, const uint8_t*
     if (count > d->kcap || d->keys6 > d->kcap || d->keysw > d->kcapw) return GV_EINVAL;   // (never: the arenas hold their slots)
     int rc;
     // which: 0 the k4 tables (every slot), 1 the k6 tables (slots below keys6),
-    // 2 the wide tables in the arena's layout (slots below keysw); the chunks of gv_keys_load
+    // 2 the wide tables in the arena's layout (slots below keysw); one pass of
+    // gv_keys_load's chunks per table set
     for (int which = 0; which < 3; ++which) {
       const size_t lim = which == 0 ? count : which == 1 ? (d->kqt6 ? d->keys6 : 0) : (d->kqtw ? d->keysw : 0);
       if (lim == 0) continue;
@@ -2594,35 +2611,9 @@ int gv_keys_replace(gv_ctx* ctx, size_t n, const uint32_t* slots, const uint8_t*
         pb = fp.data();
         m = fs.size();
       }
-      if (which == 2) {
-        if ((rc = build_wide(ctx, d, s, st, pb, m, 0, sl))) return rc;
-        continue;
-      }
-      const size_t step = which == 1 ? std::min<size_t>(ctx->max_batch, 32768) : ctx->max_batch;
-      for (size_t c0 = 0; c0 < m; c0 += step) {
-        const size_t cn = std::min(step, m - c0);
-        const size_t C = round_up(cn, 256);
-        const size_t ww = which == 1 ? gvk_keys_scratch_words((uint32_t)cn, GV_KN_ARENA_NG, GV_K6_NT, 1)
-                                     : gvk_keys_scratch_words((uint32_t)cn, GV_LGRP, GV_QTAB_N, 0);
-        const size_t Cs = std::max(C, round_up(ww / GV_QTAB_WORDS + 1, 256));
-        if ((rc = ensure_cap(s, Cs))) return rc;
-        if ((rc = set_acquire(s, st))) return rc;
-        CK(hipMemcpyAsync(s->d_in, pb + c0 * 33, cn * 33, hipMemcpyHostToDevice, st));
-        const uint32_t* d_slots = nullptr;
-        CK(stage_slots(s, C, sl + c0, cn, st, &d_slots));
-        if (which == 0) {
-          const size_t room = (size_t)GV_QTAB_WORDS * s->cap;
-          const int qe4 = ctx->keys_scratch && gvk_keys_scratch_words((uint32_t)cn, GV_LGRP, GV_QTAB_N, 1) <= room;
-          CK(gvk_keys_build(s->d_in, (uint32_t)cn, (uint32_t)C, s->in_x, s->in_pfx, s->in_r, s->in_s, s->in_e, s->qtab,
-                            qe4, 0u, d_slots, d->kqt, d->kzq, (uint32_t)d->kcap, d->kok, d->kqt2, d->kzq2, st));
-        } else {
-          CK(gvk_keys_build6(s->d_in, (uint32_t)cn, (uint32_t)C, s->in_x, s->in_pfx, s->in_r, s->in_s, s->in_e, s->qtab,
-                             ctx->keys_scratch ? 1 : 0, 0u, d_slots, d->kqt6, d->kzq6, (uint32_t)d->kcap, d->kok,
-                             d->kqt62, d->kzq62, st));
-        }
-        if ((rc = set_release(s, st))) return rc;
-        CK(hipStreamSynchronize(st));            // the caller's chunk is read by then
-      }
+      rc = which == 2 ? build_wide(ctx, d, s, st, pb, m, 0, sl)
+                      : build_k4k6(ctx, d, s, st, pb, m, 0, sl, which == 0, which == 1);
+      if (rc) return rc;
     }
   }
   ctx->keys_replaced.fetch_add(n);
@@ -2669,6 +2660,26 @@ int ensure_ed_keys(Dev* d, size_t need, size_t used, hipStream_t st, size_t cap_
   d->ektab = t; d->ekpub = p; d->ekok = o; d->ekcap = cap;
   return GV_OK;
 }
+
+// The tables of the n keys pub32 (host) into slots base.. of d's arena, or
+// into slots[i] (host, n entries; null: append) -- nothing else in the arena
+// moves.  Scratch: the keys, the slot list when there is one, then the window
+// bases of the split build.
+int ed_build(gv_ctx* ctx, Dev* d, hipStream_t st, const uint8_t* pub32, size_t n, size_t base, const uint32_t* slots) {
+  uint8_t* dp = nullptr;
+  const size_t o_sl = round_up(n * 32, 256), o_wb = o_sl + (slots ? round_up(n * 4, 256) : 0);
+  const size_t wb_bytes = n * 64 * 36 * 4;
+  const bool split = ctx->ed_keys_split && wb_bytes <= ((size_t)1 << 30);
+  if (hipMalloc(&dp, o_wb + (split ? wb_bytes : 0)) != hipSuccess) return GV_ENOMEM;
+  const bool ok = hipMemcpyAsync(dp, pub32, n * 32, hipMemcpyHostToDevice, st) == hipSuccess &&
+                  (!slots || hipMemcpyAsync(dp + o_sl, slots, n * 4, hipMemcpyHostToDevice, st) == hipSuccess) &&
+                  gvk_ed_keys(dp, (uint32_t)n, slots ? 0u : (uint32_t)base, slots ? (const uint32_t*)(dp + o_sl) : nullptr,
+                              d->ektab, d->ekpub, d->ekok, split ? (uint32_t*)(dp + o_wb) : nullptr, 4,
+                              st) == hipSuccess &&
+                  hipStreamSynchronize(st) == hipSuccess;
+  (void)hipFree(dp);
+  return ok ? GV_OK : GV_EHIP;
+}
 }  // namespace
 
 int gv_ed_keys_load(gv_ctx* ctx, size_t n, const uint8_t* pub32, uint32_t* slot_out) {
@@ -2683,19 +2694,8 @@ int gv_ed_keys_load(gv_ctx* ctx, size_t n, const uint8_t* pub32, uint32_t* slot_
     CK(hipSetDevice(d->id));
     hipStream_t st = d->set[0].st;
     int rc = ensure_ed_keys(d, base + n, base, st, ctx->ed_key_cap);
+    if (!rc) rc = ed_build(ctx, d, st, pub32, n, base, nullptr);
     if (rc) return rc;
-    uint8_t* dp = nullptr;
-    const size_t o_wb = round_up(n * 32, 256), wb_bytes = n * 64 * 36 * 4;
-    const bool split = ctx->ed_keys_split && wb_bytes <= ((size_t)1 << 30);
-    if (hipMalloc(&dp, o_wb + (split ? wb_bytes : 0)) != hipSuccess) return GV_ENOMEM;
-    if (hipMemcpyAsync(dp, pub32, n * 32, hipMemcpyHostToDevice, st) != hipSuccess ||
-        gvk_ed_keys(dp, (uint32_t)n, (uint32_t)base, nullptr, d->ektab, d->ekpub, d->ekok,
-                    split ? (uint32_t*)(dp + o_wb) : nullptr, 4, st) != hipSuccess ||
-        hipStreamSynchronize(st) != hipSuccess) {
-      (void)hipFree(dp);
-      return GV_EHIP;
-    }
-    (void)hipFree(dp);
   }
   ctx->ed_kpub.insert(ctx->ed_kpub.end(), pub32, pub32 + n * 32);
   ctx->ed_keys = base + n;
@@ -2709,37 +2709,15 @@ int gv_ed_keys_replace(gv_ctx* ctx, size_t n, const uint32_t* slots, const uint8
   if (!slots || !pub32) return GV_EINVAL;
   // keyed verifies hold ed_keys_mu for the whole call: none runs under a replacement
   std::lock_guard<std::mutex> kl(ctx->ed_keys_mu);
-  // every check before the first device write: each slot loaded, none twice
-  // (two lanes would write one row)
+  // every check before the first device write
   const size_t count = ctx->ed_keys;
-  if (n > count) return GV_EINVAL;
-  {
-    std::vector<uint64_t> seen((count + 63) / 64, 0);
-    for (size_t i = 0; i < n; ++i) {
-      const size_t sl = slots[i];
-      if (sl >= count || (seen[sl >> 6] >> (sl & 63) & 1)) return GV_EINVAL;
-      seen[sl >> 6] |= (uint64_t)1 << (sl & 63);
-    }
-  }
+  if (!check_slots(count, n, slots)) return GV_EINVAL;
   for (Dev* d : ctx->devs) {                    // every device holds every key
     std::lock_guard<std::mutex> lk(d->mu);
     CK(hipSetDevice(d->id));
-    hipStream_t st = d->set[0].st;
     if (count > d->ekcap) return GV_EINVAL;     // (never: the arena holds its slots)
-    // the scratch of gv_ed_keys_load (keys, then the window bases) and the slot list; nothing in the arena moves
-    uint8_t* dp = nullptr;
-    const size_t o_sl = round_up(n * 32, 256), o_wb = o_sl + round_up(n * 4, 256), wb_bytes = n * 64 * 36 * 4;
-    const bool split = ctx->ed_keys_split && wb_bytes <= ((size_t)1 << 30);
-    if (hipMalloc(&dp, o_wb + (split ? wb_bytes : 0)) != hipSuccess) return GV_ENOMEM;
-    if (hipMemcpyAsync(dp, pub32, n * 32, hipMemcpyHostToDevice, st) != hipSuccess ||
-        hipMemcpyAsync(dp + o_sl, slots, n * 4, hipMemcpyHostToDevice, st) != hipSuccess ||
-        gvk_ed_keys(dp, (uint32_t)n, 0u, (const uint32_t*)(dp + o_sl), d->ektab, d->ekpub, d->ekok,
-                    split ? (uint32_t*)(dp + o_wb) : nullptr, 4, st) != hipSuccess ||
-        hipStreamSynchronize(st) != hipSuccess) {
-      (void)hipFree(dp);
-      return GV_EHIP;
-    }
-    (void)hipFree(dp);
+    const int rc = ed_build(ctx, d, d->set[0].st, pub32, n, 0, slots);
+    if (rc) return rc;
   }
   // the host copy (large batches with ed_keyed 0 read it) only after every device has succeeded
   for (size_t i = 0; i < n; ++i) memcpy(&ctx->ed_kpub[(size_t)slots[i] * 32], pub32 + i * 32, 32);

@@ -1278,11 +1278,11 @@ class FlatSlotMap {
 };
 
 // Second-chance clock over the slots of a key arena kept at a resident size
-// (the ed25519 arena, gvh_set_ed_key_resident; verify_secp keeps the same
-// state in gvh_app's slot_* members).  Per slot: the K-byte key it holds (the
-// map's reverse), a reference bit set by every batch that names the slot, and
-// the stamp of the last such batch -- a slot named by the batch in hand is
-// never a victim.  The hand persists across batches.  Not thread-safe.
+// (gvh_set_key_resident, gvh_set_ed_key_resident).  Per slot: the K-byte key
+// it holds (the map's reverse), a reference bit set by every batch that names
+// the slot, and the stamp of the last such batch -- a slot named by the batch
+// in hand is never a victim.  The hand persists across batches.  Not
+// thread-safe.
 template <size_t K>
 struct SlotClock {
   std::vector<std::array<uint8_t, K>> key;
@@ -1350,6 +1350,107 @@ struct SlotClock {
   std::vector<uint32_t> taken_, cleared_;
   size_t hand0_ = 0;
 };
+
+// The host's view of one key arena of the GPU context (K-byte keys): key ->
+// slot, and with a resident size (0: eviction off) the clock over the slots.
+template <size_t K>
+struct KeyArena {
+  FlatSlotMap<K> map;
+  SlotClock<K> clock;
+  size_t resident = 0;
+  uint64_t gen = 0;                            // the arena generation the map belongs to
+  uint64_t stamp = 0;                          // of the last batch that touched the clock
+  uint64_t replaced = 0, resets = 0;           // gvh_get_key_stats / gvh_get_ed_key_stats
+  void clear() {
+    map.clear();
+    clock.clear();
+  }
+  void follow(uint64_t g) {                    // the arena was reset (here or by another user)
+    if (g == gen) return;
+    clear();
+    gen = g;
+  }
+};
+// The library's calls over one arena; replace is null when the library lacks it.
+struct ArenaLib {
+  size_t (*count)(const gv_ctx*);
+  int (*load)(gv_ctx*, size_t, const uint8_t*, uint32_t*);
+  int (*replace)(gv_ctx*, size_t, const uint32_t*, const uint8_t*);
+  int (*reset)(gv_ctx*);
+  uint64_t (*generation)(const gv_ctx*);
+};
+const ArenaLib kSecpLib{gv_keys_count, gv_keys_load, gv_keys_replace, gv_keys_reset, gv_keys_generation};
+const ArenaLib kEdLib{gv_ed_keys_count, gv_ed_keys_load, gv_ed_keys_replace, gv_ed_keys_reset, gv_ed_keys_generation};
+
+constexpr uint32_t kPending = 0x80000000u;     // + i: map value of fresh key i, queued for this call's load
+enum class Admit { kDone, kUnchanged, kResetAtCap, kResetAfterReplace };
+
+// A batch's fresh keys (in the map as kPending + i) into the arena: the free
+// slots below the resident size take the first nl with one load, the other nv
+// replace the clock's victims with one replace (evict off: all are loaded).
+// kDone: map and clock hold them, and the batch's pending slots[0..m) are
+// resolved.  kUnchanged (too few evictable slots, or the load failed): the
+// pending entries are gone and nothing else moved.  Reset (cap reached, or a
+// failed replacement, after which no slot it named is trusted): the arena and
+// its bookkeeping start over.  In each case but kDone the caller's batch goes
+// unkeyed.
+template <size_t K>
+Admit admit_keys(KeyArena<K>& a, gv_ctx* gpu, const ArenaLib& lib, size_t cap, bool evict, uint64_t stamp,
+                 const std::vector<std::array<uint8_t, K>>& fresh, uint32_t* slots, size_t m, size_t* replaced) {
+  static_assert(sizeof(std::array<uint8_t, K>) == K, "the fresh keys are handed over as one byte string");
+  const uint8_t* bytes = fresh[0].data();
+  const size_t nf = fresh.size();
+  std::vector<uint32_t> got(nf);
+  const size_t count = lib.count(gpu);
+  const size_t free_slots = !evict ? nf : count < a.resident ? a.resident - count : 0;
+  const size_t nl = std::min(nf, free_slots), nv = nf - nl;
+  auto drop_pending = [&] {
+    for (auto& key : fresh) a.map.erase(key.data());
+  };
+  auto start_over = [&] {
+    lib.reset(gpu);
+    a.clear();
+    a.gen = lib.generation(gpu);
+  };
+  std::vector<uint32_t> victims;
+  if (nv && !a.clock.sweep(count, nv, stamp, victims)) {
+    drop_pending();
+    return Admit::kUnchanged;
+  }
+#ifdef GVH_EVICT_AUDIT
+  for (size_t k = 0; k < m; ++k)                 // no slot the batch names is a victim
+    for (uint32_t v : victims)
+      if (slots[k] == v) abort();
+#endif
+  if (count + nl > cap) {
+    start_over();
+    return Admit::kResetAtCap;
+  }
+  if (nl && lib.load(gpu, nl, bytes, got.data()) != GV_OK) {
+    if (nv) a.clock.undo();
+    drop_pending();
+    return Admit::kUnchanged;
+  }
+  if (nv && lib.replace(gpu, nv, victims.data(), bytes + K * nl) != GV_OK) {
+    start_over();
+    return Admit::kResetAfterReplace;
+  }
+  auto put = [&](uint32_t slot, const uint8_t* key) {   // map and, under eviction, the reverse array together
+    a.map.set(key, slot);
+    if (evict) a.clock.holds(slot, key, stamp);
+  };
+  for (size_t i = 0; i < nl; ++i) put(got[i], fresh[i].data());
+  for (size_t i = 0; i < nv; ++i) {               // erase the victim's key, set the fresh key
+    a.map.erase(a.clock.key[victims[i]].data());
+    got[nl + i] = victims[i];
+    put(victims[i], fresh[nl + i].data());
+  }
+  a.replaced += nv;
+  for (size_t k = 0; k < m; ++k)
+    if (slots[k] >= kPending) slots[k] = got[slots[k] - kPending];
+  if (replaced) *replaced = nv;
+  return Admit::kDone;
+}
 
 // A decoded amino pubkey with its canonical bytes (pk.Bytes()), address and
 // CountSubKeys -- pure functions of the amino bytes, shared by every tx and
@@ -1585,13 +1686,18 @@ struct gvh_app {
   Window window;
   std::mutex gpu_mu;                           // one GPU batch at a time per app
   // account key cache: pub33 -> key-arena slot of the GPU
-  // context (gv_keys_load); guarded by gpu_mu.  keyed = 0: pub33 batches.
-  FlatSlotMap<33> key_slots;
+  // context (gv_keys_load).  keyed = 0: pub33 batches.  Under key_mu.
+  // Eviction (gvh_set_key_resident; 0 = off): the arena is never loaded past
+  // `resident` slots -- a block's fresh keys beyond the free slots replace
+  // victims of the clock (gv_keys_replace).  epoch moves with every
+  // replacement: a batch packed before it looks its slots up again.
+  struct SecpArena : KeyArena<33> {
+    uint64_t epoch = 0;
+  } secp;
   // ed25519 keys (IBC validator sets, multisig ed25519 sub-keys): pub32 ->
-  // slot of the context's ed25519 key arena (gv_ed_keys_load); gpu_mu
-  FlatSlotMap<32> ed_slots;
-  uint64_t ed_key_gen = 0;
-  uint64_t key_gen = 0;                        // gv_keys_generation the map belongs to
+  // slot of the context's ed25519 key arena (gv_ed_keys_load), kept at a
+  // resident size the same way (gvh_set_ed_key_resident); under gpu_mu
+  KeyArena<32> ed;
   bool keyed = true;
   // PreVerifyTxs of a delivered block (keep == false) with an empty verdict
   // cache: secp256k1 sign bytes hashed by the GPU batch (gv_verify_msgs*)
@@ -1602,31 +1708,6 @@ struct gvh_app {
   size_t key_cap = GV_KEY_CAP;                 // arena reset past this many keys (5.4 KB of HBM each)
   size_t key_load_min = GV_KEY_LOAD_MIN;       // smaller batches never load keys (k_keys_build's ~ms latency):
                                                // keyed only when all their keys are resident
-  // Eviction (gvh_set_key_resident; 0 = off): the arena is never loaded past
-  // key_resident slots -- a block's fresh keys beyond the free slots replace
-  // victims of a second-chance clock (gv_keys_replace).  Per slot: the key it
-  // holds (the map's reverse), a reference bit set by every batch that names
-  // the slot, and the stamp of the last such batch (a slot named by the batch
-  // in hand is never a victim).  key_epoch moves with every replacement: a
-  // batch packed before it looks its slots up again.  All under key_mu.
-  size_t key_resident = 0;
-  std::vector<std::array<uint8_t, 33>> slot_key;
-  std::vector<uint8_t> slot_ref;
-  std::vector<uint64_t> slot_stamp;
-  size_t clock_hand = 0;
-  uint64_t batch_stamp = 0, key_epoch = 0;
-  uint64_t keys_replaced = 0, key_resets = 0;
-  void clock_clear() {
-    slot_key.clear();
-    slot_ref.clear();
-    slot_stamp.clear();
-    clock_hand = 0;
-  }
-  // the same for the ed25519 arena (gvh_set_ed_key_resident, gv_ed_keys_replace); under gpu_mu
-  size_t ed_key_resident = 0;
-  SlotClock<32> ed_clock;
-  uint64_t ed_batch_stamp = 0;
-  uint64_t ed_keys_replaced = 0, ed_key_resets = 0;
   int threads = std::max(1, std::min(16, (int)std::thread::hardware_concurrency()));
   std::unique_ptr<Pool> pool{new Pool(threads - 1)};
   std::mutex pool_mu;                          // guards replacing the pool (gvh_set_threads)
@@ -1641,7 +1722,7 @@ struct gvh_app {
   std::array<ObjPool, 64> objs;
   uint64_t bump_epoch = 0;
   uint64_t carry_epoch = 0;                    // a pre-verified block not yet delivered (deliver_blocks), 0: none
-  // key_slots readers (slot lookups on the pool, before the GPU lock) share
+  // secp.map readers (slot lookups on the pool, before the GPU lock) share
   // key_mu; verify_secp's updates take it exclusively (under gpu_mu)
   std::shared_mutex key_mu;
   // pinned pack buffers (gv_host_alloc): the GPU batch reads them in place, no staging copy
@@ -2056,11 +2137,11 @@ void batch_pack(gvh_app* app, GpuBatch& b) {
     b.slots = (uint32_t*)(b.buf.p + slot_off);
     b.ok = b.buf.p + slot_off + m * 4;
     std::shared_lock<std::shared_mutex> rk(app->key_mu);
-    const bool look = app->keyed && app->gpu && gv_keys_generation(app->gpu) == app->key_gen;
-    b.gen = app->key_gen;
-    b.epoch = app->key_epoch;
+    const bool look = app->keyed && app->gpu && gv_keys_generation(app->gpu) == app->secp.gen;
+    b.gen = app->secp.gen;
+    b.epoch = app->secp.epoch;
     b.looked_up = look;
-    auto& map = app->key_slots;
+    auto& map = app->secp.map;
     parallel_for(app, m, [&](size_t k) {
       Leaf& L = *b.miss[k];
       memcpy(&b.pub[k * 33], L.pub.data(), 33);
@@ -2102,8 +2183,8 @@ void batch_pack(gvh_app* app, GpuBatch& b) {
 // (a key ParsePubKey rejects keeps a false slot), without the per-item
 // decompression and Q-table build, on the 4-group ladder.  Any arena problem
 // (cap reached, load error) falls back to the pub33 batch for this call.
-// With a resident size (gvh_set_key_resident) the arena stops growing there:
-// a block's fresh keys take the free slots, the rest replace the clock's
+// With a resident size (gvh_set_key_resident) the arena stops growing there
+// (admit_keys): a block's fresh keys take the free slots, the rest replace the clock's
 // victims with one gv_keys_replace; when the sweep finds too few victims the
 // batch takes the pub33 path and nothing changes.
 // ticket: queue the batch (gv_submit_*) instead of verifying it; the caller
@@ -2120,139 +2201,40 @@ int verify_secp(gvh_app* app, GpuBatch& b, uint64_t* ticket = nullptr) {
                   : gv_verify_digests(app->gpu, m, b.pub, b.sig, b.dig, b.ok);
   };
   if (!app->keyed) return plain();
-  constexpr uint32_t kPending = 0x80000000u;      // map value of a key queued for this call's load
   std::unique_lock<std::shared_mutex> wk(app->key_mu);
-  auto& map = app->key_slots;
+  auto& a = app->secp;
+  auto& map = a.map;
   const uint64_t gen = gv_keys_generation(app->gpu);
-  if (gen != app->key_gen) {                      // the arena was reset (here or by another user)
-    map.clear();
-    app->clock_clear();
-    app->key_gen = gen;
-  }
-  if (!b.looked_up || b.gen != gen || b.epoch != app->key_epoch)   // packed against another arena, or slots
+  a.follow(gen);
+  if (!b.looked_up || b.gen != gen || b.epoch != a.epoch)          // packed against another arena, or slots
     for (size_t k = 0; k < m; ++k) {                                // have changed hands since: look up again
       const uint32_t* v = map.find(b.pub + 33 * k);
       b.slots[k] = v ? *v : UINT32_MAX;
     }
-  const bool evict = app->key_resident > 0 && gv_keys_replace != nullptr;
-  uint64_t stamp = 0;
-  auto touch = [&](uint32_t slot) {               // this batch names the slot
-    if (slot >= app->slot_ref.size()) return;
-    app->slot_ref[slot] = 1;
-    app->slot_stamp[slot] = stamp;
-  };
-  auto holds = [&](uint32_t slot, const uint8_t* key) {   // the slot now holds key (map and reverse array together)
-    if (slot >= app->slot_key.size()) {
-      app->slot_key.resize(slot + 1, {});
-      app->slot_ref.resize(slot + 1, 0);
-      app->slot_stamp.resize(slot + 1, 0);
-    }
-    memcpy(app->slot_key[slot].data(), key, 33);
-    map.set(key, slot);
-    touch(slot);
-  };
-  if (evict) {
-    stamp = ++app->batch_stamp;
-    for (size_t k = 0; k < m; ++k)
-      if (b.slots[k] != UINT32_MAX) touch(b.slots[k]);
-  }
+  const bool evict = a.resident > 0 && gv_keys_replace != nullptr;
+  const uint64_t stamp = evict ? ++a.stamp : 0;
+  if (evict)
+    for (size_t k = 0; k < m; ++k) a.clock.touch(b.slots[k], stamp);   // this batch names the slot (UINT32_MAX: none)
   if (m < app->key_load_min) {                    // small batch (CheckTx window, per-tx ante)
     bool all = true;
     for (size_t k = 0; k < m && all; ++k) all = b.slots[k] != UINT32_MAX;
     if (!all) return plain();
   }
-  std::vector<uint8_t> fresh;
-  std::vector<std::array<uint8_t, 33>> fresh_keys;
+  std::vector<std::array<uint8_t, 33>> fresh;
   for (size_t k = 0; k < m; ++k) {
     if (b.slots[k] != UINT32_MAX) continue;
     std::array<uint8_t, 33> key;
     memcpy(key.data(), b.pub + 33 * k, 33);
-    auto ins = map.emplace(key.data(), kPending + (uint32_t)fresh_keys.size());
-    if (ins.second) {
-      fresh.insert(fresh.end(), key.begin(), key.end());
-      fresh_keys.push_back(key);
-    }
+    auto ins = map.emplace(key.data(), kPending + (uint32_t)fresh.size());
+    if (ins.second) fresh.push_back(key);
     b.slots[k] = *ins.first;
   }
-  if (!fresh_keys.empty()) {
-    const size_t nf = fresh_keys.size();
-    std::vector<uint32_t> got(nf);
-    const size_t count = gv_keys_count(app->gpu);
-    const size_t free_slots = !evict ? nf : count < app->key_resident ? app->key_resident - count : 0;
-    const size_t nl = std::min(nf, free_slots), nv = nf - nl;   // loaded into free slots / put into victims' slots
-    auto drop_pending = [&] {
-      for (auto& key : fresh_keys) map.erase(key.data());
-    };
-    std::vector<uint32_t> victims, cleared;
-    if (nv) {
-      // second-chance sweep from the persistent hand over the loaded slots:
-      // two turns at most (the first clears reference bits, the second takes)
-      const size_t span = std::min(count, app->slot_key.size());
-      const size_t hand0 = app->clock_hand;
-      size_t h = span ? hand0 % span : 0;
-      for (size_t step = 0; step < 2 * span && victims.size() < nv; ++step, h = (h + 1) % span) {
-        if (app->slot_stamp[h] == stamp) continue;   // named by the batch in hand
-        if (app->slot_ref[h]) {
-          app->slot_ref[h] = 0;
-          cleared.push_back((uint32_t)h);
-        } else {
-          victims.push_back((uint32_t)h);
-          app->slot_stamp[h] = stamp;                // (taken: not twice in one sweep)
-        }
-      }
-      if (victims.size() < nv) {                     // too few evictable slots: nothing changes
-        for (uint32_t v : victims) app->slot_stamp[v] = 0;
-        for (uint32_t c : cleared) app->slot_ref[c] = 1;
-        app->clock_hand = hand0;
-        drop_pending();
-        return plain();
-      }
-      app->clock_hand = h;
-#ifdef GVH_EVICT_AUDIT
-      for (size_t k = 0; k < m; ++k)                 // no slot the batch names is a victim
-        for (uint32_t v : victims)
-          if (b.slots[k] == v) abort();
-#endif
-    }
-    const bool room = count + nl <= app->key_cap;
-    if (!room || (nl && gv_keys_load(app->gpu, nl, fresh.data(), got.data()) != GV_OK)) {
-      if (!room) {                                  // start the arena over; this call takes the pub33 path
-        gv_keys_reset(app->gpu);
-        map.clear();
-        app->clock_clear();
-        app->key_resets++;
-        app->key_gen = gv_keys_generation(app->gpu);
-      } else {
-        for (uint32_t v : victims) app->slot_stamp[v] = 0;
-        for (uint32_t c : cleared) app->slot_ref[c] = 1;
-        drop_pending();
-      }
-      return plain();
-    }
-    if (nv && gv_keys_replace(app->gpu, nv, victims.data(), fresh.data() + 33 * nl) != GV_OK) {
-      gv_keys_reset(app->gpu);                      // no slot named in a failed replacement is trusted
-      map.clear();
-      app->clock_clear();
-      app->key_resets++;
-      app->key_gen = gv_keys_generation(app->gpu);
-      return plain();
-    }
-    if (evict) {
-      for (size_t i = 0; i < nl; ++i) holds(got[i], fresh_keys[i].data());
-      for (size_t i = 0; i < nv; ++i) {             // erase the victim's key, set the fresh key
-        map.erase(app->slot_key[victims[i]].data());
-        got[nl + i] = victims[i];
-        holds(victims[i], fresh_keys[nl + i].data());
-      }
-      if (nv) {
-        app->key_epoch++;
-        app->keys_replaced += nv;
-      }
-    } else {
-      for (size_t i = 0; i < nf; ++i) map.set(fresh_keys[i].data(), got[i]);
-    }
-    for (size_t k = 0; k < m; ++k)
-      if (b.slots[k] >= kPending) b.slots[k] = got[b.slots[k] - kPending];
+  if (!fresh.empty()) {
+    size_t nv = 0;
+    const Admit r = admit_keys(a, app->gpu, kSecpLib, app->key_cap, evict, stamp, fresh, b.slots, m, &nv);
+    if (r == Admit::kResetAtCap || r == Admit::kResetAfterReplace) a.resets++;
+    if (r != Admit::kDone) return plain();
+    if (nv) a.epoch++;
   }
   if (ticket)
     return b.msgs ? gv_submit_msgs_keyed(app->gpu, m, b.slots, b.sig, b.blob, b.moff, b.mlen, b.ok, ticket)
@@ -2275,97 +2257,53 @@ int verify_ed(gvh_app* app, size_t m, const uint8_t* pub, const uint8_t* sig, co
               const uint32_t* len, uint8_t* ok, bool load) {
   if (!app->keyed) return gv_verify_ed25519_msgs(app->gpu, m, pub, sig, blob, off, len, ok);
   auto plain = [&] { return gv_verify_ed25519_msgs(app->gpu, m, pub, sig, blob, off, len, ok); };
-  auto& map = app->ed_slots;
-  auto& clk = app->ed_clock;
-  const uint64_t gen = gv_ed_keys_generation(app->gpu);
-  if (gen != app->ed_key_gen) {                   // the arena was reset (here or by another user)
-    map.clear();
-    clk.clear();
-    app->ed_key_gen = gen;
-  }
-  const bool evict = app->ed_key_resident > 0 && gv_ed_keys_replace != nullptr;
-  const uint64_t stamp = evict ? ++app->ed_batch_stamp : 0;
+  auto& a = app->ed;
+  auto& map = a.map;
+  a.follow(gv_ed_keys_generation(app->gpu));
+  const bool evict = a.resident > 0 && gv_ed_keys_replace != nullptr;
+  const uint64_t stamp = evict ? ++a.stamp : 0;
   std::vector<uint32_t> slots(m);
-  std::vector<uint8_t> fresh;
-  std::vector<std::array<uint8_t, 32>> fresh_keys;
-  constexpr uint32_t kPending = 0x80000000u;
+  std::vector<std::array<uint8_t, 32>> fresh;
   for (size_t k = 0; k < m; ++k) {
     std::array<uint8_t, 32> key;
     memcpy(key.data(), pub + 32 * k, 32);
     if (const uint32_t* v = map.find(key.data())) {
       slots[k] = *v;
-      if (evict && *v < kPending) clk.touch(*v, stamp);   // this batch names the slot
+      if (evict) a.clock.touch(*v, stamp);          // this batch names the slot (a pending value: none)
       continue;
     }
     if (!load) return plain();
-    auto ins = map.emplace(key.data(), kPending + (uint32_t)fresh_keys.size());
-    if (ins.second) {
-      fresh.insert(fresh.end(), key.begin(), key.end());
-      fresh_keys.push_back(key);
-    }
+    auto ins = map.emplace(key.data(), kPending + (uint32_t)fresh.size());
+    if (ins.second) fresh.push_back(key);
     slots[k] = *ins.first;
   }
-  if (!fresh_keys.empty()) {
-    const size_t nf = fresh_keys.size();
-    std::vector<uint32_t> got(nf);
-    const size_t count = gv_ed_keys_count(app->gpu);
-    // resident size: the fresh keys take the free slots up to it, the rest
-    // replace the clock's victims; 0: every fresh key is loaded
-    const size_t free_slots = !evict ? nf : count < app->ed_key_resident ? app->ed_key_resident - count : 0;
-    const size_t nl = std::min(nf, free_slots), nv = nf - nl;
-    auto drop_pending = [&] {
-      for (auto& key : fresh_keys) map.erase(key.data());
-    };
-    auto start_over = [&] {
-      gv_ed_keys_reset(app->gpu);
-      map.clear();
-      clk.clear();
-      app->ed_key_gen = gv_ed_keys_generation(app->gpu);
-    };
-    std::vector<uint32_t> victims;
-    if (nv && !clk.sweep(count, nv, stamp, victims)) {   // too few evictable slots: nothing changes
-      drop_pending();
-      return plain();
-    }
-#ifdef GVH_EVICT_AUDIT
-    for (size_t k = 0; k < m; ++k)                 // no slot the batch names is a victim
-      for (uint32_t v : victims)
-        if (slots[k] == v) abort();
-#endif
-    const bool room = count + nl <= GV_ED_KEY_CAP;
-    if (!room || (nl && gv_ed_keys_load(app->gpu, nl, fresh.data(), got.data()) != GV_OK)) {
-      if (!room) {
-        start_over();
-      } else {
-        clk.undo();
-        drop_pending();
-      }
-      return plain();
-    }
-    if (nv && gv_ed_keys_replace(app->gpu, nv, victims.data(), fresh.data() + 32 * nl) != GV_OK) {
-      start_over();                                // no slot named in a failed replacement is trusted
-      app->ed_key_resets++;
-      return plain();
-    }
-    if (evict) {
-      for (size_t i = 0; i < nl; ++i) {
-        map.set(fresh_keys[i].data(), got[i]);
-        clk.holds(got[i], fresh_keys[i].data(), stamp);
-      }
-      for (size_t i = 0; i < nv; ++i) {             // erase the victim's key, set the fresh key
-        map.erase(clk.key[victims[i]].data());
-        got[nl + i] = victims[i];
-        map.set(fresh_keys[nl + i].data(), victims[i]);
-        clk.holds(victims[i], fresh_keys[nl + i].data(), stamp);
-      }
-      app->ed_keys_replaced += nv;
-    } else {
-      for (size_t i = 0; i < nf; ++i) map.set(fresh_keys[i].data(), got[i]);
-    }
-    for (size_t k = 0; k < m; ++k)
-      if (slots[k] >= kPending) slots[k] = got[slots[k] - kPending];
+  if (!fresh.empty()) {
+    const Admit r = admit_keys(a, app->gpu, kEdLib, GV_ED_KEY_CAP, evict, stamp, fresh, slots.data(), m, nullptr);
+    if (r == Admit::kResetAfterReplace) a.resets++;   // (alone: gvh_get_ed_key_stats)
+    if (r != Admit::kDone) return plain();
   }
   return gv_verify_ed25519_msgs_keyed(app->gpu, m, slots.data(), sig, blob, off, len, ok);
+}
+
+// gvh_set_key_resident / gvh_set_ed_key_resident and the stats getters, under the arena's locks
+template <size_t K>
+void set_resident(gvh_app* app, KeyArena<K>& a, const ArenaLib& lib, size_t resident) {
+  if (!lib.replace) resident = 0;                 // a library without the replace call: eviction stays off
+  if (resident == a.resident) return;
+  // the clock starts from an empty arena: slots loaded before carry no reverse entry
+  if (resident && app->gpu && app->keyed && lib.count(app->gpu)) {
+    lib.reset(app->gpu);
+    a.map.clear();
+    a.gen = lib.generation(app->gpu);
+  }
+  a.clock.clear();
+  a.resident = resident;
+}
+template <size_t K>
+void get_stats(const KeyArena<K>& a, size_t* resident, uint64_t* replaced, uint64_t* resets) {
+  if (resident) *resident = a.resident;
+  if (replaced) *replaced = a.replaced;
+  if (resets) *resets = a.resets;
 }
 
 int batch_run(gvh_app* app, GpuBatch& b) {
@@ -3422,44 +3360,20 @@ void gvh_set_keyed(gvh_app* app, int keyed, size_t load_min) {
 void gvh_set_key_resident(gvh_app* app, size_t resident) {
   std::lock_guard<std::mutex> g(app->gpu_mu);
   std::unique_lock<std::shared_mutex> wk(app->key_mu);
-  if (!gv_keys_replace) resident = 0;             // a library without gv_keys_replace: eviction stays off
-  if (resident == app->key_resident) return;
-  // the clock starts from an empty arena: slots loaded before carry no reverse entry
-  if (resident && app->gpu && app->keyed && gv_keys_count(app->gpu)) {
-    gv_keys_reset(app->gpu);
-    app->key_slots.clear();
-    app->key_gen = gv_keys_generation(app->gpu);
-  }
-  app->clock_clear();
-  app->key_resident = resident;
+  set_resident(app, app->secp, kSecpLib, resident);
 }
 void gvh_get_key_stats(gvh_app* app, size_t* resident, uint64_t* replaced, uint64_t* resets) {
   std::lock_guard<std::mutex> g(app->gpu_mu);
   std::shared_lock<std::shared_mutex> rk(app->key_mu);
-  if (resident) *resident = app->key_resident;
-  if (replaced) *replaced = app->keys_replaced;
-  if (resets) *resets = app->key_resets;
+  get_stats(app->secp, resident, replaced, resets);
 }
-
 void gvh_set_ed_key_resident(gvh_app* app, size_t resident) {
   std::lock_guard<std::mutex> g(app->gpu_mu);
-  if (!gv_ed_keys_replace) resident = 0;          // a library without gv_ed_keys_replace: eviction stays off
-  resident = std::min<size_t>(resident, GV_ED_KEY_CAP);
-  if (resident == app->ed_key_resident) return;
-  // the clock starts from an empty arena: slots loaded before carry no reverse entry
-  if (resident && app->gpu && app->keyed && gv_ed_keys_count(app->gpu)) {
-    gv_ed_keys_reset(app->gpu);
-    app->ed_slots.clear();
-    app->ed_key_gen = gv_ed_keys_generation(app->gpu);
-  }
-  app->ed_clock.clear();
-  app->ed_key_resident = resident;
+  set_resident(app, app->ed, kEdLib, std::min<size_t>(resident, GV_ED_KEY_CAP));
 }
 void gvh_get_ed_key_stats(gvh_app* app, size_t* resident, uint64_t* replaced, uint64_t* resets) {
   std::lock_guard<std::mutex> g(app->gpu_mu);
-  if (resident) *resident = app->ed_key_resident;
-  if (replaced) *replaced = app->ed_keys_replaced;
-  if (resets) *resets = app->ed_key_resets;
+  get_stats(app->ed, resident, replaced, resets);
 }
 
 void gvh_set_gpu_hash(gvh_app* app, int on) {

@@ -1,7 +1,7 @@
 // evict_ed_harness.cpp -- the host mirror's clock eviction over the ed25519
 // key arena (gvh_set_ed_key_resident) under ASan + UBSan or TSan
 // (tests/test_ed_key_evict_host.py), over the CPU fake with
-// gv_ed_keys_replace (evict_ed_fake.cpp).  host/gvhost.cpp is compiled into
+// gv_ed_keys_replace (evict_fake.cpp).  host/gvhost.cpp is compiled into
 // this file so that the checks below can read the app's ed25519 key-slot
 // bookkeeping.
 //   1. SETS validator sets of VALS keys each (OpenSSL keys from fixed seeds)
@@ -11,8 +11,8 @@
 //      size of `resident`.  After every call: the arena never passes the
 //      resident size, every slot's stored key is the key the clock's reverse
 //      array names, the map sends that key to that slot and holds nothing else
-//      (GVH_EVICT_AUDIT: verify_ed aborts if a slot named by the batch in hand
-//      is among the victims).
+//      (GVH_EVICT_AUDIT: admit_keys aborts if a slot named by the batch in
+//      hand is among the victims).
 //   2. The same calls, serially, on an app with resident 0: every result must
 //      be equal, and the arena must have grown past the resident size.
 // Prints {"codes": [...], "replaced": n, "resets": n, "count": n} and exits 0,
@@ -87,15 +87,15 @@ const char* audit(gvh_app* app, gv_ctx* ctx, size_t resident) {
   std::lock_guard<std::mutex> g(app->gpu_mu);
   const size_t count = gv_ed_keys_count(ctx);
   if (count > resident) return "arena past the resident size";
-  const auto& clk = app->ed_clock;
+  const auto& clk = app->ed.clock;
   if (clk.key.size() != count) return "reverse array and arena differ in size";
   if (clk.ref.size() != count || clk.stamp.size() != count) return "clock arrays differ in size";
-  if (app->ed_slots.size() != count) return "map holds a key no slot holds";
+  if (app->ed.map.size() != count) return "map holds a key no slot holds";
   for (size_t s = 0; s < count; ++s) {
     uint8_t k[32];
     if (!gvfake_ed_key(ctx, (uint32_t)s, k)) return "slot not in the store";
     if (memcmp(k, clk.key[s].data(), 32)) return "reverse array names another key than the store holds";
-    const uint32_t* v = app->ed_slots.find(k);
+    const uint32_t* v = app->ed.map.find(k);
     if (!v || *v != s) return "map does not send a slot's key to that slot";
   }
   return nullptr;

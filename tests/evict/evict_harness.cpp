@@ -12,7 +12,7 @@
 //      bookkeeping checked after every block: every slot's stored key is the
 //      key the app's reverse array names, the map sends that key to that slot,
 //      the map holds nothing else, and the arena never passes R slots
-//      (GVH_EVICT_AUDIT: verify_secp aborts if a slot named by the batch in
+//      (GVH_EVICT_AUDIT: admit_keys aborts if a slot named by the batch in
 //      hand is among the victims);
 //   3. the same with resident = 0, and gvh_ante tx by tx.
 // All codes and final accounts must agree.  Prints {"blocks": [...],
@@ -83,14 +83,15 @@ static const char* audit(gvh_app* app, gv_ctx* ctx, size_t resident) {
   std::unique_lock<std::shared_mutex> wk(app->key_mu);
   const size_t count = gv_keys_count(ctx);
   if (count > resident) return "arena past the resident size";
-  if (app->slot_key.size() != count) return "reverse array and arena differ in size";
-  if (app->slot_ref.size() != count || app->slot_stamp.size() != count) return "clock arrays differ in size";
-  if (app->key_slots.size() != count) return "map holds a key no slot holds";
+  const auto& clk = app->secp.clock;
+  if (clk.key.size() != count) return "reverse array and arena differ in size";
+  if (clk.ref.size() != count || clk.stamp.size() != count) return "clock arrays differ in size";
+  if (app->secp.map.size() != count) return "map holds a key no slot holds";
   for (size_t s = 0; s < count; ++s) {
     uint8_t k[33];
     if (!gvfake_key(ctx, (uint32_t)s, k)) return "slot not in the store";
-    if (memcmp(k, app->slot_key[s].data(), 33)) return "reverse array names another key than the store holds";
-    const uint32_t* v = app->key_slots.find(k);
+    if (memcmp(k, clk.key[s].data(), 33)) return "reverse array names another key than the store holds";
+    const uint32_t* v = app->secp.map.find(k);
     if (!v || *v != s) return "map does not send a slot's key to that slot";
   }
   return nullptr;

@@ -1,5 +1,5 @@
 """The host mirror's clock eviction over the ed25519 key arena
-(gvh_set_ed_key_resident) on the CPU: tests/evict_ed/evict_ed_harness.cpp --
+(gvh_set_ed_key_resident) on the CPU: tests/evict/evict_ed_harness.cpp --
 host/gvhost.cpp over a CPU fake that also defines gv_ed_keys_replace -- built
 with ASan + UBSan and with TSan and run as a program.  Four threads drive
 gvh_verify_commits (keys_trusted) over 12 validator sets of 40 keys with a
@@ -12,7 +12,7 @@ import subprocess
 import pytest
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DIR = os.path.join(REPO, "tests", "evict_ed")
+DIR = os.path.join(REPO, "tests", "evict")
 RESIDENT = 128
 
 

@@ -260,6 +260,57 @@ def test_chunk_edges(ver):
             priv[777], pub[777] = new_priv[1100], new_pub[1100]
 
 
+@pytest.fixture(scope="module")
+def edge_load():
+    """1,300 keys, 3,001 items over their slots (30 % signed by a key that is
+    nowhere in the arena) with the oracle's verdicts, and keys_point of a
+    second Verifier that loaded the keys at the default max_batch."""
+    rng = np.random.default_rng(0xE6)
+    nk, n = 1300, 3001
+    priv = fresh_privs(rng, nk)
+    pub = O.pubkey_batch(priv, threads=8)
+    slots = (np.arange(n) % nk).astype(np.uint32)
+    signer = priv[slots].copy()
+    stale = rng.random(n) < 0.3
+    signer[stale] = fresh_privs(rng, int(stale.sum()))
+    sig, dig = sign_items(rng, signer)
+    item_pub = np.ascontiguousarray(pub[slots])
+    want = O.verify_digests(item_pub, sig, dig, threads=16)
+    assert 0.3 < want.mean() < 0.7
+    with gvm.Verifier([0]) as v:
+        assert v.get_option("max_batch") > nk                         # one chunk
+        v.keys_load(pub)
+        point = v.keys_point(np.arange(nk, dtype=np.uint32))
+    return pub, slots, sig, dig, item_pub, want, point
+
+
+def test_load_chunk_edges(ver, path, edge_load):
+    """max_batch 256 under one gv_keys_load of 1,300 keys: five full chunks and
+    a tail of 20 in the k4, k6 and wide loops.  The slots then hold what a load
+    in one chunk gives them, and serve every keyed schedule."""
+    pub, slots, sig, dig, item_pub, want, point = edge_load
+    keys_k6, keys_wide = KEYED_PATHS[path][2:4]
+    mb = ver.get_option("max_batch")
+    ver.keys_reset()
+    ver.set_option("keys_k6", 1)                                      # the load builds every table set
+    ver.set_option("keys_wide", 2)
+    ver.set_option("max_batch", 256)
+    try:
+        assert np.array_equal(ver.keys_load(pub), np.arange(len(pub)))
+    finally:
+        ver.set_option("max_batch", mb)
+        ver.set_option("keys_k6", keys_k6)
+        ver.set_option("keys_wide", keys_wide)
+    assert ver.get_option("kw_arena_qw") == 11                        # the wide loop ran too
+    xy, ok = ver.keys_point(np.arange(len(pub), dtype=np.uint32))
+    assert np.array_equal(ok, point[1])
+    assert xy.tobytes() == point[0].tobytes()
+    got = ver.verify_batch_digests_keyed(slots, sig, dig)
+    bad = np.nonzero(got != want)[0]
+    assert bad.size == 0, (bad[:10], slots[bad[:10]])
+    assert np.array_equal(got, ver.verify_batch_digests(item_pub, sig, dig))
+
+
 def test_validation_changes_nothing(ver, world):
     load_world(ver, world)
     L, ctx = ver._L, ver._ctx
