@@ -95,15 +95,19 @@ GV_DEV void ext_load(ge_ext& a, const u32* p) {
   for (int i = 0; i < 9; ++i) { a.X.n[i] = p[i]; a.Y.n[i] = p[9 + i]; a.Z.n[i] = p[18 + i]; a.T.n[i] = p[27 + i]; }
 }
 // RB: the comb's radix bits -- 4 (the key arena's tables, 64 windows of 8
-// entries, read by k_ed_lat_sl too) or 6 (the grouped route's per-batch
-// tables: 43 windows of 32 entries, 43 additions per [h](-A) instead of 64).
+// entries, read by k_ed_lat_sl too), 6 (the grouped route's per-batch tables
+// and the wide arena's: 43 windows of 32 entries, 43 additions per [h](-A)
+// instead of 64) or 8 (the wide arena's: 32 windows of 128 entries).
 template <int RB>
 struct EdComb {
-  static constexpr int NW = RB == 4 ? 64 : 43;              // windows over h < 2^253
+  static_assert(RB == 4 || RB == 6 || RB == 8, "comb radix bits");
+  static constexpr int NW = ed_comb_windows<RB>();          // windows over h < 2^253: 64 / 43 / 32
   static constexpr int NE = 1 << (RB - 1);                  // entries j = 1..NE per window
   static constexpr size_t WORDS = (size_t)NW * NE * ED_CACHED_WORDS;
 };
+static_assert(EdComb<4>::NW == 64 && EdComb<6>::NW == 43 && EdComb<8>::NW == 32, "comb windows");
 static_assert(EdComb<4>::WORDS == GV_EDK_WORDS && EdComb<6>::WORDS == GV_EDK64_WORDS, "comb table sizes");
+static_assert(EdComb<8>::WORDS == GV_EDK256_WORDS, "comb table sizes");
 
 template <int RB>
 __global__ __launch_bounds__(64) void k_ed_keys_chain(const uint8_t* pub32, uint32_t n, uint32_t base, const uint32_t* slots,
@@ -687,8 +691,9 @@ __global__ __launch_bounds__(256) void k_ed_lat_unc(const gvk_edl b) {
 
 // Large batches against cached keys (k_ed_keyed, one signature per lane):
 // the key's comb table of -A replaces FromBytes(A), the per-lane table and
-// the 252 doublings of the throughput ladder -- [h](-A) is 64 table adds, no
-// doubling --, then the 32 [s]B comb adds and the encode / compare of
+// the 252 doublings of the throughput ladder -- [h](-A) is 64 table adds (43 /
+// 32 on the radix-64 / radix-256 tables of the grouped route and the wide
+// arena), no doubling --, then the 32 [s]B comb adds and the encode / compare of
 // ed_ladder_check.  Lanes run in slot order (perm from gv_sort.hip's counting
 // sort): a validator set's commits name their keys in the same order every
 // block, so item order would put 64 different 73 KB tables under one wave.
@@ -727,11 +732,7 @@ __global__ __launch_bounds__(256) void k_ed_keyed(const gvk_edk b) {
   int cin = 0;
 #pragma unroll 1
   for (int w = 0; w < L::NW; ++w) {
-    const int pos = RB * w, wi = pos >> 5;
-    const uint64_t pair = (uint64_t)h[wi] | (wi < 7 ? (uint64_t)h[wi + 1] << 32 : 0ull);
-    int dg = (int)((pair >> (pos & 31)) & (uint64_t)((1u << RB) - 1u)) + cin;
-    cin = 0;
-    if (w < L::NW - 1 && dg >= L::NE) { dg -= 1 << RB; cin = 1; }   // h < 2^253: no carry out of the top window
+    const int dg = ed_comb_digit<RB>(h, w, cin);   // h < 2^253: no carry out of the top window
     if (dg != 0) {
       const int mag = dg < 0 ? -dg : dg;
       ge_add_tab<true>(acc, acc, kt + (size_t)(w * L::NE + mag - 1) * ED_CACHED_WORDS, 1, 0, dg < 0);
@@ -866,8 +867,53 @@ __global__ __launch_bounds__(256) void k_ed_keys_point(u32 n, const u32* slots, 
   out_ok[g] = ok ? 1u : 0u;
 }
 
+// The same for a slot's wide table (gv_ed_keys_wide_point): entry (w, j) =
+// j * 2^(RB w) * (-A) of the radix-2^RB comb, w < NW, 1 <= j <= NE.  kcount:
+// the slots that have wide tables; kok: the key arena's decode verdicts.
+template <int RB>
+__global__ __launch_bounds__(256) void k_ed_keys_wide_point(u32 n, const u32* slots, u32 w, u32 j, const u32* ktab,
+                                                            const u32* kok, u32 kcount, u32* out_enc, uint8_t* out_ok) {
+  using L = EdComb<RB>;
+  const u32 g = blockIdx.x * 256 + threadIdx.x;
+  if (g >= n) return;
+  const u32 sl = slots[g];
+  const bool ok = sl < kcount && kok[sl] != 0u;
+  u32 ew[8];
+#pragma unroll
+  for (int i = 0; i < 8; ++i) ew[i] = 0;
+  if (ok) {
+    ge_cached c;
+    atab_load(c, ktab + (size_t)sl * L::WORDS + (size_t)(w * L::NE + j - 1) * ED_CACHED_WORDS, 1, 0);
+    ge_ext p;
+    e29_sub_norm<1>(p.X, c.ypx, c.ymx);
+    e29_add_norm(p.Y, c.ypx, c.ymx);
+    p.Z = c.z2;
+    f29_set_zero(p.T);                      // ToBytes reads X, Y, Z
+    ge_tobytes(ew, p);
+  }
+#pragma unroll
+  for (int i = 0; i < 8; ++i) out_enc[(size_t)g * 8 + i] = ew[i];
+  out_ok[g] = ok ? 1u : 0u;
+}
+
 }  // namespace ed
 }  // namespace gv
+
+extern "C" hipError_t gvk_ed_keys_wide_point(uint32_t n, const uint32_t* slots, uint32_t w, uint32_t j, int rb,
+                                             const uint32_t* ktab, const uint32_t* kok, uint32_t kcount,
+                                             uint8_t* out_enc32, uint8_t* out_ok, hipStream_t st) {
+  if (n == 0) return hipSuccess;
+  const dim3 grd((n + 255) / 256), blk(256);
+  if (rb == 6 && w < 43 && j >= 1 && j <= 32)
+    hipLaunchKernelGGL(gv::ed::k_ed_keys_wide_point<6>, grd, blk, 0, st, n, slots, w, j, ktab, kok, kcount,
+                       (uint32_t*)out_enc32, out_ok);
+  else if (rb == 8 && w < 32 && j >= 1 && j <= 128)
+    hipLaunchKernelGGL(gv::ed::k_ed_keys_wide_point<8>, grd, blk, 0, st, n, slots, w, j, ktab, kok, kcount,
+                       (uint32_t*)out_enc32, out_ok);
+  else
+    return hipErrorInvalidValue;
+  return hipGetLastError();
+}
 
 extern "C" hipError_t gvk_ed_keys_point(uint32_t n, const uint32_t* slots, uint32_t w, uint32_t j,
                                         const uint32_t* ktab, const uint32_t* kpub, const uint32_t* kok,
@@ -900,7 +946,8 @@ extern "C" hipError_t gvk_ed_pack_bits(uint32_t n, const uint8_t* out8, uint64_t
 
 extern "C" hipError_t gvk_ed_keyed(const gvk_edk* b, hipStream_t st) {
   if (b->n == 0) return hipSuccess;
-  if (b->rb == 6) hipLaunchKernelGGL(gv::ed::k_ed_keyed<6>, dim3((b->n + 255) / 256), dim3(256), 0, st, *b);
+  if (b->rb == 8) hipLaunchKernelGGL(gv::ed::k_ed_keyed<8>, dim3((b->n + 255) / 256), dim3(256), 0, st, *b);
+  else if (b->rb == 6) hipLaunchKernelGGL(gv::ed::k_ed_keyed<6>, dim3((b->n + 255) / 256), dim3(256), 0, st, *b);
   else hipLaunchKernelGGL(gv::ed::k_ed_keyed<4>, dim3((b->n + 255) / 256), dim3(256), 0, st, *b);
   return hipGetLastError();
 }
@@ -909,8 +956,14 @@ extern "C" hipError_t gvk_ed_keys(const uint8_t* pub32, uint32_t n, uint32_t bas
                                   uint32_t* ktab, uint32_t* kpub, uint32_t* kok, uint32_t* wbase, int rb,
                                   hipStream_t st) {
   if (n == 0) return hipSuccess;
-  if (rb == 6 && !wbase) return hipErrorInvalidValue;     // the radix-64 tables: the split build only
-  if (wbase && rb == 6) {                   // chain + table launches (scratch: n * 64 * 36 words)
+  if (rb != 4 && rb != 6 && rb != 8) return hipErrorInvalidValue;
+  if (rb != 4 && !wbase) return hipErrorInvalidValue;     // the radix-64 / radix-256 tables: the split build only
+  if (rb == 8) {                            // scratch: n * 32 * 36 words
+    hipLaunchKernelGGL(gv::ed::k_ed_keys_chain<8>, dim3((n + 63) / 64), dim3(64), 0, st, pub32, n, base, slots, kpub,
+                       kok, wbase);
+    hipLaunchKernelGGL(gv::ed::k_ed_keys_tab<8>, dim3((n * gv::ed::EdComb<8>::NW + 255) / 256), dim3(256), 0, st, n,
+                       base, slots, ktab, (const uint32_t*)wbase);
+  } else if (wbase && rb == 6) {                   // chain + table launches (scratch: n * 64 * 36 words)
     hipLaunchKernelGGL(gv::ed::k_ed_keys_chain<6>, dim3((n + 63) / 64), dim3(64), 0, st, pub32, n, base, slots, kpub,
                        kok, wbase);
     hipLaunchKernelGGL(gv::ed::k_ed_keys_tab<6>, dim3((n * gv::ed::EdComb<6>::NW + 255) / 256), dim3(256), 0, st, n,

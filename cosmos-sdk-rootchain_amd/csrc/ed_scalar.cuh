@@ -89,5 +89,25 @@ GV_DEV bool sc_minimal(const uint32_t s[8]) {
   return b != 0;                         // s - L borrows
 }
 
+// Signed radix-2^RB digits of h < 2^253 (8 words) for the comb tables of -A
+// (k_ed_keyed): h = sum_w digit_w * 2^(RB w) over ed_comb_windows<RB>()
+// windows, digit_w in [-2^(RB-1), 2^(RB-1)) below the top window.  Window w's
+// digit from its RB bits and the carry of window w - 1 (cin: 0 before window
+// 0, updated for w + 1).  The top window keeps its value -- no carry out of
+// it: for h < L it holds at most 1 (RB 6: bit 252) or 17 (RB 8: bits
+// 248..252 and a carry), inside the table's entries 1..2^(RB-1).
+template <int RB>
+constexpr int ed_comb_windows() { return (253 + RB - 1) / RB; }
+template <int RB>
+GV_DEV int ed_comb_digit(const uint32_t h[8], int w, int& cin) {
+  constexpr int NW = ed_comb_windows<RB>(), NE = 1 << (RB - 1);
+  const int pos = RB * w, wi = pos >> 5;
+  const uint64_t pair = (uint64_t)h[wi] | (wi < 7 ? (uint64_t)h[wi + 1] << 32 : 0ull);
+  int dg = (int)((pair >> (pos & 31)) & (uint64_t)((1u << RB) - 1u)) + cin;
+  cin = 0;
+  if (w < NW - 1 && dg >= NE) { dg -= 1 << RB; cin = 1; }
+  return dg;
+}
+
 }  // namespace ed
 }  // namespace gv

@@ -316,6 +316,9 @@ hipError_t gvk_ed_verify(const gvk_ed* b, hipStream_t st);
 #define GV_EDK_WORDS (64 * 8 * 36)
 // The grouped route's radix-64 comb tables: 43 windows of 32 entries per key.
 #define GV_EDK64_WORDS (43 * 32 * 36)
+// The wide ed25519 arena (option "ed_keys_wide"): radix-64 combs as above
+// (198,144 B per key) or radix-256 ones, 32 windows of 128 entries (576 KiB).
+#define GV_EDK256_WORDS (32 * 128 * 36)
 typedef struct gvk_edl {
   uint32_t n;
   const uint32_t* slot;         // n key slots
@@ -334,7 +337,8 @@ typedef struct gvk_edl {
 // wbase (may be null: one lane per key does everything): n * 64 * 36 words of
 // scratch for the window bases -- the chain and the table adds then run as
 // two launches (k_ed_keys_chain, k_ed_keys_tab), same table words.  rb: the
-// comb radix bits, 4 (GV_EDK_WORDS per key) or 6 (GV_EDK64_WORDS; needs wbase).
+// comb radix bits, 4 (GV_EDK_WORDS per key), 6 (GV_EDK64_WORDS; needs wbase:
+// n * 43 * 36 words) or 8 (GV_EDK256_WORDS; needs wbase: n * 32 * 36 words).
 // slots (device memory, n words, or null): key g goes to row slots[g] of
 // ktab / kpub / kok instead of base + g (gv_ed_keys_replace; the caller has
 // bounded every entry and made them distinct).  The scratch stays per g.
@@ -348,6 +352,13 @@ hipError_t gvk_ed_keys(const uint8_t* pub32, uint32_t n, uint32_t base, const ui
 hipError_t gvk_ed_keys_point(uint32_t n, const uint32_t* slots, uint32_t w, uint32_t j, const uint32_t* ktab,
                              const uint32_t* kpub, const uint32_t* kok, uint32_t kcount, uint8_t* out_enc32,
                              uint8_t* out_pub32, uint8_t* out_ok, hipStream_t st);
+// The same for the wide arena's tables (k_ed_keys_wide_point): entry (w, j) =
+// j * 2^(rb w) * (-A) of the radix-2^rb comb (rb 6: w < 43, j <= 32; rb 8:
+// w < 32, j <= 128; else hipErrorInvalidValue).  kcount: the slots with wide
+// tables; kok: the key arena's verdicts.
+hipError_t gvk_ed_keys_wide_point(uint32_t n, const uint32_t* slots, uint32_t w, uint32_t j, int rb,
+                                  const uint32_t* ktab, const uint32_t* kok, uint32_t kcount, uint8_t* out_enc32,
+                                  uint8_t* out_ok, hipStream_t st);
 hipError_t gvk_ed_lat(const gvk_edl* b, hipStream_t st);
 // Small ed25519 batches against uncached keys (k_ed_lat_unc): b->pub32 per item.
 hipError_t gvk_ed_lat_unc(const gvk_edl* b, hipStream_t st);
@@ -367,7 +378,7 @@ typedef struct gvk_edk {
   uint32_t kcount;
   const uint32_t* btab;
   const uint32_t* btab16;       // GV_ED_BTAB16_WORDS, or null: [s]B from btab (32 additions instead of 16)
-  int rb;                       // ktab's comb radix bits: 4 (GV_EDK_WORDS per key; 0 = 4) or 6 (GV_EDK64_WORDS)
+  int rb;                       // ktab's comb radix bits: 4 (GV_EDK_WORDS per key; 0 = 4), 6 (GV_EDK64_WORDS) or 8 (GV_EDK256_WORDS)
   uint8_t* out8;                // n verdict bytes (device)
 } gvk_edk;
 hipError_t gvk_ed_keyed(const gvk_edk* b, hipStream_t st);

@@ -201,7 +201,23 @@ struct Dev {
   // (GV_EDK_WORDS), the raw key words (8), the FromBytes verdict
   uint32_t *ektab = nullptr, *ekpub = nullptr, *ekok = nullptr;
   size_t ekcap = 0;
-  uint8_t* edl_h = nullptr;                       // small keyed ed25519 batches: pinned inputs + verdicts (zero-copy)
+  // the wide ed25519 arena (option "ed_keys_wide"): per slot the radix-2^ekw_rb
+  // comb of -A (ekw_rb 6: GV_EDK64_WORDS, 8: GV_EDK256_WORDS; the raw key and
+  // the verdict stay in ekpub / ekok), capacity ekcapw, grown by doubling while
+  // the HBM budget holds it; ekeysw leading slots built.  ekw_full: a growth or
+  // a build failed (no more wide builds until gv_ed_keys_reset)
+  uint32_t* ektabw = nullptr;
+  size_t ekcapw = 0, ekeysw = 0;
+  int ekw_rb = 0;
+  bool ekw_full = false;
+  // device-resident keyed ed25519 calls (gv_dev_verify_ed25519_msgs_keyed):
+  // verdict bytes + slot-order sort scratch, and the event behind the last
+  // kernel that reads it and the arena (the arena's writers wait for it)
+  uint8_t* edkd_s = nullptr;
+  size_t edkd_s_cap = 0;
+  hipEvent_t edkd_last = nullptr;
+  hipStream_t edkd_last_st = nullptr;
+  uint8_t* edl_h = nullptr;                      // small keyed ed25519 batches: pinned inputs + verdicts (zero-copy)
   size_t edl_h_cap = 0;
   // ed25519 in-batch key grouping: per-batch key arena (comb tables of -A), pinned count, stats
   uint32_t *edg_ktab = nullptr, *edg_kpub = nullptr, *edg_kok = nullptr;
@@ -775,6 +791,12 @@ struct gv_ctx {
   bool ed_group_r64 = true;      // grouped ed25519 key tables as radix-64 combs: 43 [h](-A) additions, not 64 (GV_ED_GROUP_R64)
   bool ed_keyed = true;          // keyed ed25519 batches past ed_lat_max on k_ed_keyed (GV_ED_KEYED=0: the throughput kernels)
   size_t ed_lat_max = 2048;      // keyed ed25519 batches up to this size take k_ed_lat_sl (one signature per block)
+  int ed_keys_wide = 0;          // the ed25519 arena also holds radix-2^6 or radix-2^8 combs of -A for k_ed_keyed
+                                 // (0 = none, 6, 8; "ed_keys_wide", GV_ED_KEYS_WIDE): taken by an arena started from
+                                 // slot 0; 0 stops their use at once
+  size_t ed_keys_wide_bytes = 0; // the wide ed25519 arena is never allocated larger than this ("ed_keys_wide_mb",
+                                 // GV_ED_KEYS_WIDE_MB; 0 = no limit)
+  std::atomic<uint64_t> ed_keyed_wide{0};   // keyed batches / chunks that ran on wide tables since gv_open ("ed_keyed_wide")
   size_t ed_unc_lat_max = 2048;  // uncached ed25519 host batches up to this size take k_ed_lat_unc (one signature per block)
 };
 
@@ -2059,6 +2081,14 @@ int gv_open(const int* dev_ids, int n_dev, gv_ctx** out) {
     const long long v = atoll(kc);
     if (v >= 256 && (unsigned long long)v <= kMaxItems) ctx->ed_key_cap = (size_t)v;
   }
+  if (const char* ew = getenv("GV_ED_KEYS_WIDE")) {
+    const int v = atoi(ew);
+    if (v == 0 || v == 6 || v == 8) ctx->ed_keys_wide = v;
+  }
+  if (const char* em = getenv("GV_ED_KEYS_WIDE_MB")) {
+    const long long v = atoll(em);
+    if (v >= 0 && v <= (long long)(SIZE_MAX >> 20)) ctx->ed_keys_wide_bytes = (size_t)v << 20;
+  }
   if (const char* hb = getenv("GV_HBM_BUDGET_MB")) {
     const long long v = atoll(hb);
     if (v > 0) ctx->hbm_budget = (size_t)v << 20;
@@ -2170,7 +2200,9 @@ void gv_close(gv_ctx* ctx) {
     if (d->ed.h_blob) (void)hipHostFree(d->ed.h_blob);
     if (d->ed.h_bits) (void)hipHostFree(d->ed.h_bits);
     if (d->ed.last) (void)hipEventDestroy(d->ed.last);
-    for (uint32_t* p : {d->ektab, d->ekpub, d->ekok}) if (p) (void)hipFree(p);
+    for (uint32_t* p : {d->ektab, d->ekpub, d->ekok, d->ektabw}) if (p) (void)hipFree(p);
+    if (d->edkd_s) (void)hipFree(d->edkd_s);
+    if (d->edkd_last) (void)hipEventDestroy(d->edkd_last);
     if (d->edl_h) (void)hipHostFree(d->edl_h);
     for (uint32_t* q : {d->edg_ktab, d->edg_kpub, d->edg_kok}) if (q) (void)hipFree(q);
     if (d->ed_h_count) (void)hipHostFree(d->ed_h_count);
@@ -2680,6 +2712,97 @@ int ed_build(gv_ctx* ctx, Dev* d, hipStream_t st, const uint8_t* pub32, size_t n
   (void)hipFree(dp);
   return ok ? GV_OK : GV_EHIP;
 }
+
+// ---- the wide ed25519 arena (option "ed_keys_wide"; ektabw beside ektab)
+inline size_t ed_wide_slot_bytes(int rb) {
+  return rb == 8 ? (size_t)GV_EDK256_WORDS * 4 : rb == 6 ? (size_t)GV_EDK64_WORDS * 4 : 0;
+}
+inline size_t ed_wide_windows(int rb) { return rb == 8 ? 32 : 43; }
+
+// Drop the wide ed25519 arena (its memory back to the device).
+void free_ed_keys_wide(Dev* d) {
+  if (d->ektabw) { (void)hipFree(d->ektabw); d->ektabw = nullptr; }
+  d->opt_bytes -= std::min(d->opt_bytes, d->ekcapw * ed_wide_slot_bytes(d->ekw_rb));
+  d->ekcapw = d->ekeysw = 0;
+}
+
+// Grow the wide ed25519 arena (radix d->ekw_rb) to `need` slots keeping the
+// first `used` -- doubling, not past ed_key_cap, then exact, as
+// ensure_ed_keys.  False, and the arena as it was, when `limit` (option
+// "ed_keys_wide_mb"; 0: none) or the HBM budget does not hold the new arena,
+// when it would take device memory the secp256k1 wide arena keeps free too
+// (the k4 / k6 arena's growth to key_cap, the radix-16 ed25519 arena's to
+// ed_key_cap, 8 GiB of batch scratch), or when an allocation fails.
+bool ensure_ed_keys_wide(gv_ctx* ctx, Dev* d, size_t need, size_t used, hipStream_t st) {
+  if (need <= d->ekcapw) return true;
+  const size_t cap_limit = ctx->ed_key_cap;
+  const size_t grow = d->ekcapw >= cap_limit ? need
+                                             : std::min<size_t>(2 * d->ekcapw, std::max<size_t>(need, cap_limit));
+  const size_t cap = round_up(std::max<size_t>({need, grow, 256}), 256);
+  const size_t slot_b = ed_wide_slot_bytes(d->ekw_rb);
+  if (!slot_b) return false;
+  if (ctx->ed_keys_wide_bytes && cap * slot_b > ctx->ed_keys_wide_bytes) return false;
+  if (d->opt_bytes + cap * slot_b > ctx->hbm_budget) return false;
+  size_t free_b = 0, total_b = 0;
+  if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) return false;
+  const size_t reserve = (ctx->key_cap > d->kcap ? ctx->key_cap - d->kcap : 0) * key_slot_bytes(true) +
+                         (ctx->ed_key_cap > d->ekcap ? ctx->ed_key_cap - d->ekcap : 0) *
+                             ((size_t)GV_EDK_WORDS + 8 + 1) * 4 +
+                         (size_t(8) << 30);
+  if (free_b < cap * slot_b + reserve) return false;
+  uint32_t* t = nullptr;
+  if (hipMalloc(&t, cap * slot_b) != hipSuccess) {
+    (void)hipGetLastError();
+    return false;
+  }
+  used = std::min(used, d->ekeysw);
+  if (used && (hipMemcpyAsync(t, d->ektabw, used * slot_b, hipMemcpyDeviceToDevice, st) != hipSuccess ||
+               hipStreamSynchronize(st) != hipSuccess)) {
+    (void)hipFree(t);
+    (void)hipGetLastError();
+    return false;
+  }
+  if (d->ektabw) (void)hipFree(d->ektabw);
+  d->opt_bytes = d->opt_bytes - std::min(d->opt_bytes, d->ekcapw * slot_b) + cap * slot_b;
+  d->ektabw = t;
+  d->ekcapw = cap;
+  return true;
+}
+
+// The wide tables of the n keys pub32 (host) into slots base.. of d's wide
+// arena, or into slots[i] (host; null: append), by the split build
+// (k_ed_keys_chain / k_ed_keys_tab at the arena's radix; the chain rewrites
+// the slots' raw key words and verdicts with the values ed_build left), in
+// chunks whose window-base scratch stays within ed_build's 1 GiB.
+int ed_build_wide(Dev* d, hipStream_t st, const uint8_t* pub32, size_t n, size_t base, const uint32_t* slots) {
+  const size_t wb_key = ed_wide_windows(d->ekw_rb) * 36 * 4;
+  const size_t step = std::min<size_t>(n, std::min<size_t>(65536, ((size_t)1 << 30) / wb_key));
+  const size_t o_sl = round_up(step * 32, 256), o_wb = o_sl + round_up(step * 4, 256);
+  uint8_t* dp = nullptr;
+  if (hipMalloc(&dp, o_wb + step * wb_key) != hipSuccess) {
+    (void)hipGetLastError();
+    return GV_ENOMEM;
+  }
+  bool ok = true;
+  for (size_t c0 = 0; ok && c0 < n; c0 += step) {
+    const size_t cn = std::min(step, n - c0);
+    ok = hipMemcpyAsync(dp, pub32 + c0 * 32, cn * 32, hipMemcpyHostToDevice, st) == hipSuccess &&
+         (!slots || hipMemcpyAsync(dp + o_sl, slots + c0, cn * 4, hipMemcpyHostToDevice, st) == hipSuccess) &&
+         gvk_ed_keys(dp, (uint32_t)cn, slots ? 0u : (uint32_t)(base + c0), slots ? (const uint32_t*)(dp + o_sl) : nullptr,
+                     d->ektabw, d->ekpub, d->ekok, (uint32_t*)(dp + o_wb), d->ekw_rb, st) == hipSuccess &&
+         hipStreamSynchronize(st) == hipSuccess;
+  }
+  (void)hipFree(dp);
+  return ok ? GV_OK : GV_EHIP;
+}
+
+// A device-resident keyed batch still queued reads the arena: its writers
+// (load, replace, a load after reset) wait for it before they write, move or
+// free arena memory.  The caller holds ed_keys_mu and d->mu.
+int ed_arena_quiesce(Dev* d) {
+  if (d->edkd_last_st) CK(hipEventSynchronize(d->edkd_last));
+  return GV_OK;
+}
 }  // namespace
 
 int gv_ed_keys_load(gv_ctx* ctx, size_t n, const uint8_t* pub32, uint32_t* slot_out) {
@@ -2693,9 +2816,31 @@ int gv_ed_keys_load(gv_ctx* ctx, size_t n, const uint8_t* pub32, uint32_t* slot_
     std::lock_guard<std::mutex> lk(d->mu);
     CK(hipSetDevice(d->id));
     hipStream_t st = d->set[0].st;
-    int rc = ensure_ed_keys(d, base + n, base, st, ctx->ed_key_cap);
+    int rc = ed_arena_quiesce(d);
+    if (rc) return rc;
+    if (base == 0) {                            // after gv_ed_keys_reset the slots are rewritten from 0
+      d->ekeysw = 0;
+      d->ekw_full = false;
+      if (d->ekw_rb != ctx->ed_keys_wide) {     // the option is read again: another radix, or none
+        free_ed_keys_wide(d);
+        d->ekw_rb = ctx->ed_keys_wide;
+      }
+    }
+    rc = ensure_ed_keys(d, base + n, base, st, ctx->ed_key_cap);
     if (!rc) rc = ed_build(ctx, d, st, pub32, n, base, nullptr);
     if (rc) return rc;
+    // the wide tables while every earlier slot has them and memory holds the
+    // grown arena; a refusal or a failed build frees them and stops them until
+    // gv_ed_keys_reset (every slot keeps its radix-16 table): never an error
+    if (ctx->ed_keys_wide && d->ekw_rb && d->ekeysw == base && !d->ekw_full) {
+      if (ensure_ed_keys_wide(ctx, d, base + n, base, st) && ed_build_wide(d, st, pub32, n, base, nullptr) == GV_OK) {
+        d->ekeysw = base + n;
+      } else {
+        (void)hipGetLastError();
+        free_ed_keys_wide(d);
+        d->ekw_full = true;
+      }
+    }
   }
   ctx->ed_kpub.insert(ctx->ed_kpub.end(), pub32, pub32 + n * 32);
   ctx->ed_keys = base + n;
@@ -2712,12 +2857,33 @@ int gv_ed_keys_replace(gv_ctx* ctx, size_t n, const uint32_t* slots, const uint8
   // every check before the first device write
   const size_t count = ctx->ed_keys;
   if (!check_slots(count, n, slots)) return GV_EINVAL;
+  std::vector<uint32_t> ws;                     // the slots (and their keys) below the wide tables' built prefix
+  std::vector<uint8_t> wp;
   for (Dev* d : ctx->devs) {                    // every device holds every key
     std::lock_guard<std::mutex> lk(d->mu);
     CK(hipSetDevice(d->id));
-    if (count > d->ekcap) return GV_EINVAL;     // (never: the arena holds its slots)
-    const int rc = ed_build(ctx, d, d->set[0].st, pub32, n, 0, slots);
+    if (count > d->ekcap || d->ekeysw > d->ekcapw) return GV_EINVAL;   // (never: the arenas hold their slots)
+    int rc = ed_arena_quiesce(d);               // a batch already enqueued runs against the old keys
+    if (!rc) rc = ed_build(ctx, d, d->set[0].st, pub32, n, 0, slots);
     if (rc) return rc;
+    if (d->ektabw && d->ekeysw) {               // the wide tables of the named slots that have them
+      const uint32_t* sl = slots;
+      const uint8_t* pb = pub32;
+      size_t m = n;
+      if (d->ekeysw < count) {
+        ws.clear();
+        wp.clear();
+        for (size_t i = 0; i < n; ++i)
+          if (slots[i] < d->ekeysw) {
+            ws.push_back(slots[i]);
+            wp.insert(wp.end(), pub32 + i * 32, pub32 + (i + 1) * 32);
+          }
+        sl = ws.data();
+        pb = wp.data();
+        m = ws.size();
+      }
+      if (m && (rc = ed_build_wide(d, d->set[0].st, pb, m, 0, sl))) return rc;
+    }
   }
   // the host copy (large batches with ed_keyed 0 read it) only after every device has succeeded
   for (size_t i = 0; i < n; ++i) memcpy(&ctx->ed_kpub[(size_t)slots[i] * 32], pub32 + i * 32, 32);
@@ -2759,6 +2925,11 @@ int gv_ed_keys_reset(gv_ctx* ctx) {
   std::lock_guard<std::mutex> kl(ctx->ed_keys_mu);
   ctx->ed_keys = 0;
   ctx->ed_kpub.clear();
+  for (Dev* d : ctx->devs) {                    // the wide tables start over with the arena (memory kept for the next load)
+    std::lock_guard<std::mutex> lk(d->mu);
+    d->ekeysw = 0;
+    d->ekw_full = false;
+  }
   ctx->ed_keys_gen.fetch_add(1);
   return GV_OK;
 }
@@ -2783,6 +2954,12 @@ int ensure_dev(uint8_t** p, size_t* cap, size_t bytes) {
   if (hipMalloc((void**)p, c) != hipSuccess) { *p = nullptr; return GV_ENOMEM; }
   *cap = c;
   return GV_OK;
+}
+
+// k_ed_keyed reads d's wide tables when every slot of the arena has them
+// (option "ed_keys_wide" still on), else the radix-16 ones.
+bool ed_wide_serves(const gv_ctx* ctx, const Dev* d, size_t kcount) {
+  return ctx->ed_keys_wide && d->ektabw && d->ekw_rb && kcount && d->ekeysw >= kcount && d->ekcapw >= kcount;
 }
 
 // Items [lo, hi) of a large keyed ed25519 batch on one device (k_ed_keyed):
@@ -2852,7 +3029,9 @@ int ed_keyed_slice(gv_ctx* ctx, Dev* d, size_t lo, size_t hi, const EdKeyedHost&
     b.msg_blob = dd + o_blob;
     b.msg_off = (const uint64_t*)(dd + o_off);
     b.msg_len = (const uint32_t*)(dd + o_len);
-    b.ktab = d->ektab;
+    const bool wide = ed_wide_serves(ctx, d, kcount);
+    b.ktab = wide ? d->ektabw : d->ektab;
+    b.rb = wide ? d->ekw_rb : 4;
     b.kpub = d->ekpub;
     b.kok = d->ekok;
     b.kcount = (uint32_t)kcount;
@@ -2860,6 +3039,7 @@ int ed_keyed_slice(gv_ctx* ctx, Dev* d, size_t lo, size_t hi, const EdKeyedHost&
     b.btab16 = ed_btab16(d, ctx->ed_btab16, st);
     b.out8 = dd + o_out;
     CK(gvk_ed_keyed(&b, st));
+    if (wide) ctx->ed_keyed_wide.fetch_add(1);
     CK(hipMemcpyAsync(h + o_out, dd + o_out, cn, hipMemcpyDeviceToHost, st));
     pend[k] = Pending{c0, cn, o_out, true};
     return GV_OK;
@@ -2955,6 +3135,130 @@ int gv_verify_ed25519_msgs_keyed(gv_ctx* ctx, size_t n, const uint32_t* slot, co
   CK(hipStreamSynchronize(st));
   memcpy(out_ok, h + o_out, n);
   return GV_OK;
+}
+
+// Device-resident keyed ed25519: batches up to "ed_lat_max" on k_ed_lat_sl
+// (the radix-16 tables), larger ones on k_ed_keyed in slot order -- the wide
+// tables when every slot has them --, whatever "ed_keyed" says (no host copy
+// of the items exists for the throughput kernels).  Either kernel writes a
+// verdict byte per item into the device's scratch; k_ed_pack_bits makes the
+// bitmap.  ed_keys_mu is held while the batch is enqueued and edkd_last is
+// recorded behind its last kernel: the arena's writers wait for it.
+int gv_dev_verify_ed25519_msgs_keyed(gv_ctx* ctx, int dev_slot, size_t n, const void* d_slot, const void* d_sig64,
+                                     const void* d_msg_blob, const void* d_msg_off, const void* d_msg_len,
+                                     void* d_bits, void* stream) {
+  Dev* d = nullptr;
+  int rc = dev_common(ctx, dev_slot, n, d_slot, d_sig64, d_bits, &d);
+  if (rc || n == 0) return rc;
+  if (!d_msg_off || !d_msg_len || ((uintptr_t)d_sig64 & 15)) return GV_EINVAL;
+  std::lock_guard<std::mutex> kl(ctx->ed_keys_mu);
+  std::lock_guard<std::mutex> lk(d->mu);
+  CK(hipSetDevice(d->id));
+  hipStream_t st = stream ? (hipStream_t)stream : d->set[0].st;
+  order_after_pipeline(d, st);
+  // an arena never allocated (or smaller than the count: never) reads as empty
+  const size_t kcount = std::min(ctx->ed_keys, d->ekcap);
+  if (kcount == 0) {                              // no key in any slot: no launch reads the arena
+    CK(hipMemsetAsync(d_bits, 0, (n + 63) / 64 * 8, st));
+    return GV_OK;
+  }
+  if ((rc = ed_ensure(d, 256, st))) return rc;    // the resident comb table of B
+  if (!d->edkd_last) CK(hipEventCreateWithFlags(&d->edkd_last, hipEventDisableTiming));
+  const bool small = n <= ctx->ed_lat_max;
+  const bool sorted = !small && ctx->sort_keys;
+  const size_t C = round_up(n, 256), nb = kcount + 1, tb = gvk_sort_temp_bytes((uint32_t)nb);
+  const size_t sw = sorted ? 3 * C + 2 * round_up(nb, 64) + round_up(tb / 4 + 1, 64) : 0;
+  if (C + sw * 4 > d->edkd_s_cap) {               // the scratch grows: the last batch on it first
+    if (d->edkd_last_st) CK(hipEventSynchronize(d->edkd_last));
+    if ((rc = ensure_dev(&d->edkd_s, &d->edkd_s_cap, C + sw * 4))) return rc;
+  }
+  if (d->edkd_last_st && d->edkd_last_st != st) CK(hipStreamWaitEvent(st, d->edkd_last, 0));
+  uint8_t* out8 = d->edkd_s;
+  if (small) {
+    gvk_edl b;
+    memset(&b, 0, sizeof b);
+    b.n = (uint32_t)n;
+    b.slot = (const uint32_t*)d_slot;
+    b.sig64 = (const uint8_t*)d_sig64;
+    b.msg_blob = (const uint8_t*)d_msg_blob;
+    b.msg_off = (const uint64_t*)d_msg_off;
+    b.msg_len = (const uint32_t*)d_msg_len;
+    b.ktab = d->ektab;
+    b.kpub = d->ekpub;
+    b.kok = d->ekok;
+    b.kcount = (uint32_t)kcount;
+    b.btab = d->edtab;
+    b.out8 = out8;
+    CK(gvk_ed_lat(&b, st));
+  } else {
+    const uint32_t* btab16 = ed_btab16(d, ctx->ed_btab16, st);
+    gvk_sort so;
+    memset(&so, 0, sizeof so);
+    if (sorted) {
+      uint32_t* p = (uint32_t*)(d->edkd_s + C);
+      so.pos = p; p += C;
+      so.perm = p; p += C;
+      so.kslot = p; p += C;
+      so.cnt = p; p += round_up(nb, 64);
+      so.off = p; p += round_up(nb, 64);
+      so.temp = p;
+      so.temp_bytes = tb;
+      CK(gvk_sort_slots(&so, (uint32_t)n, (const uint32_t*)d_slot, (uint32_t)kcount, st));
+    }
+    const bool wide = ed_wide_serves(ctx, d, kcount);
+    gvk_edk b;
+    memset(&b, 0, sizeof b);
+    b.n = (uint32_t)n;
+    b.perm = sorted ? so.perm : nullptr;
+    b.slot = (const uint32_t*)d_slot;
+    b.sig64 = (const uint8_t*)d_sig64;
+    b.msg_blob = (const uint8_t*)d_msg_blob;
+    b.msg_off = (const uint64_t*)d_msg_off;
+    b.msg_len = (const uint32_t*)d_msg_len;
+    b.ktab = wide ? d->ektabw : d->ektab;
+    b.rb = wide ? d->ekw_rb : 4;
+    b.kpub = d->ekpub;
+    b.kok = d->ekok;
+    b.kcount = (uint32_t)kcount;
+    b.btab = d->edtab;
+    b.btab16 = btab16;
+    b.out8 = out8;
+    CK(gvk_ed_keyed(&b, st));
+    if (wide) ctx->ed_keyed_wide.fetch_add(1);
+  }
+  CK(gvk_ed_pack_bits((uint32_t)n, out8, (uint64_t*)d_bits, st));
+  CK(hipEventRecord(d->edkd_last, st));
+  d->edkd_last_st = st;
+  return GV_OK;
+}
+
+int gv_ed_keys_wide_point(gv_ctx* ctx, size_t n, const uint32_t* slots, uint32_t w, uint32_t j, uint8_t* out_enc32,
+                          uint8_t* out_ok) {
+  if (!ctx) return GV_EINVAL;
+  std::lock_guard<std::mutex> kl(ctx->ed_keys_mu);
+  Dev* d = ctx->devs[0];
+  std::lock_guard<std::mutex> lk(d->mu);
+  const size_t kcount = d->ektabw ? std::min(std::min(d->ekeysw, d->ekcapw), ctx->ed_keys) : 0;
+  const int rb = kcount ? d->ekw_rb : 0;
+  if (rb != 6 && rb != 8) return GV_EINVAL;       // no wide arena
+  if (w >= ed_wide_windows(rb) || j < 1 || j > (1u << (rb - 1))) return GV_EINVAL;
+  if (n == 0) return GV_OK;
+  if (!slots || !out_enc32 || !out_ok || n > kMaxItems) return GV_EINVAL;
+  CK(hipSetDevice(d->id));
+  hipStream_t st = d->set[0].st;
+  uint8_t* buf = nullptr;
+  const size_t sb = round_up(n * 4, 256), eb = round_up(n * 32, 256);
+  if (hipMalloc(&buf, sb + eb + n) != hipSuccess) return GV_ENOMEM;
+  int rc = GV_OK;
+  if (hipMemcpyAsync(buf, slots, n * 4, hipMemcpyHostToDevice, st) != hipSuccess ||
+      gvk_ed_keys_wide_point((uint32_t)n, (const uint32_t*)buf, w, j, rb, d->ektabw, d->ekok, (uint32_t)kcount, buf + sb,
+                             buf + sb + eb, st) != hipSuccess ||
+      hipMemcpyAsync(out_enc32, buf + sb, n * 32, hipMemcpyDeviceToHost, st) != hipSuccess ||
+      hipMemcpyAsync(out_ok, buf + sb + eb, n, hipMemcpyDeviceToHost, st) != hipSuccess ||
+      hipStreamSynchronize(st) != hipSuccess)
+    rc = GV_EHIP;
+  (void)hipFree(buf);
+  return rc;
 }
 
 int gv_host_alloc(gv_ctx* ctx, size_t bytes, void** out) {
@@ -3074,6 +3378,9 @@ int gv_get_option(gv_ctx* ctx, const char* key, long long* val) {
               {"keys_wide_mb", (long long)(ctx->keys_wide_bytes >> 20)},
               {"keys_replaced", (long long)ctx->keys_replaced.load()},   // read-only: gv_keys_replace's slots so far
               {"ed_keys_replaced", (long long)ctx->ed_keys_replaced.load()},   // the same for gv_ed_keys_replace
+              {"ed_keys_wide", ctx->ed_keys_wide},
+              {"ed_keys_wide_mb", (long long)(ctx->ed_keys_wide_bytes >> 20)},
+              {"ed_keyed_wide", (long long)ctx->ed_keyed_wide.load()},   // read-only: keyed batches / chunks on wide tables
               {"kw_qw", GV_KW_QW},                   // read-only: the wide arena's window width (build)
               {"kwn_qw", GV_KWN ? GV_KWN_QW : 0}};   // read-only: its narrow width (build; 0: not compiled)
   // read-only: the first device's wide arena as gv_keys_load left it -- its
@@ -3084,6 +3391,17 @@ int gv_get_option(gv_ctx* ctx, const char* key, long long* val) {
     std::lock_guard<std::mutex> lk(d->mu);
     const bool live = d->kqtw && d->keysw;
     *val = !live ? 0 : !strcmp(key, "kw_arena_qw") ? d->kw_qw : d->kw_ng;
+    return GV_OK;
+  }
+  // read-only: the first device's wide ed25519 arena as gv_ed_keys_load left
+  // it -- its radix bits (0: no slot has wide tables) and the slots that have them
+  if (!strcmp(key, "ed_kw_rb") || !strcmp(key, "ed_kw_keys")) {
+    if (ctx->devs.empty()) return GV_EINVAL;
+    std::lock_guard<std::mutex> kl(ctx->ed_keys_mu);
+    Dev* d = ctx->devs[0];
+    std::lock_guard<std::mutex> lk(d->mu);
+    const bool live = d->ektabw && d->ekeysw;
+    *val = !live ? 0 : !strcmp(key, "ed_kw_rb") ? d->ekw_rb : (long long)d->ekeysw;
     return GV_OK;
   }
   for (const auto& o : opts)
@@ -3179,6 +3497,16 @@ int gv_set_option(gv_ctx* ctx, const char* key, long long val) {
   } else if (!strcmp(key, "ed_keyed")) {
     if (val != 0 && val != 1) return GV_EINVAL;
     ctx->ed_keyed = val != 0;
+  } else if (!strcmp(key, "ed_keys_wide")) {
+    // the radix of an arena started from slot 0 from now on (a running arena
+    // keeps its tables until gv_ed_keys_reset); 0 stops their use at once
+    if (val != 0 && val != 6 && val != 8) return GV_EINVAL;
+    std::lock_guard<std::mutex> kl(ctx->ed_keys_mu);
+    ctx->ed_keys_wide = (int)val;
+  } else if (!strcmp(key, "ed_keys_wide_mb")) {
+    if (val < 0 || (unsigned long long)val > (SIZE_MAX >> 20)) return GV_EINVAL;
+    std::lock_guard<std::mutex> kl(ctx->ed_keys_mu);
+    ctx->ed_keys_wide_bytes = (size_t)val << 20;
   } else if (!strcmp(key, "keys_wide")) {
     // the layout of an arena started from slot 0 from now on (a running arena
     // keeps its layout until gv_keys_reset); 0 stops its use at once

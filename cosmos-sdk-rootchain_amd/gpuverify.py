@@ -46,7 +46,7 @@ EXPORTED_SYMBOLS = (
     "gv_keys_point", "gv_keys_replace", "gv_dev_stream_create", "gv_dev_stream_sync", "gv_dev_stream_destroy",
     "gv_verify_ed25519_msgs", "gv_dev_verify_ed25519_msgs", "gv_last_slices", "gv_group_stats", "gv_route_stats", "gv_host_alloc", "gv_host_free",
     "gv_ed_keys_load", "gv_ed_keys_reset", "gv_ed_keys_count", "gv_ed_keys_generation", "gv_verify_ed25519_msgs_keyed",
-    "gv_ed_keys_replace", "gv_ed_keys_point",
+    "gv_ed_keys_replace", "gv_ed_keys_point", "gv_dev_verify_ed25519_msgs_keyed", "gv_ed_keys_wide_point",
     "gv_submit_digests", "gv_submit_digests_keyed", "gv_submit_msgs", "gv_submit_msgs_keyed", "gv_wait",
 )
 
@@ -111,6 +111,10 @@ def load(path: str = LIB_PATH):
     L.gv_ed_keys_point.restype = i32
     L.gv_verify_ed25519_msgs_keyed.argtypes = [vp, sz, vp, vp, vp, vp, vp, vp]
     L.gv_verify_ed25519_msgs_keyed.restype = i32
+    L.gv_dev_verify_ed25519_msgs_keyed.argtypes = [vp, i32, sz, vp, vp, vp, vp, vp, vp, vp]
+    L.gv_dev_verify_ed25519_msgs_keyed.restype = i32
+    L.gv_ed_keys_wide_point.argtypes = [vp, sz, vp, ctypes.c_uint32, ctypes.c_uint32, vp, vp]
+    L.gv_ed_keys_wide_point.restype = i32
     L.gv_set_option.argtypes = [vp, ctypes.c_char_p, ctypes.c_longlong]
     L.gv_set_option.restype = i32
     L.gv_get_option.argtypes = [vp, ctypes.c_char_p, ctypes.POINTER(ctypes.c_longlong)]
@@ -523,6 +527,46 @@ class Verifier:
                                                   ctypes.c_void_p(d_blob), ctypes.c_void_p(d_off),
                                                   ctypes.c_void_p(d_len), ctypes.c_void_p(d_bits),
                                                   ctypes.c_void_p(stream or 0)), "gv_dev_verify_ed25519_msgs")
+
+    def dev_verify_ed25519_keyed(self, slot: int, n: int, d_slots, d_sig, d_blob, d_off, d_len, d_bits, stream=None):
+        """Device-resident verify_batch_ed25519_keyed: d_* are device addresses (ints) on device
+        slot `slot` -- d_slots n x u32, d_sig n x 64 (16-byte aligned), d_off u64 / d_len u32 per
+        item, d_blob (0 when every length is 0) --, accept bits into d_bits ((n + 63) // 64 u64
+        words); stream a hipStream_t int (None: the library's)."""
+        if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or n < 0:
+            raise ValueError("dev_verify_ed25519_keyed: n must be a non-negative integer")
+        if isinstance(slot, bool) or not isinstance(slot, (int, np.integer)):
+            raise ValueError("dev_verify_ed25519_keyed: slot must be a device slot number")
+        for name, a in (("d_slots", d_slots), ("d_sig", d_sig), ("d_blob", d_blob), ("d_off", d_off),
+                        ("d_len", d_len), ("d_bits", d_bits), ("stream", stream)):
+            if a is not None and (isinstance(a, bool) or not isinstance(a, (int, np.integer)) or a < 0):
+                raise ValueError(f"dev_verify_ed25519_keyed: {name} must be a device address (int)")
+        if n == 0:
+            return
+        _check(self._L.gv_dev_verify_ed25519_msgs_keyed(self._ctx, int(slot), int(n), ctypes.c_void_p(d_slots or 0),
+                                                        ctypes.c_void_p(d_sig or 0), ctypes.c_void_p(d_blob or 0),
+                                                        ctypes.c_void_p(d_off or 0), ctypes.c_void_p(d_len or 0),
+                                                        ctypes.c_void_p(d_bits or 0), ctypes.c_void_p(stream or 0)),
+               "gv_dev_verify_ed25519_msgs_keyed")
+
+    def ed_keys_wide_point(self, slots: np.ndarray, w: int = 0, j: int = 1):
+        """For `slots` of the wide ed25519 arena (option "ed_keys_wide" 6 or 8): the encoding of
+        table entry j * 2^(rb w) * (-A) (n x 32 bytes) and the FromBytes verdicts; rb, the
+        windows and the entries per window are the arena's ("ed_kw_rb": 43 x 32 or 32 x 128)."""
+        slots = np.ascontiguousarray(slots)
+        if slots.ndim != 1 or slots.dtype.kind not in "ui" or (slots.size and (slots.min() < 0 or slots.max() >= 2 ** 32)):
+            raise ValueError("ed_keys_wide_point: slots must be a 1-d array of u32 slot numbers")
+        for name, a, lo, hi in (("w", w, 0, 42), ("j", j, 1, 128)):      # the widest ranges either radix has
+            if isinstance(a, bool) or not isinstance(a, (int, np.integer)) or not lo <= a <= hi:
+                raise ValueError(f"ed_keys_wide_point: {name} must be an integer in [{lo}, {hi}]")
+        slots = np.ascontiguousarray(slots, dtype=np.uint32)
+        n = slots.shape[0]
+        enc = np.zeros((n, 32), dtype=np.uint8)
+        ok = np.zeros(n, dtype=np.uint8)
+        if n:
+            _check(self._L.gv_ed_keys_wide_point(self._ctx, n, _ptr(slots), int(w), int(j), _ptr(enc), _ptr(ok)),
+                   "gv_ed_keys_wide_point")
+        return enc, ok
 
     def last_stage_ms(self, slot: int = 0):
         a, b, c = ctypes.c_float(), ctypes.c_float(), ctypes.c_float()

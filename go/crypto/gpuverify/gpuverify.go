@@ -241,6 +241,12 @@ type GPU struct {
 	// those no longer fit; 11 or 9 = that width only.  Applies to an arena
 	// started from slot 0 (default 0, env GV_KEYS_WIDE_QW).
 	KeysWideQW int
+	// EdKeysWide: the ed25519 key arena also keeps each key's radix-2^6 (6:
+	// 194 KB more per key) or radix-2^8 (8: 576 KB more) comb table, read by
+	// large keyed ed25519 batches (gv_set_option "ed_keys_wide"); 0 = the
+	// radix-16 tables only.  Applies to an arena started from slot 0
+	// (default 0, env GV_ED_KEYS_WIDE).
+	EdKeysWide int
 	// Logger, when set, reports every call that fell back to the CPU.
 	Logger Logger
 
@@ -282,7 +288,7 @@ func Open(devices []int) (*GPU, error) {
 	}
 	g := &GPU{ctx: ctx, CPUBelow: DefaultCPUBelow, Keyed: true, KeyLoadMin: DefaultKeyLoadMin,
 		KeyCap: envInt("GV_KEY_CAP", DefaultKeyCap), EdKeyCap: envInt("GV_ED_KEY_CAP", DefaultEdKeyCap),
-		KeysWideQW: envInt("GV_KEYS_WIDE_QW", 0),
+		KeysWideQW: envInt("GV_KEYS_WIDE_QW", 0), EdKeysWide: envInt("GV_ED_KEYS_WIDE", 0),
 		slots: map[secp256k1.PubKeySecp256k1]uint32{}, edSlots: map[ed25519.PubKeyEd25519]uint32{}}
 	g.pool.ctx = ctx
 	// the library's arena growth doubles up to the reset points the shim uses
@@ -292,6 +298,10 @@ func Open(devices []int) (*GPU, error) {
 		return nil, err
 	}
 	if err := g.SetOption("ed_key_cap", int64(g.EdKeyCap)); err != nil {
+		g.Close()
+		return nil, err
+	}
+	if err := g.SetOption("ed_keys_wide", int64(g.EdKeysWide)); err != nil { // 0, 6 or 8
 		g.Close()
 		return nil, err
 	}

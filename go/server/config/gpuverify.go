@@ -46,6 +46,10 @@ type GPUVerifyConfig struct {
 	// keys_wide_qw): 0 = 11-bit, then 9-bit when those no longer fit; 11 or 9
 	// = that width only.
 	KeysWideQW int `mapstructure:"keys-wide-qw"`
+	// EdKeysWide: the ed25519 arena also keeps radix-2^6 (6) or radix-2^8 (8)
+	// comb tables for large keyed batches (gv_set_option ed_keys_wide); 0 =
+	// the radix-16 tables only.
+	EdKeysWide int `mapstructure:"ed-keys-wide"`
 	// CacheEntries: the verdict cache (0 = no cache).
 	CacheEntries int `mapstructure:"cache-entries"`
 	// CheckTxWindowTxs / CheckTxWindow: the concurrent-CheckTx accumulation
@@ -64,7 +68,7 @@ type GPUVerifyConfig struct {
 func DefaultGPUVerifyConfig() GPUVerifyConfig {
 	return GPUVerifyConfig{
 		Enable: false, Devices: "", MaxBatch: 1 << 20, CPUBelow: 4, Keyed: true, KeyLoadMin: 4096,
-		KeyCap: 1 << 22, EdKeyCap: 1 << 16, KeyResident: 0, EdKeyResident: 0, KeysWideQW: 0, CacheEntries: 1 << 20,
+		KeyCap: 1 << 22, EdKeyCap: 1 << 16, KeyResident: 0, EdKeyResident: 0, KeysWideQW: 0, EdKeysWide: 0, CacheEntries: 1 << 20,
 		CheckTxWindowTxs: 64, CheckTxWindow: 200 * time.Microsecond, PreVerifyBlocks: true,
 	}
 }
@@ -101,6 +105,8 @@ func (c GPUVerifyConfig) Validate() error {
 		return fmt.Errorf("gpu-verify.ed-key-resident must be 0 (off) or at most ed-key-cap, got %d", c.EdKeyResident)
 	case c.KeysWideQW != 0 && c.KeysWideQW != 9 && c.KeysWideQW != 11:
 		return fmt.Errorf("gpu-verify.keys-wide-qw must be 0, 9 or 11, got %d", c.KeysWideQW)
+	case c.EdKeysWide != 0 && c.EdKeysWide != 6 && c.EdKeysWide != 8:
+		return fmt.Errorf("gpu-verify.ed-keys-wide must be 0, 6 or 8, got %d", c.EdKeysWide)
 	case c.CheckTxWindowTxs < 1 || c.CheckTxWindow < 0:
 		return fmt.Errorf("gpu-verify: bad CheckTx window (%d txs, %v)", c.CheckTxWindowTxs, c.CheckTxWindow)
 	}
@@ -147,6 +153,11 @@ ed-key-resident = {{ .GPUVerify.EdKeyResident }}
 # per key), then 9-bit ones (240 / 128 KiB) when those no longer fit; 11 or 9 =
 # that width only.
 keys-wide-qw = {{ .GPUVerify.KeysWideQW }}
+
+# Wider comb tables of the ed25519 arena for large keyed batches: 0 = off (72 KiB
+# per key), 6 = radix-64 tables beside them (194 KiB more per key), 8 = radix-256
+# ones (576 KiB more).  Taken when the arena next starts from slot 0.
+ed-keys-wide = {{ .GPUVerify.EdKeysWide }}
 
 # Verdict cache entries (0 disables it).
 cache-entries = {{ .GPUVerify.CacheEntries }}

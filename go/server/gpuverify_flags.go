@@ -25,6 +25,7 @@ const (
 	FlagGPUVerifyWindow   = "gpu-verify.checktx-window"
 	FlagGPUVerifyResident = "gpu-verify.key-resident"
 	FlagGPUVerifyEdRes    = "gpu-verify.ed-key-resident"
+	FlagGPUVerifyEdWide   = "gpu-verify.ed-keys-wide"
 )
 
 // AddGPUVerifyFlags registers the flags that override app.toml.
@@ -38,8 +39,9 @@ func AddGPUVerifyFlags(cmd *cobra.Command) {
 	cmd.Flags().Duration(FlagGPUVerifyWindow, d.CheckTxWindow, "Concurrent CheckTx accumulation window")
 	cmd.Flags().Int(FlagGPUVerifyResident, d.KeyResident, "Keep the account-key arena at this many keys (0 = off)")
 	cmd.Flags().Int(FlagGPUVerifyEdRes, d.EdKeyResident, "Keep the ed25519 key arena at this many keys (0 = off)")
+	cmd.Flags().Int(FlagGPUVerifyEdWide, d.EdKeysWide, "Wide ed25519 key tables: 0 (off), 6 or 8 radix bits")
 	for _, f := range []string{FlagGPUVerify, FlagGPUVerifyDevices, FlagGPUVerifyMaxBatch, FlagGPUVerifyCPUBelow,
-		FlagGPUVerifyKeyed, FlagGPUVerifyWindow, FlagGPUVerifyResident, FlagGPUVerifyEdRes} {
+		FlagGPUVerifyKeyed, FlagGPUVerifyWindow, FlagGPUVerifyResident, FlagGPUVerifyEdRes, FlagGPUVerifyEdWide} {
 		_ = viper.BindPFlag(f, cmd.Flags().Lookup(f))
 	}
 }
@@ -73,6 +75,11 @@ func NewGPUVerifier(cfg config.GPUVerifyConfig, logger log.Logger) (gv.Verifier,
 		logger.Error("gpu-verify: keys-wide-qw not applied", "err", err)
 	} else {
 		g.KeysWideQW = cfg.KeysWideQW
+	}
+	if err := g.SetOption("ed_keys_wide", int64(cfg.EdKeysWide)); err != nil {
+		logger.Error("gpu-verify: ed-keys-wide not applied", "err", err)
+	} else {
+		g.EdKeysWide = cfg.EdKeysWide
 	}
 	g.Logger = logger.With("module", "gpuverify")
 	logger.Info("gpu-verify enabled", "devices", cfg.Devices, "keyed", cfg.Keyed, "cpu-below", cfg.CPUBelow)

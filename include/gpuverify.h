@@ -264,6 +264,38 @@ int gv_ed_keys_point(gv_ctx* ctx, size_t n, const uint32_t* slots, uint32_t w, u
 int gv_verify_ed25519_msgs_keyed(gv_ctx* ctx, size_t n, const uint32_t* slot, const uint8_t* sig64,
                                  const uint8_t* msg_blob, const uint64_t* msg_off, const uint32_t* msg_len,
                                  uint8_t* out_ok);
+/* Device-resident keyed ed25519: bit i of d_bits (ceil(n/64) u64 words, the
+ * unused high bits of the last word 0) is exactly
+ * gv_verify_ed25519_msgs_keyed's verdict for item i -- d_slot (n x u32, 4-byte
+ * aligned), d_sig64 (n x 64, 16-byte aligned), d_msg_off u64 / d_msg_len u32
+ * per item, d_msg_blob (may be NULL when every length is 0), all device
+ * memory of dev_slot; GV_EINVAL, and d_bits untouched, for a NULL or
+ * misaligned one.  A slot >= gv_ed_keys_count() gives 0; an empty arena gives
+ * all zeros without a launch that reads the arena.  Every n >= 1 is answered:
+ * up to "ed_lat_max" items on k_ed_lat_sl (one signature per block, the
+ * radix-16 tables), more on k_ed_keyed with the lanes in slot order
+ * ("sort_keys"), on the wide tables (option "ed_keys_wide") when every slot
+ * has them -- "ed_keyed" does not apply: the items never reach the host.
+ * Asynchronous on `stream` (NULL: the library's); its scratch use is ordered
+ * after the previous call's, as for the other gv_dev_* calls.
+ * Arena safety: the call holds the arena's lock while it enqueues and leaves
+ * an event per device behind its last kernel.  gv_ed_keys_load,
+ * gv_ed_keys_replace and a load after gv_ed_keys_reset wait for that event
+ * before they write, move or free arena memory (a growth frees the old arena,
+ * and so does a wide arena that stops): a batch enqueued before a replacement
+ * sees the old keys, one enqueued after it the new ones. */
+int gv_dev_verify_ed25519_msgs_keyed(gv_ctx* ctx, int dev_slot, size_t n, const void* d_slot, const void* d_sig64,
+                                     const void* d_msg_blob, const void* d_msg_off, const void* d_msg_len,
+                                     void* d_bits, void* stream);
+/* Wide ed25519 arena readback (tests, tools): out_enc32 + 32*i = the
+ * canonical encoding of entry (w, j) = j * 2^(rb w) * (-A) of slot slots[i]'s
+ * wide table, rb = "ed_kw_rb" (6: w < 43, j = 1..32; 8: w < 32, j = 1..128);
+ * out_ok[i] = the key's FromBytes verdict.  GV_EINVAL when there is no wide
+ * arena ("ed_kw_rb" 0) or w / j is out of range.  A slot >= "ed_kw_keys":
+ * zeros and 0; a rejected key: a zero encoding and 0.  Reads the first
+ * device's wide arena under gv_ed_keys_point's locks. */
+int gv_ed_keys_wide_point(gv_ctx* ctx, size_t n, const uint32_t* slots, uint32_t w, uint32_t j, uint8_t* out_enc32,
+                          uint8_t* out_ok);
 
 /* Options: "max_batch" (lanes per device launch, default 1<<20, at most
  * 0xFFFFFF00),
@@ -342,6 +374,21 @@ int gv_verify_ed25519_msgs_keyed(gv_ctx* ctx, size_t n, const uint32_t* slot, co
  * "ed_group_r64" (0/1: the grouped route's per-batch ed25519 key tables are
  * radix-64 combs -- 43 windows of 32 entries, 43 additions per [h](-A)
  * instead of 64; same verdicts; default 1, env GV_ED_GROUP_R64),
+ * "ed_keys_wide" (0, 6 or 8, else GV_EINVAL; default 0, env
+ * GV_ED_KEYS_WIDE: gv_ed_keys_load also builds, in an arena of its own beside
+ * the radix-16 one, each key's radix-2^6 comb of -A -- 43 windows of 32
+ * entries, 198,144 B per key -- or radix-2^8 comb -- 32 windows of 128
+ * entries, 576 KiB per key --, and k_ed_keyed batches, host and
+ * device-resident, read them while every slot has them: 43 / 32 additions
+ * per [h](-A) instead of 64; same verdicts.  Taken by an arena started from
+ * slot 0; 0 stops their use at once.  The wide arena doubles up to
+ * "ed_key_cap", is charged to "hbm_budget_mb" and is admitted only while the
+ * device keeps the room the secp256k1 wide arena reserves; a refused growth,
+ * a failed allocation or build frees it and stops it until gv_ed_keys_reset
+ * -- never a gv_ed_keys_load error, every slot keeps its radix-16 table;
+ * gv_ed_keys_replace rebuilds the wide tables of the slots that have them),
+ * "ed_keys_wide_mb" (MiB, 0 = no limit, the default; env GV_ED_KEYS_WIDE_MB:
+ * the wide ed25519 arena is never allocated larger),
  * "ed_btab16" (0/1: k_ed_keyed -- cached keys past "ed_lat_max" and grouped
  * keys -- and the per-item throughput kernels add [s]B from a radix-2^16 comb table of B, j * 65536^w * B for
  * w < 16 and j <= 2^15 (56.6 MB per device, built on first use): 16
@@ -432,7 +479,12 @@ int gv_set_option(gv_ctx* ctx, const char* key, long long val);
  * "kw_arena_ng", the window width and the group count of the first device's
  * wide arena as the last gv_keys_load left it (both 0: no slot has wide
  * tables), and "keys_replaced" / "ed_keys_replaced", the slots
- * gv_keys_replace / gv_ed_keys_replace have rewritten since gv_open.  GV_EINVAL for any other key.  Instrumentation (bench route
+ * gv_keys_replace / gv_ed_keys_replace have rewritten since gv_open, and
+ * "ed_keys_wide" / "ed_keys_wide_mb" with (read only) "ed_kw_rb", the radix
+ * bits of the first device's wide ed25519 arena (0: no slot has wide tables),
+ * "ed_kw_keys", the slots that have them, and "ed_keyed_wide", the keyed
+ * ed25519 batches (host calls: chunks) that ran on wide tables since gv_open.
+ * GV_EINVAL for any other key.  Instrumentation (bench route
  * attribution). */
 int gv_get_option(gv_ctx* ctx, const char* key, long long* val);
 
