@@ -466,6 +466,22 @@ hipError_t gvk_keys_build(const uint8_t* pub33, uint32_t n, uint32_t C, uint32_t
                           uint32_t* kok, uint32_t* kqt2, uint32_t* kzq2, hipStream_t st);
 hipError_t gvk_keys_point(uint32_t n, const uint32_t* slots, const uint32_t* kqt, const uint32_t* kzq, uint32_t kC,
                           const uint32_t* kok, uint32_t kcount, uint8_t* out_xy, uint8_t* out_ok, hipStream_t st);
+// The resident arena's pubkey index (gv_kidx.hip; gv_kidx.h: GV_KIDX_ROW words
+// per key row, a table of tslots words, a power of two, GV_KIDX_EMPTY or a
+// slot).  Keys and slots as the key-table builds take them: n keys for slots
+// base.., or for slots[g] (device, n words, bounded and distinct).
+// gvk_kidx_rows: the chunk's device pub33 -> the slots' key rows.
+// gvk_kidx_put: the slots enter the table (their rows written by an earlier
+// launch); *left_out += the keys that found no word within GV_KIDX_PROBE.
+// gvk_kidx_find: item g's 33 bytes (AoS, unaligned) -> slot_out[g], the lowest
+// slot below count holding exactly those bytes, or GV_KIDX_EMPTY; *miss (may
+// be null) += the items not found.
+hipError_t gvk_kidx_rows(const uint8_t* pub33, uint32_t n, uint32_t base, const uint32_t* slots, uint32_t* rows,
+                         hipStream_t st);
+hipError_t gvk_kidx_put(uint32_t* table, uint32_t tslots, const uint32_t* rows, uint32_t n, uint32_t base,
+                        const uint32_t* slots, uint64_t seed, uint32_t* left_out, hipStream_t st);
+hipError_t gvk_kidx_find(const uint32_t* table, uint32_t tslots, const uint32_t* rows, uint32_t count, uint64_t seed,
+                         const uint8_t* pub33, uint32_t n, uint32_t* slot_out, uint32_t* miss, hipStream_t st);
 hipError_t gvk_debug(int op, uint32_t n, const uint32_t* in, uint32_t* out, hipStream_t st);
 #if GV_STAMP
 hipError_t gvk_stamps_read(uint64_t* host, size_t n_u64);   // diagnostic builds (gv_kernels.hip GV_STAMP)

@@ -1,0 +1,122 @@
+// gv_kidx.h -- the resident key arena's pubkey index (option "keys_index"):
+// the hash, the probe sequence, insert and lookup over one table word per
+// probe.  Shared by the kernels (gv_kidx.hip) and, compiled by g++, by the
+// host model the CPU tests run (tools/fe29/kidx_host.cpp) -- one routine on
+// both sides, as ed_comb_digit in ed_scalar.cuh.
+//
+// A key row is 9 words: the SEC1 prefix byte, then the 8 x words k_unpack
+// writes to in_pfx / in_x (word i = big-endian bytes 29 - 4 i .. 32 - 4 i of
+// the 33, least significant word first).  The row keeps the bytes as sent, a
+// key ParsePubKey rejects included: a lookup matches bytes, not points.
+//
+// The table is T u32 words (T a power of two), GV_KIDX_EMPTY or a slot
+// number; open addressing, linear probing from the key's home word, at most
+// GV_KIDX_PROBE words per insert or lookup.  Contract: a
+// lookup returns a slot only after all 9 words of its row compared equal; a
+// miss is always safe (the batch takes the pub33 route), so an insert that
+// finds no word within the bound leaves the key out, and nothing is ever
+// deleted -- a replacement refills the table from the rows.
+#pragma once
+#include <stdint.h>
+
+#if defined(__HIPCC__)
+#define GV_KIDX_FN __host__ __device__ inline
+#else
+#define GV_KIDX_FN inline
+#endif
+
+#define GV_KIDX_PROBE 64
+#define GV_KIDX_EMPTY 0xFFFFFFFFu
+#define GV_KIDX_ROW 9
+
+// Row of the 33 key bytes at p (any alignment).
+GV_KIDX_FN void gv_kidx_row(const uint8_t* p, uint32_t row[GV_KIDX_ROW]) {
+  row[0] = p[0];
+  for (int i = 0; i < 8; ++i) {
+    const uint8_t* q = p + 1 + 4 * (7 - i);
+    row[1 + i] = ((uint32_t)q[0] << 24) | ((uint32_t)q[1] << 16) | ((uint32_t)q[2] << 8) | (uint32_t)q[3];
+  }
+}
+
+GV_KIDX_FN bool gv_kidx_equal(const uint32_t* a, const uint32_t* b) {
+  bool eq = true;
+  for (int i = 0; i < GV_KIDX_ROW; ++i) eq &= a[i] == b[i];
+  return eq;
+}
+
+// key_hash (gv_kernels.hip) over the prefix and all 8 words, started from the
+// context's 64-bit seed and closed with it: accounts are chosen by whoever
+// sends transactions and the index outlives a batch, so the home word of a
+// key must not be computable without the seed.  (The probe bound, not the
+// hash, is what keeps run time and verdicts independent of the keys.)
+GV_KIDX_FN uint32_t gv_kidx_hash(const uint32_t row[GV_KIDX_ROW], uint64_t seed) {
+  uint64_t h = 0x9E3779B97F4A7C15ull ^ seed;
+  for (int i = 0; i < GV_KIDX_ROW; ++i) {
+    h ^= row[i];
+    h *= 0xFF51AFD7ED558CCDull;
+    h ^= h >> 29;
+  }
+  h ^= (seed << 32) | (seed >> 32);
+  h *= 0xC4CEB9FE1A85EC53ull;
+  h ^= h >> 33;
+  return (uint32_t)(h ^ (h >> 32));
+}
+
+// Probe step i (0 .. GV_KIDX_PROBE - 1) of a key whose hash is h: the table
+// word it looks at.  Linear, wrapping at T = tmask + 1.
+GV_KIDX_FN uint32_t gv_kidx_word(uint32_t h, uint32_t i, uint32_t tmask) { return (h + i) & tmask; }
+
+// Compare-and-swap and minimum on one table word: atomics in a kernel (the
+// table word is the only datum the lanes of a launch share), plain code in
+// the sequential host model.
+GV_KIDX_FN uint32_t gv_kidx_cas(uint32_t* w, uint32_t expect, uint32_t val) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  return atomicCAS(w, expect, val);
+#else
+  const uint32_t cur = *w;
+  if (cur == expect) *w = val;
+  return cur;
+#endif
+}
+GV_KIDX_FN void gv_kidx_min(uint32_t* w, uint32_t val) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  atomicMin(w, val);
+#else
+  if (val < *w) *w = val;
+#endif
+}
+
+// Enter slot `slot` (its row already in rows, GV_KIDX_ROW words per slot).
+// An empty word is taken; a word whose slot holds the same bytes keeps the
+// lower of the two slots (the same key in two slots is legal: the index names
+// the lowest); another key's word sends the probe on.  Returns false when the
+// bound ran out: the key stays out of the index.
+GV_KIDX_FN bool gv_kidx_put(uint32_t* table, uint32_t tmask, const uint32_t* rows, uint32_t slot, uint64_t seed) {
+  const uint32_t* row = rows + (size_t)slot * GV_KIDX_ROW;
+  const uint32_t h = gv_kidx_hash(row, seed);
+  for (uint32_t i = 0; i < GV_KIDX_PROBE; ++i) {
+    uint32_t* w = table + gv_kidx_word(h, i, tmask);
+    const uint32_t cur = gv_kidx_cas(w, GV_KIDX_EMPTY, slot);
+    if (cur == GV_KIDX_EMPTY || cur == slot) return true;
+    if (gv_kidx_equal(rows + (size_t)cur * GV_KIDX_ROW, row)) {
+      gv_kidx_min(w, slot);
+      return true;
+    }
+  }
+  return false;
+}
+
+// The slot whose row equals `row` (the lowest, by gv_kidx_put), or
+// GV_KIDX_EMPTY: an empty word ends the probe, and so does the bound.  A
+// table word at or past `count` (never written by gv_kidx_put over
+// [0, count)) is passed over like another key's.
+GV_KIDX_FN uint32_t gv_kidx_find(const uint32_t* table, uint32_t tmask, const uint32_t* rows, uint32_t count,
+                                 const uint32_t row[GV_KIDX_ROW], uint64_t seed) {
+  const uint32_t h = gv_kidx_hash(row, seed);
+  for (uint32_t i = 0; i < GV_KIDX_PROBE; ++i) {
+    const uint32_t cur = table[gv_kidx_word(h, i, tmask)];
+    if (cur == GV_KIDX_EMPTY) return GV_KIDX_EMPTY;
+    if (cur < count && gv_kidx_equal(rows + (size_t)cur * GV_KIDX_ROW, row)) return cur;
+  }
+  return GV_KIDX_EMPTY;
+}

@@ -30,6 +30,7 @@
 #include <unordered_map>
 #include <future>
 #include <mutex>
+#include <random>
 #include <memory>
 #include <sched.h>
 #include <thread>
@@ -37,6 +38,7 @@
 
 #include "../../include/gpuverify.h"
 #include "gv_kernels.h"
+#include "gv_kidx.h"
 #include "gv_stage.h"
 #include "gv_async.h"
 
@@ -171,6 +173,22 @@ struct Dev {
   size_t kcapw = 0, keysw = 0;
   int kw_ng = 0, kw_qw = 0;
   bool kw_full = false;
+  // the arena's pubkey index (option "keys_index"; gv_kidx.h): per slot the raw
+  // key row (GV_KIDX_ROW words: the prefix and x as k_unpack forms them, the
+  // bytes as loaded -- a rejected key's too), capacity kidx_cap = kcap; the
+  // table of kidx_T words (a power of two >= 2 kcap, >= 512; a slot or
+  // GV_KIDX_EMPTY); kidx_keys leading slots have their row and went through
+  // k_kidx_put.  kidx_on: the running arena took the option at slot 0.
+  // kidx_failed: an allocation was refused or a launch failed (no index until
+  // gv_keys_reset).  kidx_cnt (device): [0] keys k_kidx_put left out since the
+  // last refill, [16] the misses of the lookup in flight; kidx_h: its pinned copy
+  uint32_t *kidx_rows = nullptr, *kidx_tab = nullptr, *kidx_cnt = nullptr, *kidx_h = nullptr;
+  size_t kidx_cap = 0, kidx_T = 0, kidx_keys = 0;
+  bool kidx_on = false, kidx_failed = false;
+  uint64_t kidx_left_out = 0;
+  hipEvent_t kidx_ev[2] = {nullptr, nullptr};     // time_kernels: around the last routed lookup's k_kidx_find
+  hipEvent_t kidx_found = nullptr;                // the last gv_dev_keys_find on the context stream: the next pipelined
+  bool kidx_found_used = false;                   // calls' FRONT streams wait for it (their sort / k_prep read its slots)
   // HBM held by the optional tables (G tables, key arenas) against ctx->hbm_budget
   size_t opt_bytes = 0;
   // ring of per-launch stage events for gv_stage_stats
@@ -774,6 +792,14 @@ struct gv_ctx {
   std::atomic<uint64_t> keys_gen{0};  // gv_keys_reset calls
   std::atomic<uint64_t> keys_replaced{0};   // slots gv_keys_replace rewrote since gv_open ("keys_replaced")
   std::mutex keys_mu;
+  bool keys_index = false;      // gv_keys_load also keeps a device index of the arena, 33 key bytes -> slot (gv_kidx.h),
+                                // and gv_dev_verify_digests / _msgs route a throughput batch whose keys are all
+                                // resident onto the keyed pipeline ("keys_index", GV_KEYS_INDEX): taken by an arena
+                                // started from slot 0; 0 stops its use at once
+  uint64_t kidx_seed = 0;       // the index hash's seed, drawn at gv_open ("keys_index_seed": a test hook)
+  std::atomic<uint64_t> kidx_hit{0}, kidx_miss{0};   // pub33 device batches routed keyed / that fell through
+  std::atomic<uint64_t> kidx_launches{0};            // k_kidx_* launches since gv_open ("keys_index_launches")
+  std::atomic<uint64_t> kidx_find_ns{0};             // time_kernels: the last routed lookup's k_kidx_find
   // ed25519 key arena (gv_ed_keys_load), same on every device
   size_t ed_keys = 0;
   std::atomic<uint64_t> ed_keys_gen{0};
@@ -1051,6 +1077,110 @@ struct KeyArena {
   hipEvent_t ready;
 };
 
+// ---- the resident arena's pubkey index (option "keys_index"; gv_kidx.h)
+// Table words for an arena of `cap` slots: a power of two, at least twice the
+// capacity and 512.
+size_t kidx_table_words(size_t cap) {
+  size_t T = 512;
+  while (T < 2 * cap) T <<= 1;
+  return T;
+}
+size_t kidx_bytes(size_t cap, size_t T) { return (cap * GV_KIDX_ROW + T) * 4; }
+constexpr size_t kKidxCntBytes = 256;
+
+void kidx_free(Dev* d) {
+  if (d->kidx_rows) {                             // one block: the rows, then the table
+    (void)hipFree(d->kidx_rows);
+    d->opt_bytes -= std::min(d->opt_bytes, kidx_bytes(d->kidx_cap, d->kidx_T));
+  }
+  d->kidx_rows = d->kidx_tab = nullptr;
+  d->kidx_cap = d->kidx_T = 0;
+}
+// No index on this device until gv_keys_reset: every call takes the routes it
+// takes without one.
+void kidx_stop(Dev* d) {
+  (void)hipGetLastError();
+  kidx_free(d);
+  d->kidx_failed = true;
+  d->kidx_keys = 0;
+}
+// The index covers the arena as it stands (an empty arena: every key misses).
+bool kidx_live(const gv_ctx* ctx, const Dev* d) {
+  if (!ctx->keys_index || d->kidx_failed || d->kidx_keys != ctx->keys) return false;
+  return ctx->keys == 0 || (d->kidx_on && d->kidx_tab);
+}
+
+// Empty the table and enter slots [0, count) from their rows.
+int kidx_refill(gv_ctx* ctx, Dev* d, size_t count, hipStream_t st) {
+  CK(hipMemsetAsync(d->kidx_tab, 0xFF, d->kidx_T * 4, st));
+  CK(hipMemsetAsync(d->kidx_cnt, 0, 4, st));
+  if (count) {
+    CK(gvk_kidx_put(d->kidx_tab, (uint32_t)d->kidx_T, d->kidx_rows, (uint32_t)count, 0, nullptr, ctx->kidx_seed,
+                    d->kidx_cnt, st));
+    ctx->kidx_launches++;
+  }
+  return GV_OK;
+}
+
+// Rows and table for the arena's capacity (d->kcap), charged to the HBM budget
+// like the other optional tables.  On growth the rows of the first `used`
+// slots are copied and the table refilled from them.
+int kidx_ensure(gv_ctx* ctx, Dev* d, size_t used, hipStream_t st) {
+  if (!d->kidx_cnt) {
+    if (!(d->kidx_cnt = opt_alloc(ctx, d, kKidxCntBytes))) return GV_ENOMEM;
+    CK(hipMemsetAsync(d->kidx_cnt, 0, kKidxCntBytes, st));
+  }
+  if (!d->kidx_h && hipHostMalloc((void**)&d->kidx_h, 64, hipHostMallocDefault) != hipSuccess) {
+    d->kidx_h = nullptr;
+    return GV_ENOMEM;
+  }
+  if (d->kidx_rows && d->kidx_cap >= d->kcap) return GV_OK;
+  const size_t cap = d->kcap, T = kidx_table_words(cap);
+  if (T > (size_t(1) << 31)) return GV_ENOMEM;
+  uint32_t* rows = opt_alloc(ctx, d, kidx_bytes(cap, T));      // one block: the rows, then the table
+  if (!rows) return GV_ENOMEM;
+  uint32_t* tab = rows + cap * GV_KIDX_ROW;
+  used = d->kidx_rows ? std::min(used, d->kidx_keys) : 0;
+  if (used && (hipMemcpyAsync(rows, d->kidx_rows, used * GV_KIDX_ROW * 4, hipMemcpyDeviceToDevice, st) != hipSuccess ||
+               hipStreamSynchronize(st) != hipSuccess)) {
+    opt_free(d, rows, kidx_bytes(cap, T));
+    return GV_EHIP;
+  }
+  if (d->kidx_rows) {
+    (void)hipFree(d->kidx_rows);
+    d->opt_bytes -= std::min(d->opt_bytes, kidx_bytes(d->kidx_cap, d->kidx_T));
+  }
+  d->kidx_rows = rows; d->kidx_tab = tab; d->kidx_cap = cap; d->kidx_T = T;
+  return kidx_refill(ctx, d, used, st);
+}
+
+// The slots of a pub33 device batch (n items, device AoS) into `out` (n
+// words): k_kidx_find on st, then one 4-byte read-back of the miss count and
+// a sync -- what group_keys pays for its key count.  *all: every key was found.
+int kidx_lookup(gv_ctx* ctx, Dev* d, size_t n, const uint8_t* pub, uint32_t* out, hipStream_t st, bool* all) {
+  uint32_t* miss = d->kidx_cnt + 16;
+  CK(hipMemsetAsync(miss, 0, 4, st));
+  const bool timed = ctx->time_kernels;
+  if (timed) {
+    for (hipEvent_t& e : d->kidx_ev)
+      if (!e) CK(hipEventCreate(&e));
+    CK(hipEventRecord(d->kidx_ev[0], st));
+  }
+  CK(gvk_kidx_find(d->kidx_tab, (uint32_t)d->kidx_T, d->kidx_rows, (uint32_t)ctx->keys, ctx->kidx_seed, pub,
+                   (uint32_t)n, out, miss, st));
+  ctx->kidx_launches++;
+  if (timed) CK(hipEventRecord(d->kidx_ev[1], st));
+  CK(hipMemcpyAsync(d->kidx_h, miss, 4, hipMemcpyDeviceToHost, st));
+  CK(hipStreamSynchronize(st));
+  *all = *d->kidx_h == 0;
+  if (timed) {
+    float ms = 0;
+    CK(hipEventElapsedTime(&ms, d->kidx_ev[0], d->kidx_ev[1]));
+    ctx->kidx_find_ns = (uint64_t)(ms * 1e6f);
+  }
+  return GV_OK;
+}
+
 // A chunk past the ramp's first size grows its set straight to a whole
 // max_batch chunk (device scratch, pinned staging, the grouping arena): a
 // regrowth costs tens of ms (hipFree waits for the device, pinning pages), so
@@ -1067,7 +1197,7 @@ size_t grow_items(const gv_ctx* ctx, size_t C) {
 int launch(gv_ctx* ctx, Dev* d, Set* s, size_t n, const uint8_t* pub, const uint8_t* sig, const uint8_t* dig,
            const uint8_t* blob, const uint64_t* off, const uint32_t* len, uint64_t* bits_out,
            hipStream_t st, const uint32_t* kslot = nullptr, uint8_t* out8 = nullptr, hipStream_t st_ecm = nullptr,
-           const KeyArena* ka = nullptr, bool no_group = false) {
+           const KeyArena* ka = nullptr, bool no_group = false, bool index = false) {
   if (n == 0 || n > kMaxItems) return GV_EINVAL;
   const size_t C = round_up(n, 256);
   int rc = ensure_cap(s, grow_items(ctx, C));
@@ -1090,6 +1220,17 @@ int launch(gv_ctx* ctx, Dev* d, Set* s, size_t n, const uint8_t* pub, const uint
   b.bits = bits_out;
   b.inv_m = ctx->inv_small ? 0u : (uint32_t)GV_INV_M;
   const uint32_t* kzq2 = d->kzq2;
+  // index (gv_dev_verify_digests / _msgs, option "keys_index"): a throughput
+  // batch whose keys are all resident runs as the keyed call with those slots
+  // would -- the slots looked up into the head of the set's Q-table region
+  // (free on the keyed pipeline; plan_sort starts past them).  Any miss: the
+  // batch goes on as without the index.
+  bool via_index = false;
+  if (index && pub && !kslot && n > ctx->lat_max && ctx->keys && kidx_live(ctx, d)) {
+    if ((rc = kidx_lookup(ctx, d, n, pub, s->qtab, st, &via_index))) return rc;
+    if (via_index) kslot = s->qtab;
+    (via_index ? ctx->kidx_hit : ctx->kidx_miss)++;
+  }
   if (kslot && ka) {                            // a host slice's grouped keys
     b.pub33 = nullptr;
     b.kslot = kslot; b.kqt = ka->kqt; b.kzq = ka->kzq; b.kok = ka->kok;
@@ -1119,7 +1260,7 @@ int launch(gv_ctx* ctx, Dev* d, Set* s, size_t n, const uint8_t* pub, const uint
   }
   // k6 group tables (a grouped slice's chunks) are read by k_ecmult_k6 only:
   // such a chunk takes the pipeline whatever its size
-  const bool small = n <= (kslot ? ctx->lat_max_keyed : ctx->lat_max) && !b.k6;
+  const bool small = n <= (kslot ? ctx->lat_max_keyed : ctx->lat_max) && !b.k6 && !via_index;
   const bool pipelined = st_ecm != nullptr && !small;
   // the resident arena's k6 tables (every slot in use has them): throughput
   // batches on k_ecmult_k6; the small-batch kernels keep the k4 tables
@@ -1184,7 +1325,7 @@ int launch(gv_ctx* ctx, Dev* d, Set* s, size_t n, const uint8_t* pub, const uint
       CK(hipEventRecord(rs[5], st));
     }
   } else {
-    uint32_t* sort_base = s->qtab;                // keyed: the Q-table region is free
+    uint32_t* sort_base = s->qtab + (via_index ? C : 0);   // keyed: the Q-table region is free (past the looked-up slots)
     if (!kslot && pub && ctx->group_keys && !no_group && n >= ctx->group_min) {
       rc = group_keys(ctx, d, s, b, n, st, &sort_base);
       if (rc) return rc;
@@ -1250,6 +1391,9 @@ int dev_run(gv_ctx* ctx, Dev* d, void* stream, size_t n, bool keyed, F&& fn) {
   hipStream_t hs = d->hi_st[ctx->two_ladders ? j : 0];
   hipEvent_t& hd = d->hi_done[ctx->two_ladders ? j : 0];
   if (d->plain_used) CK(hipStreamWaitEvent(hs, d->plain_done, 0));
+  // a gv_dev_keys_find enqueued on the context stream before this call: its
+  // slots may be this call's d_slot, which the front kernels read
+  if (d->kidx_found_used) CK(hipStreamWaitEvent(d->lo_st[j], d->kidx_found, 0));
   d->bits_wait = (ctx->two_ladders && d->bits_used) ? d->bits_ev[j ^ 1] : nullptr;
   d->bits_rec = ctx->two_ladders ? d->bits_ev[j] : nullptr;
   const int rc = fn(&d->set[j], d->lo_st[j], hs);
@@ -2085,6 +2229,13 @@ int gv_open(const int* dev_ids, int n_dev, gv_ctx** out) {
     const int v = atoi(ew);
     if (v == 0 || v == 6 || v == 8) ctx->ed_keys_wide = v;
   }
+  if (const char* ki = getenv("GV_KEYS_INDEX")) ctx->keys_index = !strcmp(ki, "1");
+  {                                             // the index hash's seed: not computable from outside the process
+    std::random_device rd;
+    ctx->kidx_seed = ((uint64_t)rd() << 32) ^ (uint64_t)rd() ^
+                     (uint64_t)std::chrono::steady_clock::now().time_since_epoch().count() * 0x9E3779B97F4A7C15ull ^
+                     (uint64_t)(uintptr_t)ctx;
+  }
   if (const char* em = getenv("GV_ED_KEYS_WIDE_MB")) {
     const long long v = atoll(em);
     if (v >= 0 && v <= (long long)(SIZE_MAX >> 20)) ctx->ed_keys_wide_bytes = (size_t)v << 20;
@@ -2203,6 +2354,10 @@ void gv_close(gv_ctx* ctx) {
     for (uint32_t* p : {d->ektab, d->ekpub, d->ekok, d->ektabw}) if (p) (void)hipFree(p);
     if (d->edkd_s) (void)hipFree(d->edkd_s);
     if (d->edkd_last) (void)hipEventDestroy(d->edkd_last);
+    for (uint32_t* p : {d->kidx_rows, d->kidx_cnt}) if (p) (void)hipFree(p);   // (the table rides behind the rows)
+    if (d->kidx_h) (void)hipHostFree(d->kidx_h);
+    for (hipEvent_t e : d->kidx_ev) if (e) (void)hipEventDestroy(e);
+    if (d->kidx_found) (void)hipEventDestroy(d->kidx_found);
     if (d->edl_h) (void)hipHostFree(d->edl_h);
     for (uint32_t* q : {d->edg_ktab, d->edg_kpub, d->edg_kok}) if (q) (void)hipFree(q);
     if (d->ed_h_count) (void)hipHostFree(d->ed_h_count);
@@ -2305,7 +2460,7 @@ int gv_dev_verify_digests(gv_ctx* ctx, int dev_slot, size_t n, const void* d_pub
   CK(hipSetDevice(d->id));
   return dev_run(ctx, d, stream, n, false, [&](Set* s, hipStream_t st, hipStream_t se) {
     return launch(ctx, d, s, n, (const uint8_t*)d_pub33, (const uint8_t*)d_sig64, (const uint8_t*)d_dig32, nullptr,
-                  nullptr, nullptr, (uint64_t*)d_bits, st, nullptr, nullptr, se);
+                  nullptr, nullptr, (uint64_t*)d_bits, st, nullptr, nullptr, se, nullptr, false, true);
   });
 }
 
@@ -2321,7 +2476,7 @@ int gv_dev_verify_msgs(gv_ctx* ctx, int dev_slot, size_t n, const void* d_pub33,
   return dev_run(ctx, d, stream, n, false, [&](Set* s, hipStream_t st, hipStream_t se) {
     return launch(ctx, d, s, n, (const uint8_t*)d_pub33, (const uint8_t*)d_sig64, nullptr,
                   (const uint8_t*)d_msg_blob, (const uint64_t*)d_msg_off, (const uint32_t*)d_msg_len,
-                  (uint64_t*)d_bits, st, nullptr, nullptr, se);
+                  (uint64_t*)d_bits, st, nullptr, nullptr, se, nullptr, false, true);
   });
 }
 
@@ -2476,6 +2631,53 @@ int build_wide(gv_ctx* ctx, Dev* d, Set* s, hipStream_t st, const uint8_t* pub33
   return GV_OK;
 }
 
+// The index rows of the n keys pub33 (host) for slots base.. (slots: as
+// build_wide's), in the build chunks' staging; put: the chunk's slots also
+// enter the table (an append; a replacement refills it afterwards).  The rows
+// come from the bytes as given: read_back_pub33 below cannot stand in, it
+// turns a rejected key's prefix into 00.
+int kidx_write(gv_ctx* ctx, Dev* d, Set* s, hipStream_t st, const uint8_t* pub33, size_t n, size_t base,
+               const uint32_t* slots, bool put) {
+  int rc;
+  for (size_t c0 = 0; c0 < n; c0 += ctx->max_batch) {
+    const size_t cn = std::min(ctx->max_batch, n - c0);
+    const size_t C = round_up(cn, 256);
+    if ((rc = ensure_cap(s, C))) return rc;
+    if ((rc = set_acquire(s, st))) return rc;
+    CK(hipMemcpyAsync(s->d_in, pub33 + c0 * 33, cn * 33, hipMemcpyHostToDevice, st));
+    const uint32_t* d_slots = nullptr;
+    if (slots) CK(stage_slots(s, C, slots + c0, cn, st, &d_slots));
+    const uint32_t b0 = slots ? 0u : (uint32_t)(base + c0);
+    CK(gvk_kidx_rows(s->d_in, (uint32_t)cn, b0, d_slots, d->kidx_rows, st));
+    ctx->kidx_launches++;
+    if (put) {
+      CK(gvk_kidx_put(d->kidx_tab, (uint32_t)d->kidx_T, d->kidx_rows, (uint32_t)cn, b0, d_slots, ctx->kidx_seed,
+                      d->kidx_cnt, st));
+      ctx->kidx_launches++;
+    }
+    if ((rc = set_release(s, st))) return rc;
+    CK(hipStreamSynchronize(st));              // the caller's pub33 chunk is read by then
+  }
+  return GV_OK;
+}
+// The keys the table's last fill and the appends since left out.
+int kidx_read_left_out(Dev* d, hipStream_t st) {
+  CK(hipMemcpyAsync(d->kidx_h + 8, d->kidx_cnt, 4, hipMemcpyDeviceToHost, st));
+  CK(hipStreamSynchronize(st));
+  d->kidx_left_out = d->kidx_h[8];
+  return GV_OK;
+}
+// gv_keys_load's part: rows and table entries of the new slots base.., after
+// their tables.
+int kidx_load(gv_ctx* ctx, Dev* d, Set* s, hipStream_t st, const uint8_t* pub33, size_t n, size_t base) {
+  int rc;
+  const bool had = d->kidx_rows && d->kidx_cap >= d->kcap;
+  if ((rc = kidx_ensure(ctx, d, base, st))) return rc;
+  if (base == 0 && had && (rc = kidx_refill(ctx, d, 0, st))) return rc;   // an arena restarted: the table is cleared
+  if ((rc = kidx_write(ctx, d, s, st, pub33, n, base, nullptr, true))) return rc;
+  return kidx_read_left_out(d, st);
+}
+
 // The compressed keys of slots 0..n-1 read back from the k4 tables (affine
 // 1*Q of each slot); a slot whose key ParsePubKey rejected gets a prefix
 // byte it rejects again (0x00), so a rebuild keeps its verdict.
@@ -2536,7 +2738,14 @@ int gv_keys_load(gv_ctx* ctx, size_t n, const uint8_t* pub33, uint32_t* slot_out
     if (base == 0) {                            // after gv_keys_reset the slots are rewritten from 0
       d->keys6 = d->keysw = 0;
       d->kw_full = false;
+      d->kidx_keys = 0;
+      d->kidx_left_out = 0;
+      d->kidx_failed = false;
+      d->kidx_on = ctx->keys_index;             // the arena takes the option here
     }
+    // an earlier load that failed on a later device left this one's index ahead
+    // of the arena (rows of keys no slot holds): no index until gv_keys_reset
+    if (d->kidx_keys > base) kidx_stop(d);
     // the k6 tables too when their G tables exist (or can be built) and the
     // arena has room for them (else k4 only: the k4 route serves the slots)
     int rc = ensure_gtab4(ctx, d, s, st);
@@ -2596,6 +2805,12 @@ int gv_keys_load(gv_ctx* ctx, size_t n, const uint8_t* pub33, uint32_t* slot_out
         d->keysw = base + n;
       }
     }
+    // the pubkey index, while every earlier slot is in it: a refused
+    // allocation or a failed launch only stops it on this device
+    if (ctx->keys_index && d->kidx_on && !d->kidx_failed && d->kidx_keys == base) {
+      if (kidx_load(ctx, d, s, st, pub33, n, base) != GV_OK) kidx_stop(d);
+      else d->kidx_keys = base + n;
+    }
   }
   ctx->keys = base + n;
   for (size_t i = 0; i < n; ++i) slot_out[i] = (uint32_t)(base + i);
@@ -2647,6 +2862,21 @@ int gv_keys_replace(gv_ctx* ctx, size_t n, const uint32_t* slots, const uint8_t*
                       : build_k4k6(ctx, d, s, st, pb, m, 0, sl, which == 0, which == 1);
       if (rc) return rc;
     }
+    // the index (whatever the option says now: its rows must not go stale):
+    // the named slots' rows, then the table refilled from every row -- the
+    // old bytes leave it, and the order of replacements does not matter
+    if (d->kidx_rows && d->kidx_keys && !d->kidx_failed) {
+      fs.clear();
+      fp.clear();
+      for (size_t i = 0; i < n; ++i)
+        if (slots[i] < d->kidx_keys) {
+          fs.push_back(slots[i]);
+          fp.insert(fp.end(), pub33 + i * 33, pub33 + (i + 1) * 33);
+        }
+      if ((!fs.empty() && kidx_write(ctx, d, s, st, fp.data(), fs.size(), 0, fs.data(), false) != GV_OK) ||
+          kidx_refill(ctx, d, d->kidx_keys, st) != GV_OK || kidx_read_left_out(d, st) != GV_OK)
+        kidx_stop(d);
+    }
   }
   ctx->keys_replaced.fetch_add(n);
   return GV_OK;
@@ -2658,6 +2888,12 @@ int gv_keys_reset(gv_ctx* ctx) {
   std::lock_guard<std::mutex> kl(ctx->keys_mu);
   ctx->keys = 0;
   ctx->keys_gen.fetch_add(1);
+  for (Dev* d : ctx->devs) {                    // the index is empty with the arena; a stopped one may start again
+    std::lock_guard<std::mutex> lk(d->mu);
+    d->kidx_keys = 0;
+    d->kidx_left_out = 0;
+    d->kidx_failed = false;
+  }
   return GV_OK;
 }
 
@@ -3327,6 +3563,68 @@ int gv_keys_point(gv_ctx* ctx, size_t n, const uint32_t* slots, uint8_t* out_xy6
   return rc;
 }
 
+int gv_keys_find(gv_ctx* ctx, size_t n, const uint8_t* pub33, uint32_t* slot_out) {
+  if (!ctx) return GV_EINVAL;
+  if (n == 0) return GV_OK;
+  if (!pub33 || !slot_out || n > kMaxItems) return GV_EINVAL;
+  Dev* d = ctx->devs[0];
+  std::lock_guard<std::mutex> lk(d->mu);
+  if (!kidx_live(ctx, d)) return GV_EINVAL;     // cannot tell (not: not resident)
+  if (ctx->keys == 0) {
+    memset(slot_out, 0xFF, n * 4);
+    return GV_OK;
+  }
+  CK(hipSetDevice(d->id));
+  hipStream_t st = d->set[0].st;
+  uint8_t* buf = nullptr;
+  const size_t pb = round_up(n * 33, 256);
+  if (hipMalloc(&buf, pb + n * 4) != hipSuccess) return GV_ENOMEM;
+  int rc = GV_OK;
+  if (hipMemcpyAsync(buf, pub33, n * 33, hipMemcpyHostToDevice, st) != hipSuccess ||
+      gvk_kidx_find(d->kidx_tab, (uint32_t)d->kidx_T, d->kidx_rows, (uint32_t)ctx->keys, ctx->kidx_seed, buf,
+                    (uint32_t)n, (uint32_t*)(buf + pb), nullptr, st) != hipSuccess ||
+      hipMemcpyAsync(slot_out, buf + pb, n * 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
+      hipStreamSynchronize(st) != hipSuccess)
+    rc = GV_EHIP;
+  ctx->kidx_launches++;
+  (void)hipFree(buf);
+  return rc;
+}
+
+int gv_dev_keys_find(gv_ctx* ctx, int dev_slot, size_t n, const void* d_pub33, void* d_slot_out, void* stream) {
+  if (!ctx) return GV_EINVAL;
+  if (dev_slot < 0 || dev_slot >= (int)ctx->devs.size()) return GV_ENODEV;
+  if (n == 0) return GV_OK;
+  if (!d_pub33 || !d_slot_out || ((uintptr_t)d_slot_out & 3) || n > kMaxItems) return GV_EINVAL;
+  Dev* d = ctx->devs[dev_slot];
+  std::lock_guard<std::mutex> lk(d->mu);
+  if (!kidx_live(ctx, d)) return GV_EINVAL;
+  CK(hipSetDevice(d->id));
+  if (!stream && !d->kidx_found) CK(hipEventCreateWithFlags(&d->kidx_found, hipEventDisableTiming));
+  // n = 0 to dev_run: on the context stream the lookup is ordered like a small
+  // batch -- after every pipelined ladder, and the next ladder after it; the
+  // front kernels of the pipelined calls that follow (which read d_slot_out
+  // when it is their d_slot) wait for kidx_found
+  return dev_run(ctx, d, stream, 0, false, [&](Set*, hipStream_t st, hipStream_t) -> int {
+    if (ctx->keys == 0) {
+      CK(hipMemsetAsync(d_slot_out, 0xFF, n * 4, st));
+      if (!stream) {
+        CK(hipEventRecord(d->kidx_found, st));
+        d->kidx_found_used = true;
+      }
+      return GV_OK;
+    }
+    CK(gvk_kidx_find(d->kidx_tab, (uint32_t)d->kidx_T, d->kidx_rows, (uint32_t)ctx->keys, ctx->kidx_seed,
+                     (const uint8_t*)d_pub33, (uint32_t)n, (uint32_t*)d_slot_out, nullptr, st));
+    ctx->kidx_launches++;
+    if (!stream) {
+      CK(hipEventRecord(d->kidx_found, st));
+      d->kidx_found_used = true;
+    }
+    return GV_OK;
+  });
+}
+
 int gv_verify_digests_keyed(gv_ctx* ctx, size_t n, const uint32_t* slot, const uint8_t* sig64,
                             const uint8_t* dig32, uint8_t* out_ok) {
   if (n && (!slot || !dig32)) return GV_EINVAL;
@@ -3381,6 +3679,12 @@ int gv_get_option(gv_ctx* ctx, const char* key, long long* val) {
               {"ed_keys_wide", ctx->ed_keys_wide},
               {"ed_keys_wide_mb", (long long)(ctx->ed_keys_wide_bytes >> 20)},
               {"ed_keyed_wide", (long long)ctx->ed_keyed_wide.load()},   // read-only: keyed batches / chunks on wide tables
+              {"keys_index", ctx->keys_index},
+              {"keys_index_hit", (long long)ctx->kidx_hit.load()},     // read-only: pub33 device batches routed keyed
+              {"keys_index_miss", (long long)ctx->kidx_miss.load()},   // read-only: ... that fell through on a miss
+              {"keys_index_launches", (long long)ctx->kidx_launches.load()},   // read-only: k_kidx_* launches so far
+              {"keys_index_find_ns", (long long)ctx->kidx_find_ns.load()},     // read-only: the last routed lookup's
+                                                                               // kernel ("time_kernels" on)
               {"kw_qw", GV_KW_QW},                   // read-only: the wide arena's window width (build)
               {"kwn_qw", GV_KWN ? GV_KWN_QW : 0}};   // read-only: its narrow width (build; 0: not compiled)
   // read-only: the first device's wide arena as gv_keys_load left it -- its
@@ -3391,6 +3695,20 @@ int gv_get_option(gv_ctx* ctx, const char* key, long long* val) {
     std::lock_guard<std::mutex> lk(d->mu);
     const bool live = d->kqtw && d->keysw;
     *val = !live ? 0 : !strcmp(key, "kw_arena_qw") ? d->kw_qw : d->kw_ng;
+    return GV_OK;
+  }
+  // read-only: the first device's pubkey index -- whether it covers the arena,
+  // the slots in it, the keys its probe bound left out, its table words
+  if (!strcmp(key, "keys_index_live") || !strcmp(key, "keys_index_keys") || !strcmp(key, "keys_index_left_out") ||
+      !strcmp(key, "keys_index_words")) {
+    if (ctx->devs.empty()) return GV_EINVAL;
+    Dev* d = ctx->devs[0];
+    std::lock_guard<std::mutex> lk(d->mu);
+    const bool has = d->kidx_tab && !d->kidx_failed;
+    *val = !strcmp(key, "keys_index_live")       ? (long long)kidx_live(ctx, d)
+           : !strcmp(key, "keys_index_keys")     ? (long long)(has ? d->kidx_keys : 0)
+           : !strcmp(key, "keys_index_left_out") ? (long long)(has ? d->kidx_left_out : 0)
+                                                 : (long long)(has ? d->kidx_T : 0);
     return GV_OK;
   }
   // read-only: the first device's wide ed25519 arena as gv_ed_keys_load left
@@ -3519,6 +3837,23 @@ int gv_set_option(gv_ctx* ctx, const char* key, long long val) {
       d->bits_used = false;
     }
     ctx->keys_wide = (int)val;
+  } else if (!strcmp(key, "keys_index")) {
+    // taken by an arena started from slot 0 from now on (a running arena keeps
+    // what it has until gv_keys_reset); 0 stops the use of the index at once
+    if (val != 0 && val != 1) return GV_EINVAL;
+    std::vector<std::unique_lock<std::mutex>> held;
+    for (Dev* d : ctx->devs) held.emplace_back(d->mu);
+    for (Dev* d : ctx->devs) {
+      CK(hipSetDevice(d->id));
+      for (hipStream_t t : d->hi_st) CK(hipStreamSynchronize(t));
+      d->bits_used = false;
+    }
+    ctx->keys_index = val != 0;
+  } else if (!strcmp(key, "keys_index_seed")) {
+    // test hook: the index hash's seed, while no key is in the arena
+    std::lock_guard<std::mutex> kl(ctx->keys_mu);
+    if (ctx->keys != 0) return GV_EINVAL;
+    ctx->kidx_seed = (uint64_t)val;
   } else if (!strcmp(key, "kg")) {
     if (!kg_layout_ok((int)val)) return GV_EINVAL;
     std::vector<std::unique_lock<std::mutex>> held;

@@ -247,6 +247,12 @@ type GPU struct {
 	// radix-16 tables only.  Applies to an arena started from slot 0
 	// (default 0, env GV_ED_KEYS_WIDE).
 	EdKeysWide int
+	// KeysIndex: the library also keeps a device-side index of the key arena,
+	// 33 key bytes -> slot (gv_set_option "keys_index"): KeysFind answers from
+	// it, and device-resident pub33 batches whose keys are all resident run on
+	// the arena's tables.  Applies to an arena started from slot 0 (default
+	// false, env GV_KEYS_INDEX=1).
+	KeysIndex bool
 	// Logger, when set, reports every call that fell back to the CPU.
 	Logger Logger
 
@@ -289,6 +295,7 @@ func Open(devices []int) (*GPU, error) {
 	g := &GPU{ctx: ctx, CPUBelow: DefaultCPUBelow, Keyed: true, KeyLoadMin: DefaultKeyLoadMin,
 		KeyCap: envInt("GV_KEY_CAP", DefaultKeyCap), EdKeyCap: envInt("GV_ED_KEY_CAP", DefaultEdKeyCap),
 		KeysWideQW: envInt("GV_KEYS_WIDE_QW", 0), EdKeysWide: envInt("GV_ED_KEYS_WIDE", 0),
+		KeysIndex: envInt("GV_KEYS_INDEX", 0) == 1,
 		slots: map[secp256k1.PubKeySecp256k1]uint32{}, edSlots: map[ed25519.PubKeyEd25519]uint32{}}
 	g.pool.ctx = ctx
 	// the library's arena growth doubles up to the reset points the shim uses
@@ -308,6 +315,12 @@ func Open(devices []int) (*GPU, error) {
 	if err := g.SetOption("keys_wide_qw", int64(g.KeysWideQW)); err != nil {
 		g.Close()
 		return nil, err
+	}
+	if g.KeysIndex {
+		if err := g.SetOption("keys_index", 1); err != nil {
+			g.Close()
+			return nil, err
+		}
 	}
 	return g, nil
 }
@@ -860,6 +873,35 @@ func (g *GPU) KeysReplace(slots []uint32, pub33 []byte) error {
 		return fmt.Errorf("gpuverify: gv_keys_replace: %d", int(rc))
 	}
 	return nil
+}
+
+// KeyNotFound is what KeysFind returns for a key no arena slot holds.
+const KeyNotFound = ^uint32(0)
+
+// KeysFind asks the device which arena slot holds each key (gv_keys_find,
+// option "keys_index"): slots[i] is the lowest slot holding exactly the bytes
+// pub33[33*i:], or KeyNotFound.  Unlike the shim's own key -> slot map the
+// answer is what the device holds -- it survives a restart of the caller and
+// can check that map.  An error means "cannot tell" (no live index on this
+// context), never "not resident".
+func (g *GPU) KeysFind(pub33 []byte) ([]uint32, error) {
+	if len(pub33)%33 != 0 {
+		return nil, fmt.Errorf("gpuverify: KeysFind: %d key bytes", len(pub33))
+	}
+	n := len(pub33) / 33
+	if n == 0 {
+		return nil, nil
+	}
+	pb := g.newCBuf(len(pub33))
+	sb := g.newCBuf(4 * n)
+	defer func() { pb.free(); sb.free() }()
+	copy(pb.b, pub33)
+	if rc := C.gv_keys_find(g.ctx, C.size_t(n), (*C.uint8_t)(pb.p), (*C.uint32_t)(sb.p)); rc != 0 {
+		return nil, fmt.Errorf("gpuverify: gv_keys_find: %d", int(rc))
+	}
+	slots := make([]uint32, n)
+	copy(slots, (*[maxBatchBytes / 4]uint32)(sb.p)[:n:n])
+	return slots, nil
 }
 
 // ResetKeys empties the key arena and the slot map together (a slot number

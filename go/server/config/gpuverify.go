@@ -50,6 +50,10 @@ type GPUVerifyConfig struct {
 	// comb tables for large keyed batches (gv_set_option ed_keys_wide); 0 =
 	// the radix-16 tables only.
 	EdKeysWide int `mapstructure:"ed-keys-wide"`
+	// KeysIndex: the library keeps a device-side pubkey -> slot index of the
+	// key arena (gv_set_option keys_index; gv_keys_find): device-resident
+	// pub33 batches whose keys are all resident run on the arena's tables.
+	KeysIndex bool `mapstructure:"keys-index"`
 	// CacheEntries: the verdict cache (0 = no cache).
 	CacheEntries int `mapstructure:"cache-entries"`
 	// CheckTxWindowTxs / CheckTxWindow: the concurrent-CheckTx accumulation
@@ -68,7 +72,7 @@ type GPUVerifyConfig struct {
 func DefaultGPUVerifyConfig() GPUVerifyConfig {
 	return GPUVerifyConfig{
 		Enable: false, Devices: "", MaxBatch: 1 << 20, CPUBelow: 4, Keyed: true, KeyLoadMin: 4096,
-		KeyCap: 1 << 22, EdKeyCap: 1 << 16, KeyResident: 0, EdKeyResident: 0, KeysWideQW: 0, EdKeysWide: 0, CacheEntries: 1 << 20,
+		KeyCap: 1 << 22, EdKeyCap: 1 << 16, KeyResident: 0, EdKeyResident: 0, KeysWideQW: 0, EdKeysWide: 0, KeysIndex: false, CacheEntries: 1 << 20,
 		CheckTxWindowTxs: 64, CheckTxWindow: 200 * time.Microsecond, PreVerifyBlocks: true,
 	}
 }
@@ -158,6 +162,12 @@ keys-wide-qw = {{ .GPUVerify.KeysWideQW }}
 # per key), 6 = radix-64 tables beside them (194 KiB more per key), 8 = radix-256
 # ones (576 KiB more).  Taken when the arena next starts from slot 0.
 ed-keys-wide = {{ .GPUVerify.EdKeysWide }}
+
+# Device-side index of the account-key arena (key bytes -> slot, 44 bytes of GPU
+# memory per slot of capacity): pub33 batches staged on the GPU run on the
+# resident tables when all their keys are resident.  Taken when the arena next
+# starts from slot 0.
+keys-index = {{ .GPUVerify.KeysIndex }}
 
 # Verdict cache entries (0 disables it).
 cache-entries = {{ .GPUVerify.CacheEntries }}

@@ -26,6 +26,7 @@ const (
 	FlagGPUVerifyResident = "gpu-verify.key-resident"
 	FlagGPUVerifyEdRes    = "gpu-verify.ed-key-resident"
 	FlagGPUVerifyEdWide   = "gpu-verify.ed-keys-wide"
+	FlagGPUVerifyKeysIdx  = "gpu-verify.keys-index"
 )
 
 // AddGPUVerifyFlags registers the flags that override app.toml.
@@ -40,8 +41,10 @@ func AddGPUVerifyFlags(cmd *cobra.Command) {
 	cmd.Flags().Int(FlagGPUVerifyResident, d.KeyResident, "Keep the account-key arena at this many keys (0 = off)")
 	cmd.Flags().Int(FlagGPUVerifyEdRes, d.EdKeyResident, "Keep the ed25519 key arena at this many keys (0 = off)")
 	cmd.Flags().Int(FlagGPUVerifyEdWide, d.EdKeysWide, "Wide ed25519 key tables: 0 (off), 6 or 8 radix bits")
+	cmd.Flags().Bool(FlagGPUVerifyKeysIdx, d.KeysIndex, "Device-side pubkey index of the account-key arena")
 	for _, f := range []string{FlagGPUVerify, FlagGPUVerifyDevices, FlagGPUVerifyMaxBatch, FlagGPUVerifyCPUBelow,
-		FlagGPUVerifyKeyed, FlagGPUVerifyWindow, FlagGPUVerifyResident, FlagGPUVerifyEdRes, FlagGPUVerifyEdWide} {
+		FlagGPUVerifyKeyed, FlagGPUVerifyWindow, FlagGPUVerifyResident, FlagGPUVerifyEdRes, FlagGPUVerifyEdWide,
+		FlagGPUVerifyKeysIdx} {
 		_ = viper.BindPFlag(f, cmd.Flags().Lookup(f))
 	}
 }
@@ -80,6 +83,13 @@ func NewGPUVerifier(cfg config.GPUVerifyConfig, logger log.Logger) (gv.Verifier,
 		logger.Error("gpu-verify: ed-keys-wide not applied", "err", err)
 	} else {
 		g.EdKeysWide = cfg.EdKeysWide
+	}
+	if cfg.KeysIndex {
+		if err := g.SetOption("keys_index", 1); err != nil {
+			logger.Error("gpu-verify: keys-index not applied", "err", err)
+		} else {
+			g.KeysIndex = true
+		}
 	}
 	g.Logger = logger.With("module", "gpuverify")
 	logger.Info("gpu-verify enabled", "devices", cfg.Devices, "keyed", cfg.Keyed, "cpu-below", cfg.CPUBelow)

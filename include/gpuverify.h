@@ -181,6 +181,34 @@ uint64_t gv_keys_generation(const gv_ctx* ctx);
  * and 0).  Reads the first device's arena. */
 int gv_keys_point(gv_ctx* ctx, size_t n, const uint32_t* slots, uint8_t* out_xy64, uint8_t* out_ok);
 
+/* The arena's pubkey index (option "keys_index", below): which slot holds a
+ * key.  With the option on, gv_keys_load and gv_keys_replace keep on every
+ * device, beside the tables, each slot's 33 bytes as they were given (a key
+ * ParsePubKey rejects too) and a hash table over them; a lookup returns a
+ * slot only after comparing all 33 bytes with that slot's, so verifying by
+ * the slot it returns gives exactly the pub33 verdict.  The index may be
+ * incomplete -- a key whose probe finds no free word within 64 steps is left
+ * out ("keys_index_left_out") and answers as not resident -- but it never
+ * names a slot with other bytes.
+ * gv_keys_find: slot_out[i] = the lowest slot holding exactly the bytes
+ * pub33 + 33*i, or 0xFFFFFFFF.  Host buffers, the first device's index, under
+ * gv_keys_point's locks.  GV_OK with every entry 0xFFFFFFFF on an empty arena;
+ * n == 0 is GV_OK; GV_EINVAL when ctx, pub33 or slot_out is NULL or the
+ * context has no live index ("keys_index" 0, an arena started without it, an
+ * index its device's HBM budget refused): "cannot tell", which a caller must
+ * not take for "not resident". */
+int gv_keys_find(gv_ctx* ctx, size_t n, const uint8_t* pub33, uint32_t* slot_out);
+/* The device-resident form, on dev_slot's index: d_pub33 = n x 33 key bytes
+ * (any alignment), d_slot_out = n u32 words (4-byte aligned; NULL or
+ * misaligned: GV_EINVAL and nothing is written).  Asynchronous on `stream`
+ * (NULL: the context stream, ordered with the other calls on it -- after
+ * every call enqueued before it, and the calls enqueued after it, the front
+ * kernels of pipelined ones included, after it); its output can be passed
+ * straight to gv_dev_verify_digests_keyed on the same stream (both NULL, or
+ * the same caller stream; across two streams the caller orders them).
+ * Same results and errors as gv_keys_find; GV_ENODEV for a bad dev_slot. */
+int gv_dev_keys_find(gv_ctx* ctx, int dev_slot, size_t n, const void* d_pub33, void* d_slot_out, void* stream);
+
 /* VerifyBytes with the key given by slot: out_ok[i] is exactly what
  * gv_verify_digests / gv_verify_msgs return with pub33 = the key loaded into
  * slot[i]; a slot >= gv_keys_count() gives false.  Same batching, errors and
@@ -454,6 +482,29 @@ int gv_ed_keys_wide_point(gv_ctx* ctx, size_t n, const uint32_t* slots, uint32_t
  * "keys_wide_mb" (MiB: the wide arena is never allocated larger than this --
  * a growth whose new arena would pass it is refused and the arena moves down
  * the layouts as above; 0 = no limit, the default; env GV_KEYS_WIDE_MB),
+ * "keys_index" (0/1: gv_keys_load and gv_keys_replace also keep the arena's
+ * pubkey index on every device -- 36 B of key bytes per slot of capacity and
+ * a table of at least two 4-byte words per slot, charged to "hbm_budget_mb";
+ * a refused or failed allocation stops the index on that device until
+ * gv_keys_reset and is never a gv_keys_load error -- gv_keys_find /
+ * gv_dev_keys_find answer from it, and gv_dev_verify_digests /
+ * gv_dev_verify_msgs look a batch past "lat_max" up in it (one kernel and a
+ * 4-byte read-back): when every key of the batch is resident the batch runs
+ * on the keyed throughput pipeline as gv_dev_verify_digests_keyed would with
+ * those slots -- the same arena tables, sort and ladder, no per-call key
+ * parsing or table build; one exception: a routed batch always takes the
+ * throughput pipeline, also in the band "lat_max" < n <= "lat_max_keyed"
+ * (8193..14336 by default) where the keyed call itself takes the keyed
+ * small-batch kernel -- and on any miss exactly as without the option; same
+ * verdicts either way.
+ * With it on, those two calls read the arena: the rule of the keyed calls,
+ * "loading must not race keyed verifies of the same context", then covers
+ * them too (gv_keys_load and gv_keys_replace drain the pipelined ladders
+ * before they write).  Taken by an arena started from slot 0, a running
+ * arena keeps what it has until gv_keys_reset; 0 stops the use of the index
+ * at once; default 0, env GV_KEYS_INDEX=1),
+ * "keys_index_seed" (test hook: the 64-bit seed of the index hash, drawn per
+ * context at gv_open; GV_EINVAL unless the arena is empty),
  * "key_cap" / "ed_key_cap" (the callers' reset points of the secp256k1 /
  * ed25519 key arenas: an arena grows by doubling up to it and exactly past it;
  * defaults GV_KEY_CAP / GV_ED_KEY_CAP, env of the same names; the Go shim sets
@@ -483,7 +534,16 @@ int gv_set_option(gv_ctx* ctx, const char* key, long long val);
  * "ed_keys_wide" / "ed_keys_wide_mb" with (read only) "ed_kw_rb", the radix
  * bits of the first device's wide ed25519 arena (0: no slot has wide tables),
  * "ed_kw_keys", the slots that have them, and "ed_keyed_wide", the keyed
- * ed25519 batches (host calls: chunks) that ran on wide tables since gv_open.
+ * ed25519 batches (host calls: chunks) that ran on wide tables since gv_open,
+ * and "keys_index" with (read only) "keys_index_live" (1: the first device's
+ * index covers the arena as it stands), "keys_index_keys" (the slots in it),
+ * "keys_index_left_out" (keys the probe bound kept out of the table),
+ * "keys_index_words" (its table's words), "keys_index_hit" /
+ * "keys_index_miss" (pub33 device batches routed onto the keyed pipeline /
+ * that fell through on a miss, since gv_open), "keys_index_launches" (index
+ * kernels launched since gv_open: 0 while the option has never been on) and
+ * "keys_index_find_ns" (the last routed lookup's kernel, HIP events, with
+ * "time_kernels" on).
  * GV_EINVAL for any other key.  Instrumentation (bench route
  * attribution). */
 int gv_get_option(gv_ctx* ctx, const char* key, long long* val);
