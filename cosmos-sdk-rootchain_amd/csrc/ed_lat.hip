@@ -896,8 +896,111 @@ __global__ __launch_bounds__(256) void k_ed_keys_wide_point(u32 n, const u32* sl
   out_ok[g] = ok ? 1u : 0u;
 }
 
+// -------------------------------------------------------------- k_debug_esl
+// Test hook (gv_debug_sl_op, ops GV_SLOP_ED_*): gv_lat.hip's k_debug_sl for
+// the ed25519 constants -- one item per 64-lane wave, operands replicated in
+// its four rows, raw limbs in, row 0's sixteen lanes out (gv_kernels.h).
+GV_DEV u32 desl_same_rows(u32 v, u32 lane) {
+  return __ballot(v != (u32)__shfl((int)v, (int)(lane & 15u), 64)) == 0ull ? 1u : 0u;
+}
+
+__global__ __launch_bounds__(64) void k_debug_esl(int op, const u32* in, u32* out) {
+  const fslk k = efsl_consts();
+  const u32 lane = threadIdx.x, L = k.L, row = lane >> 4;
+  const u32* it = in + (size_t)blockIdx.x * GV_SL_IN;
+  u32* o = out + (size_t)blockIdx.x * GV_SL_OUT;
+  u32 a[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) a[j] = L < 9u ? it[9 * j + (int)L] : 0u;
+  const u32 flags = it[GV_SL_IN - 1];
+  const bool neg = (flags & GV_SLF_NEG) != 0u, pre = (flags & GV_SLF_PRE) != 0u;
+  u32 w[16];                                          // operand 0 as words (GV_SLF_WORDS)
+#pragma unroll
+  for (int j = 0; j < 16; ++j) w[j] = it[j];
+  u32 r[4] = {0u, 0u, 0u, 0u};
+  u32 flag = 0u, known = 1u;
+  gesl P = {a[0], a[1], a[2], a[3]};
+  const bool wop = op == GV_SLOP_ED_FROM_WORDS || op == GV_SLOP_ED_DECODE_STRICT || op == GV_SLOP_ED_DECODE_LENIENT ||
+                   op == GV_SLOP_ED_DIGITS;
+  if (wop != ((flags & GV_SLF_WORDS) != 0u)) op = -1;   // words where the op takes limbs, or the reverse: not run
+  switch (op) {
+    case GV_SLOP_ED_MUL: r[0] = fsl_mul(a[0], a[1], k); break;
+    case GV_SLOP_ED_SQR: r[0] = fsl_sqr(a[0], k); break;
+    case GV_SLOP_ED_NORM: r[0] = fsl_norm(a[0], k); break;
+    case GV_SLOP_ED_SUB: r[0] = fsl_norm(a[0] + k.bias - a[1], k); break;
+    case GV_SLOP_ED_IS_ZERO: flag = efsl_is_zero(a[0]) ? 1u : 0u; break;
+    case GV_SLOP_ED_TO_WORDS: {
+      u32 t[8];
+      efsl_to_words(t, a[0]);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) r[0] = L == (u32)j ? t[j] : r[0];
+      break;
+    }
+    case GV_SLOP_ED_FROM_WORDS: r[0] = efsl_from_words(w, k); break;
+    case GV_SLOP_ED_POW22523: r[0] = efsl_pow22523(a[0], k); break;
+    case GV_SLOP_ED_DECODE_STRICT: flag = efsl_decode_strict(r[0], r[1], w, k) ? 1u : 0u; break;
+    case GV_SLOP_ED_DECODE_LENIENT: flag = efsl_decode_lenient(r[0], r[1], w, k) ? 1u : 0u; break;
+    case GV_SLOP_GESL_ADD_CACHED: {
+      gesl R;
+      gesl_add_cached(R, P, a[4], a[5], a[6], a[7], neg, k);
+      P = R;
+      break;
+    }
+    case GV_SLOP_GESL_ADD_PRE: {
+      gesl R;
+      gesl_add_pre(R, P, a[4], a[5], a[6], neg, k);
+      P = R;
+      break;
+    }
+    case GV_SLOP_GESL_ADD: {
+      const gesl Q = {a[4], a[5], a[6], a[7]};
+      gesl R;
+      gesl_add(R, P, Q, efsl_const(kEd2D, k), k);
+      P = R;
+      break;
+    }
+    case GV_SLOP_GE4_DOUBLE: ge4_double(P, row, k); break;
+    case GV_SLOP_GE4_ADD_CACHED: ge4_add_cached(P, a[4], a[5], a[6], a[7], pre, neg, row, k); break;
+    case GV_SLOP_GE4_ADD: {
+      const gesl Q = {a[4], a[5], a[6], a[7]};
+      ge4_add(P, Q, efsl_const(kEd2D, k), row, k);
+      break;
+    }
+    case GV_SLOP_ED_DIGITS: {                         // edl_hash_digits' last step: lane i holds digit i
+      u32 h[8];
+      sc_reduce512(h, w);
+      const uint64_t car = sc_radix16_carries(h);
+      const u32 nib = (h[lane >> 3] >> (4u * (lane & 7u))) & 15u;
+      const int cin = lane > 0u ? (int)((car >> (lane - 1u)) & 1u) : 0;
+      const int cout = lane < 63u ? (int)((car >> lane) & 1u) : 0;
+      o[lane] = (u32)((int)nib + cin - 16 * cout);
+      if (lane < 16u) o[64 + lane] = lane == GV_SLS_ROWS || lane == GV_SLS_KNOWN ? 1u : 0u;
+      return;
+    }
+    default: known = 0u; break;
+  }
+  if (op >= GV_SLOP_GESL_ADD_CACHED && op <= GV_SLOP_GE4_ADD) {
+    r[0] = P.X; r[1] = P.Y; r[2] = P.Z; r[3] = P.T;
+  }
+  u32 same = 1u;
+#pragma unroll
+  for (int s = 0; s < 4; ++s) same &= desl_same_rows(r[s], lane);
+  same &= desl_same_rows(flag, lane);
+  if (row == 0u) {
+#pragma unroll
+    for (int s = 0; s < 4; ++s) o[16 * s + (int)L] = r[s];
+    o[64 + L] = L == GV_SLS_FLAG ? flag : L == GV_SLS_ROWS ? same : L == GV_SLS_KNOWN ? known : 0u;
+  }
+}
+
 }  // namespace ed
 }  // namespace gv
+
+extern "C" hipError_t gvk_debug_esl(int op, uint32_t n, const uint32_t* in, uint32_t* out, hipStream_t st) {
+  if (n == 0) return hipSuccess;
+  hipLaunchKernelGGL(gv::ed::k_debug_esl, dim3(n), dim3(64), 0, st, op, in, out);
+  return hipGetLastError();
+}
 
 extern "C" hipError_t gvk_ed_keys_wide_point(uint32_t n, const uint32_t* slots, uint32_t w, uint32_t j, int rb,
                                              const uint32_t* ktab, const uint32_t* kok, uint32_t kcount,

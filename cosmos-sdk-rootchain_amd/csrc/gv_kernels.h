@@ -483,6 +483,38 @@ hipError_t gvk_kidx_put(uint32_t* table, uint32_t tslots, const uint32_t* rows, 
 hipError_t gvk_kidx_find(const uint32_t* table, uint32_t tslots, const uint32_t* rows, uint32_t count, uint64_t seed,
                          const uint8_t* pub33, uint32_t n, uint32_t* slot_out, uint32_t* miss, hipStream_t st);
 hipError_t gvk_debug(int op, uint32_t n, const uint32_t* in, uint32_t* out, hipStream_t st);
+
+// gv_debug_sl_op: the limb-sliced layers, one item per 64-lane wave.
+// in: GV_SL_IN words per item -- operand j's nine raw limbs at 9j..9j+8
+// (j < 8: gesl_add_cached and gesl_add take eight field elements), flags in
+// the last word; ops taking canonical words read them from word 0 on and
+// need GV_SLF_WORDS.  out: GV_SL_OUT words per item -- four result slots of
+// the sixteen lanes of row 0, then sixteen status words (GV_SLS_*).
+#define GV_SL_IN 80
+#define GV_SL_OUT 80
+#define GV_SLF_NEG 1u
+#define GV_SLF_PRE 2u
+#define GV_SLF_INF_A 4u
+#define GV_SLF_INF_B 8u
+#define GV_SLF_WORDS 16u
+#define GV_SLS_FLAG 0u      // boolean result (is_zero, decode ok)
+#define GV_SLS_INF 1u       // infinity out
+#define GV_SLS_ROWS 2u      // every result the same in the wave's four rows
+#define GV_SLS_KNOWN 3u     // the kernel knows the op
+enum {
+  // secp256k1 constants (fsl_consts): k_debug_sl in gv_lat.hip
+  GV_SLOP_MUL = 0, GV_SLOP_SQR, GV_SLOP_MUL_PLUS8, GV_SLOP_MUL_PLUSB, GV_SLOP_MUL2, GV_SLOP_NORM, GV_SLOP_SUB,
+  GV_SLOP_NEG, GV_SLOP_IS_ZERO, GV_SLOP_FROM_WORDS, GV_SLOP_LOAD_WORDS, GV_SLOP_TO_WORDS, GV_SLOP_SQRT,
+  GV_SLOP_ROWS_ALL, GV_SLOP_GJSL_DOUBLE, GV_SLOP_GJSL_ADD_SCALED, GV_SLOP_GJSL_ADD_GEJ, GV_SLOP_GJ4_DOUBLE,
+  GV_SLOP_GJ4_ADD, GV_SLOP_GJ4_ADD_GEJ, GV_SLOP_GJ4_ADD_AFFINE, GV_SLOP_MODINV, GV_SLOP_SECP_END,
+  // ed25519 constants (efsl_consts): k_debug_esl in ed_lat.hip
+  GV_SLOP_ED_MUL = 64, GV_SLOP_ED_SQR, GV_SLOP_ED_NORM, GV_SLOP_ED_SUB, GV_SLOP_ED_IS_ZERO, GV_SLOP_ED_TO_WORDS,
+  GV_SLOP_ED_FROM_WORDS, GV_SLOP_ED_POW22523, GV_SLOP_ED_DECODE_STRICT, GV_SLOP_ED_DECODE_LENIENT,
+  GV_SLOP_GESL_ADD_CACHED, GV_SLOP_GESL_ADD_PRE, GV_SLOP_GESL_ADD, GV_SLOP_GE4_DOUBLE, GV_SLOP_GE4_ADD_CACHED,
+  GV_SLOP_GE4_ADD, GV_SLOP_ED_DIGITS, GV_SLOP_ED_END
+};
+hipError_t gvk_debug_sl(int op, uint32_t n, const uint32_t* in, uint32_t* out, hipStream_t st);    // gv_lat.hip
+hipError_t gvk_debug_esl(int op, uint32_t n, const uint32_t* in, uint32_t* out, hipStream_t st);   // ed_lat.hip
 #if GV_STAMP
 hipError_t gvk_stamps_read(uint64_t* host, size_t n_u64);   // diagnostic builds (gv_kernels.hip GV_STAMP)
 #endif

@@ -1885,7 +1885,134 @@ __global__ __launch_bounds__(256) void k_verify_lat16_kw(const gvk_lat b) {
   }
 }
 
+// --------------------------------------------------------------- k_debug_sl
+// Test hook (gv_debug_sl_op in the C-ABI, ops GV_SLOP_* below 64): ONE item
+// per 64-lane wave, its operands replicated in the wave's four rows as the
+// row-parallel rounds keep them.  in: GV_SL_IN words per item, operand j's
+// nine RAW limbs (not reduced, any value < 2^32) at words 9j..9j+8, flags in
+// the last word; out: GV_SL_OUT words per item, four result slots of all
+// sixteen lanes of row 0 and sixteen status words.
+GV_DEV u32 dsl_same_rows(u32 v, u32 lane) {           // v the same in the four rows (wave-uniform 0 / 1)
+  return __ballot(v != (u32)__shfl((int)v, (int)(lane & 15u), 64)) == 0ull ? 1u : 0u;
+}
+
+__global__ __launch_bounds__(64) void k_debug_sl(int op, const u32* in, u32* out) {
+  const fslk k = fsl_consts();
+  const u32 lane = threadIdx.x, L = k.L, row = lane >> 4;
+  const u32* it = in + (size_t)blockIdx.x * GV_SL_IN;
+  u32* o = out + (size_t)blockIdx.x * GV_SL_OUT;
+  u32 a[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) a[j] = L < 9u ? it[9 * j + (int)L] : 0u;
+  const u32 flags = it[GV_SL_IN - 1];
+  const bool ainf = (flags & GV_SLF_INF_A) != 0u, binf = (flags & GV_SLF_INF_B) != 0u;
+  u32 w[8];                                           // operand 0 as words (GV_SLF_WORDS)
+#pragma unroll
+  for (int j = 0; j < 8; ++j) w[j] = it[j];
+  u32 r[4] = {0u, 0u, 0u, 0u};
+  u32 flag = 0u, inf_out = 0u, known = 1u;
+  const bool wop = op == GV_SLOP_FROM_WORDS || op == GV_SLOP_LOAD_WORDS || op == GV_SLOP_MODINV;
+  if (wop != ((flags & GV_SLF_WORDS) != 0u)) op = -1;   // words where the op takes limbs, or the reverse: not run
+  switch (op) {
+    case GV_SLOP_MUL: r[0] = fsl_mul(a[0], a[1], k); break;
+    case GV_SLOP_SQR: r[0] = fsl_sqr(a[0], k); break;
+    case GV_SLOP_MUL_PLUS8: r[0] = fsl_mul_plus(a[0], a[1], k.big8 - ((u64)a[2] << 3), k); break;
+    case GV_SLOP_MUL_PLUSB: r[0] = fsl_mul_plus(a[0], a[1], (u64)(k.bias - a[2]), k); break;
+    case GV_SLOP_MUL2: r[0] = fsl_mul2(a[0], a[1], a[2], a[3], k); break;
+    case GV_SLOP_NORM: r[0] = fsl_norm(a[0], k); break;
+    case GV_SLOP_SUB: r[0] = fsl_sub(a[0], a[1], k); break;
+    case GV_SLOP_NEG: r[0] = fsl_neg(a[0], k); break;
+    case GV_SLOP_IS_ZERO: flag = fsl_is_zero(a[0]) ? 1u : 0u; break;
+    case GV_SLOP_FROM_WORDS: r[0] = fsl_from_words(w, k); break;
+    case GV_SLOP_LOAD_WORDS: r[0] = fsl_load_words(it, k); break;
+    case GV_SLOP_TO_WORDS: {
+      u32 t[8];
+      fsl_to_words(t, a[0]);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) r[0] = L == (u32)j ? t[j] : r[0];
+      break;
+    }
+    case GV_SLOP_SQRT: r[0] = fsl_sqrt_candidate(a[0], k); break;
+    case GV_SLOP_ROWS_ALL: {                          // row j holds operand j
+      const rows4 q = rows_all(row == 0u ? a[0] : row == 1u ? a[1] : row == 2u ? a[2] : a[3]);
+      r[0] = q.r[0]; r[1] = q.r[1]; r[2] = q.r[2]; r[3] = q.r[3];
+      break;
+    }
+    case GV_SLOP_GJSL_DOUBLE: {
+      gjsl P = {a[0], a[1], a[2]}, Q;
+      gjsl_double(Q, P, k);
+      r[0] = Q.x; r[1] = Q.y; r[2] = Q.z;
+      break;
+    }
+    case GV_SLOP_GJSL_ADD_SCALED: {                   // a[0..2] += (a[3], a[4]) scaled by a[5]
+      gjsl P = {a[0], a[1], a[2]};
+      bool inf = false;
+      gjsl_add_scaled(P, inf, a[3], a[4], a[5], k);
+      r[0] = P.x; r[1] = P.y; r[2] = P.z; inf_out = inf ? 1u : 0u;
+      break;
+    }
+    case GV_SLOP_GJSL_ADD_GEJ: {
+      gjsl P = {a[0], a[1], a[2]}, Q = {a[3], a[4], a[5]}, R;
+      bool inf = false;
+      gjsl_add_gej(R, inf, P, ainf, Q, binf, k);
+      r[0] = R.x; r[1] = R.y; r[2] = R.z; inf_out = inf ? 1u : 0u;
+      break;
+    }
+    case GV_SLOP_GJ4_DOUBLE: {
+      gjsl P = {a[0], a[1], a[2]};
+      gj4_double(P, row, k);
+      r[0] = P.x; r[1] = P.y; r[2] = P.z;
+      break;
+    }
+    case GV_SLOP_GJ4_ADD: {
+      gjsl P = {a[0], a[1], a[2]};
+      bool inf = false;
+      gj4_add(P, inf, a[3], a[4], row, k);
+      r[0] = P.x; r[1] = P.y; r[2] = P.z; inf_out = inf ? 1u : 0u;
+      break;
+    }
+    case GV_SLOP_GJ4_ADD_GEJ: {
+      gjsl P = {a[0], a[1], a[2]}, Q = {a[3], a[4], a[5]};
+      bool inf = ainf;
+      gj4_add_gej(P, inf, Q, binf, row, k);
+      r[0] = P.x; r[1] = P.y; r[2] = P.z; inf_out = inf ? 1u : 0u;
+      break;
+    }
+    case GV_SLOP_GJ4_ADD_AFFINE: {
+      gjsl P = {a[0], a[1], a[2]};
+      bool inf = ainf;
+      gj4_add_affine(P, inf, a[3], a[4], row, k);
+      r[0] = P.x; r[1] = P.y; r[2] = P.z; inf_out = inf ? 1u : 0u;
+      break;
+    }
+    case GV_SLOP_MODINV: {
+      u32 t[8];
+      s30_modinv_sl(t, w, k);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) r[0] = L == (u32)j ? t[j] : r[0];
+      break;
+    }
+    default: known = 0u; break;
+  }
+  u32 same = 1u;
+#pragma unroll
+  for (int s = 0; s < 4; ++s) same &= dsl_same_rows(r[s], lane);
+  same &= dsl_same_rows(flag | (inf_out << 1), lane);
+  if (row == 0u) {
+#pragma unroll
+    for (int s = 0; s < 4; ++s) o[16 * s + (int)L] = r[s];
+    o[64 + L] = L == GV_SLS_FLAG ? flag : L == GV_SLS_INF ? inf_out : L == GV_SLS_ROWS ? same
+              : L == GV_SLS_KNOWN ? known : 0u;
+  }
+}
+
 }  // namespace gv
+
+extern "C" hipError_t gvk_debug_sl(int op, uint32_t n, const uint32_t* in, uint32_t* out, hipStream_t st) {
+  if (n == 0) return hipSuccess;
+  hipLaunchKernelGGL(gv::k_debug_sl, dim3(n), dim3(64), 0, st, op, in, out);
+  return hipGetLastError();
+}
 
 extern "C" hipError_t gvk_verify_lat16(const gvk_lat* b, hipStream_t st) {
   const uint32_t blocks = (b->n + GV_LAT16_SIGS - 1) / GV_LAT16_SIGS;

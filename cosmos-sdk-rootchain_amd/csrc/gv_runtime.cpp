@@ -4098,4 +4098,30 @@ int gv_debug_op(gv_ctx* ctx, int dev_slot, int op, size_t n, const uint32_t* in,
   return rc;
 }
 
+int gv_debug_sl_op(gv_ctx* ctx, int dev_slot, int op, size_t n, const uint32_t* in, uint32_t* out) {
+  if (!ctx || dev_slot < 0 || dev_slot >= (int)ctx->devs.size() || !in || !out) return GV_EINVAL;
+  const bool secp = op >= 0 && op < GV_SLOP_SECP_END, ed = op >= GV_SLOP_ED_MUL && op < GV_SLOP_ED_END;
+  if (!secp && !ed) return GV_EINVAL;
+  if (n == 0) return GV_OK;
+  if (n > kMaxItems) return GV_EINVAL;
+  Dev* d = ctx->devs[dev_slot];
+  std::lock_guard<std::mutex> lk(d->mu);
+  CK(hipSetDevice(d->id));
+  hipStream_t st = d->set[0].st;
+  const size_t bin = n * GV_SL_IN * 4, bout = n * GV_SL_OUT * 4;
+  uint32_t *din = nullptr, *dout = nullptr;
+  CK(hipMalloc(&din, bin));
+  if (hipMalloc(&dout, bout) != hipSuccess) { (void)hipFree(din); return GV_ENOMEM; }
+  int rc = GV_OK;
+  if (hipMemcpyAsync(din, in, bin, hipMemcpyHostToDevice, st) != hipSuccess ||
+      hipMemsetAsync(dout, 0, bout, st) != hipSuccess ||
+      (secp ? gvk_debug_sl : gvk_debug_esl)(op, (uint32_t)n, din, dout, st) != hipSuccess ||
+      hipMemcpyAsync(out, dout, bout, hipMemcpyDeviceToHost, st) != hipSuccess ||
+      hipStreamSynchronize(st) != hipSuccess)
+    rc = GV_EHIP;
+  (void)hipFree(din);
+  (void)hipFree(dout);
+  return rc;
+}
+
 }  // extern "C"

@@ -48,8 +48,21 @@ EXPORTED_SYMBOLS = (
     "gv_ed_keys_load", "gv_ed_keys_reset", "gv_ed_keys_count", "gv_ed_keys_generation", "gv_verify_ed25519_msgs_keyed",
     "gv_ed_keys_replace", "gv_ed_keys_point", "gv_dev_verify_ed25519_msgs_keyed", "gv_ed_keys_wide_point",
     "gv_submit_digests", "gv_submit_digests_keyed", "gv_submit_msgs", "gv_submit_msgs_keyed", "gv_wait",
-    "gv_keys_find", "gv_dev_keys_find",
+    "gv_keys_find", "gv_dev_keys_find", "gv_debug_sl_op",
 )
+
+# gv_debug_sl_op (csrc/gv_kernels.h): words per item, flags, status words, op codes
+SL_IN, SL_OUT = 80, 80
+SLF_NEG, SLF_PRE, SLF_INF_A, SLF_INF_B, SLF_WORDS = 1, 2, 4, 8, 16
+SLS_FLAG, SLS_INF, SLS_ROWS, SLS_KNOWN = 0, 1, 2, 3
+SLOP = {name: i for i, name in enumerate((
+    "mul", "sqr", "mul_plus8", "mul_plusb", "mul2", "norm", "sub", "neg", "is_zero", "from_words", "load_words",
+    "to_words", "sqrt", "rows_all", "gjsl_double", "gjsl_add_scaled", "gjsl_add_gej", "gj4_double", "gj4_add",
+    "gj4_add_gej", "gj4_add_affine", "modinv"))}
+SLOP.update({name: 64 + i for i, name in enumerate((
+    "ed_mul", "ed_sqr", "ed_norm", "ed_sub", "ed_is_zero", "ed_to_words", "ed_from_words", "ed_pow22523",
+    "ed_decode_strict", "ed_decode_lenient", "gesl_add_cached", "gesl_add_pre", "gesl_add", "ge4_double",
+    "ge4_add_cached", "ge4_add", "ed_digits"))})
 
 
 class GpuVerifyError(RuntimeError):
@@ -126,6 +139,8 @@ def load(path: str = LIB_PATH):
     L.gv_strerror.restype = ctypes.c_char_p
     L.gv_debug_op.argtypes = [vp, i32, i32, sz, vp, vp]
     L.gv_debug_op.restype = i32
+    L.gv_debug_sl_op.argtypes = [vp, i32, i32, sz, vp, vp]
+    L.gv_debug_sl_op.restype = i32
     L.gv_dev_alloc.argtypes = [vp, i32, sz, ctypes.POINTER(vp)]
     L.gv_dev_alloc.restype = i32
     L.gv_dev_free.argtypes = [vp, i32, vp]
@@ -710,6 +725,18 @@ class Verifier:
         assert words.shape == (n, 16)
         out = np.zeros((n, 16), dtype=np.uint32)
         _check(self._L.gv_debug_op(self._ctx, slot, op, n, _ptr(words), _ptr(out)), "gv_debug_op")
+        return out
+
+    def debug_sl_op(self, op, words: np.ndarray, slot: int = 0) -> np.ndarray:
+        """One row-sliced operation (SLOP name or code) per item: words n x SL_IN
+        (operand j's raw limbs at 9j..9j+8, flags last) -> n x SL_OUT (four
+        slots of row 0's sixteen lanes, then the status words)."""
+        words = np.ascontiguousarray(words, dtype=np.uint32)
+        n = words.shape[0]
+        assert words.shape == (n, SL_IN)
+        out = np.zeros((n, SL_OUT), dtype=np.uint32)
+        code = SLOP[op] if isinstance(op, str) else int(op)
+        _check(self._L.gv_debug_sl_op(self._ctx, slot, code, n, _ptr(words), _ptr(out)), "gv_debug_sl_op")
         return out
 
 

@@ -647,6 +647,19 @@ const char* gv_strerror(int code);
  * host arrays).  Used by the GPU unit tests only. */
 int gv_debug_op(gv_ctx* ctx, int dev_slot, int op, size_t n, const uint32_t* in, uint32_t* out);
 
+/* Test hook for the limb-sliced layers of the small-batch kernels
+ * (secp_fsl.cuh, ed_fsl.cuh, the row-parallel rounds): one item per 64-lane
+ * wave, operands replicated in its four 16-lane rows.  in = n x 80 words:
+ * operand j's nine raw limbs (unreduced) at words 9j..9j+8, j < 8 (the
+ * cached-point additions take eight field elements), word 79 = flags (1 neg,
+ * 2 pre, 4 / 8 first / second input at infinity, 16 words, not limbs: the op
+ * reads canonical words from word 0 on).  out = n x 80 words: four result
+ * slots of 16 words (all sixteen lanes of row 0), then 16 status words
+ * (0 boolean result, 1 infinity out, 2 the four rows agree, 3 op known).
+ * Op codes: GV_SLOP_* in csrc/gv_kernels.h.  GV_EINVAL for an unknown op.
+ * Used by the GPU unit tests only. */
+int gv_debug_sl_op(gv_ctx* ctx, int dev_slot, int op, size_t n, const uint32_t* in, uint32_t* out);
+
 #ifdef __cplusplus
 }
 #endif

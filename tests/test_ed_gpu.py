@@ -13,6 +13,7 @@ import random
 import numpy as np
 import pytest
 
+import ed_msglen
 import ed_openssl as OSSL
 import gpuverify as gvm
 
@@ -96,6 +97,20 @@ def test_random_batch_vs_openssl(ver, sched):
     got = ver.verify_batch_ed25519(pub, sig, msgs)
     assert np.array_equal(got.astype(bool), np.array(want)), np.nonzero(got.astype(bool) != np.array(want))[0][:10]
     assert 0.6 < got.mean() < 0.9
+    assert (ver.route_stats()["ed_lat"] > r0) == (sched == "small")
+
+
+def test_message_lengths_every_block_count(ver, sched):
+    """1 to 18 SHA-512 blocks, each boundary bracketed (ed_msglen.LENGTHS):
+    k_ed_lat_unc runs sha512_wave with up to 16 blocks and switches to the
+    byte stream at 1967 / 1968 message bytes; the throughput kernels hash the
+    same lengths lane by lane."""
+    pubs, key, msgs, sig, want = ed_msglen.items()
+    pub = np.array([np.frombuffer(pubs[k], np.uint8) for k in key]).reshape(-1, 32)
+    r0 = ver.route_stats()["ed_lat"]
+    got = ver.verify_batch_ed25519(pub, sig, msgs)
+    bad = np.nonzero(got != want)[0]
+    assert bad.size == 0, [(len(msgs[i]), int(want[i])) for i in bad[:10]]
     assert (ver.route_stats()["ed_lat"] > r0) == (sched == "small")
 
 

@@ -5,7 +5,9 @@ vector (oracle/ed25519_ref.py verdicts: non-canonical and small-order keys,
 keys off the curve, S >= L, sig[63] & 224, non-canonical R, R' = identity),
 the RFC 8032 vectors and OpenSSL on random batches, on both schedules (the
 sliced small-batch kernel k_ed_lat_sl and, past "ed_lat_max", the throughput
-kernels), at message lengths around the kernel's 2,048-byte LDS staging."""
+kernels), at every SHA-512 block count from 1 to 18 (ed_msglen.py) and at
+message lengths around the kernel's LDS staging (2,048 padded bytes: messages
+up to 1,967 bytes)."""
 import json
 import os
 import random
@@ -14,6 +16,7 @@ import time
 import numpy as np
 import pytest
 
+import ed_msglen
 import ed_openssl as OSSL
 import gpuverify as gvm
 
@@ -107,12 +110,63 @@ def test_random_batches_vs_openssl_both_schedules(ver):
         assert np.array_equal(got.astype(bool), want), (n, np.nonzero(got.astype(bool) != want)[0][:10])
 
 
+def msglen_keyed(v, lat_max):
+    """ed_msglen's items against keys cached in v: verdicts and the expected ones"""
+    pubs, key, msgs, sig, want = ed_msglen.items()
+    slots = v.ed_keys_load(np.array([np.frombuffer(p, np.uint8) for p in pubs]).reshape(-1, 32))
+    v.set_option("ed_lat_max", lat_max)
+    try:
+        got = v.verify_batch_ed25519_keyed(np.ascontiguousarray(slots[key], np.uint32), sig, msgs)
+    finally:
+        v.set_option("ed_lat_max", 2048)
+    return got, want, [len(m) for m in msgs]
+
+
+def test_message_lengths_every_block_count_sliced(ver):
+    """k_ed_lat_sl: sha512_wave at 1 to 16 blocks, the stream path at 17 and
+    18, every block boundary bracketed (1967 / 1968 is the path switch)."""
+    got, want, lens = msglen_keyed(ver, 2048)
+    bad = np.nonzero(got != want)[0]
+    assert bad.size == 0, [(lens[i], int(want[i])) for i in bad[:10]]
+
+
+@pytest.mark.parametrize("b16", [1, 0])
+def test_message_lengths_every_block_count_keyed_throughput(ver, b16):
+    """k_ed_keyed<4> (ed_lat_max = 0) on the same lengths, [s]B from either table."""
+    ver.set_option("ed_btab16", b16)
+    try:
+        got, want, lens = msglen_keyed(ver, 0)
+    finally:
+        ver.set_option("ed_btab16", 1)
+    bad = np.nonzero(got != want)[0]
+    assert bad.size == 0, [(lens[i], int(want[i])) for i in bad[:10]]
+
+
+@pytest.mark.parametrize("rb", [6, 8])
+def test_message_lengths_every_block_count_wide_arena(rb):
+    """k_ed_keyed<6> / <8> on the wide comb tables ("ed_keys_wide", set before
+    the first key is loaded), and the sliced kernel of the same context."""
+    v = gvm.Verifier([0])
+    try:
+        v.set_option("ed_keys_wide", rb)
+        for lat_max in (0, 2048):
+            got, want, lens = msglen_keyed(v, lat_max)
+            assert v.get_option("ed_kw_rb") == rb
+            bad = np.nonzero(got != want)[0]
+            assert bad.size == 0, (lat_max, [(lens[i], int(want[i])) for i in bad[:10]])
+    finally:
+        v.close()
+
+
 def test_long_messages_across_the_lds_staging(ver):
+    """The padded SHA-512 input (64 + len + 17 bytes, rounded up to 128) is
+    staged in LDS up to 2,048 bytes, that is for messages up to 1,967 bytes;
+    1,968 and longer take the byte-stream path."""
     rng = random.Random(7)
     seed = rng.randbytes(32)
     pub = OSSL.public_key(seed)
     slot = ver.ed_keys_load(np.frombuffer(pub, np.uint8).reshape(1, 32))[0]
-    lens = [0, 1, 63, 64, 127, 128, 2046, 2047, 2048, 2049, 2050, 2111, 2112, 4095, 4096, 9000]
+    lens = [0, 1, 63, 64, 127, 128, 1966, 1967, 1968, 1969, 2046, 2047, 2048, 2049, 2050, 2111, 2112, 4095, 4096, 9000]
     msgs = [rng.randbytes(n) for n in lens]
     sg = [OSSL.sign(seed, m) for m in msgs]
     bad = [m[:-1] + bytes([m[-1] ^ 0x80]) if m else b"x" for m in msgs]   # last byte flipped (past the LDS part too)
