@@ -28,6 +28,7 @@
 #include <functional>
 #include <list>
 #include <unordered_map>
+#include <utility>
 #include <future>
 #include <mutex>
 #include <random>
@@ -39,8 +40,20 @@
 #include "../../include/gpuverify.h"
 #include "gv_kernels.h"
 #include "gv_kidx.h"
+#include "gv_options.h"
 #include "gv_stage.h"
 #include "gv_async.h"
+
+// The build facts gv_options.h's accept rules ask for: the grouped route's kg
+// layouts (gv_kernels.h GV_KG_NGS), or 0 (off); the wide arena's widths.
+bool gvopt::kg_layout_ok(int ng) {
+  static const int kNGs[] = {GV_KG_NGS};
+  if (ng == 0) return true;
+  for (int v : kNGs)
+    if (v == ng) return true;
+  return false;
+}
+bool gvopt::kw_width_ok(int qw) { return gvk_kw_width_ok(qw); }
 
 namespace {
 
@@ -50,10 +63,39 @@ namespace {
     if (e_ != hipSuccess) return GV_EHIP;         \
   } while (0)
 
-constexpr size_t kMaxItems = 0xFFFFFF00ull;       // per launch (u32 lane indices)
+using gvopt::kMaxItems;
 constexpr size_t kLaneWords = 8 + 1 + 8 + 8 + 8 + GV_DIGIT_ROWS + 8 + 1 + GV_QTAB_WORDS;
 
 size_t round_up(size_t x, size_t m) { return (x + m - 1) / m * m; }
+
+// The blob bytes [lo, hi) that the messages of items [lo_i, hi_i) span; no
+// item: (0, 0).
+std::pair<uint64_t, uint64_t> msg_range(const uint64_t* off, const uint32_t* len, size_t lo_i, size_t hi_i) {
+  uint64_t lo = UINT64_MAX, hi = 0;
+  for (size_t i = lo_i; i < hi_i; ++i) {
+    lo = std::min<uint64_t>(lo, off[i]);
+    hi = std::max<uint64_t>(hi, off[i] + len[i]);
+  }
+  if (lo > hi) lo = hi = 0;
+  return {lo, hi};
+}
+
+// The key-ordered-lanes scratch (gv_sort.hip) of C lanes and nb buckets from
+// word p on: 3 C + 2 round_up(nb, 64) + round_up(tb / 4 + 1, 64) words (tb =
+// gvk_sort_temp_bytes(nb)).  No bits row: the secp256k1 pipeline adds its own.
+gvk_sort carve_sort(uint32_t* p, size_t C, size_t nb, size_t tb) {
+  gvk_sort so;
+  so.pos = p; p += C;
+  so.perm = p; p += C;
+  so.kslot = p; p += C;
+  so.bits = nullptr;
+  so.cnt = p; p += round_up(nb, 64);
+  so.off = p; p += round_up(nb, 64);
+  so.temp = p;
+  so.temp_bytes = tb;
+  return so;
+}
+size_t sort_words(size_t C, size_t nb, size_t tb) { return 3 * C + 2 * round_up(nb, 64) + round_up(tb / 4 + 1, 64); }
 
 // ------------------------------------------------------------ thread helpers
 // Pool, Worker, par_copy*, host_cpus, run_sliced: gv_stage.h
@@ -65,14 +107,6 @@ using gvstage::par_copy;
 using gvstage::par_copy_segs;
 using gvstage::run_sliced;
 
-// The grouped route's kg layouts (gv_kernels.h GV_KG_NGS), or 0 (off).
-bool kg_layout_ok(int ng) {
-  static const int kNGs[] = {GV_KG_NGS};
-  if (ng == 0) return true;
-  for (int v : kNGs)
-    if (v == ng) return true;
-  return false;
-}
 
 // ------------------------------------------------------------ device state
 // Device scratch of one batch chunk of C lanes (C % 256 == 0): the staged
@@ -189,7 +223,7 @@ struct Dev {
   hipEvent_t kidx_ev[2] = {nullptr, nullptr};     // time_kernels: around the last routed lookup's k_kidx_find
   hipEvent_t kidx_found = nullptr;                // the last gv_dev_keys_find on the context stream: the next pipelined
   bool kidx_found_used = false;                   // calls' FRONT streams wait for it (their sort / k_prep read its slots)
-  // HBM held by the optional tables (G tables, key arenas) against ctx->hbm_budget
+  // HBM held by the optional tables (G tables, key arenas) against ctx->opt.hbm_budget
   size_t opt_bytes = 0;
   // ring of per-launch stage events for gv_stage_stats
   static constexpr int kRing = 256;
@@ -571,6 +605,27 @@ const uint32_t* ed_btab16(Dev* d, bool on, hipStream_t st) {
   return d->edtab16;
 }
 
+// One small-batch ed25519 launch (k_ed_lat_sl / k_ed_lat_unc) of n items
+// against d's radix-16 key arena of kcount slots.
+gvk_edl fill_edl(const Dev* d, size_t n, size_t kcount, const uint32_t* slot, const uint8_t* sig, const uint8_t* blob,
+                 const uint64_t* off, const uint32_t* len, uint8_t* out8) {
+  gvk_edl b;
+  memset(&b, 0, sizeof b);
+  b.n = (uint32_t)n;
+  b.slot = slot;
+  b.sig64 = sig;
+  b.msg_blob = blob;
+  b.msg_off = off;
+  b.msg_len = len;
+  b.ktab = d->ektab;
+  b.kpub = d->ekpub;
+  b.kok = d->ekok;
+  b.kcount = (uint32_t)kcount;
+  b.btab = d->edtab;
+  b.out8 = out8;
+  return b;
+}
+
 int ensure_edg(Dev* d, size_t need, size_t words) {
   if (need <= d->edg_cap && words == d->edg_words) return GV_OK;
   for (uint32_t** q : {&d->edg_ktab, &d->edg_kpub, &d->edg_kok})
@@ -584,6 +639,10 @@ int ensure_edg(Dev* d, size_t need, size_t words) {
   d->edg_cap = cap;
   return GV_OK;
 }
+
+gvk_edk fill_edk(gv_ctx* ctx, const Dev* d, size_t n, size_t kcount, const uint32_t* perm, const uint32_t* slot,
+                 const uint8_t* sig, const uint8_t* blob, const uint64_t* off, const uint32_t* len, uint8_t* out8,
+                 const uint32_t* btab16);          // below gv_ctx
 
 // The grouped route on the device (scratch: the per-lane table region, which
 // the keyed kernel does not use).  *taken = false: the batch has too many
@@ -600,16 +659,8 @@ int ed_grouped(Dev* d, size_t n, const uint8_t* pub, const uint8_t* sig, const u
   uint32_t *table = q, *rep = table + T, *uid = rep + C, *slot = uid + C, *count = slot + C;
   uint8_t* kpub32 = (uint8_t*)(count + 64);
   uint32_t* sp = count + 64 + round_up(capU * 8, 64);
-  gvk_sort so;
-  so.pos = sp;
-  so.perm = sp + C;
-  so.kslot = sp + 2 * C;
-  so.bits = nullptr;
-  so.cnt = sp + 3 * C;
-  so.off = so.cnt + round_up(nb, 64);
-  so.temp = so.off + round_up(nb, 64);
-  so.temp_bytes = tb;
-  uint32_t* o8 = (uint32_t*)so.temp + round_up(tb / 4 + 1, 64);
+  const gvk_sort so = carve_sort(sp, C, nb, tb);
+  uint32_t* o8 = sp + sort_words(C, nb, tb);
   if ((size_t)(o8 + C / 4 - q) > C * (size_t)GV_ED_ROWS) return GV_OK;
   if (!d->ed_h_count && hipHostMalloc((void**)&d->ed_h_count, 64, hipHostMallocDefault) != hipSuccess) {
     d->ed_h_count = nullptr;
@@ -629,23 +680,12 @@ int ed_grouped(Dev* d, size_t n, const uint8_t* pub, const uint8_t* sig, const u
   if (rc) return rc == GV_ENOMEM ? GV_OK : rc;
   CK(gvk_ed_keys(kpub32, (uint32_t)U, 0u, nullptr, d->edg_ktab, d->edg_kpub, d->edg_kok, wb, rb, st));
   if (gc.sorted) CK(gvk_sort_slots(&so, (uint32_t)n, slot, (uint32_t)U, st));
-  gvk_edk b;
-  memset(&b, 0, sizeof b);
-  b.n = (uint32_t)n;
-  b.perm = gc.sorted ? so.perm : nullptr;
-  b.slot = slot;
-  b.sig64 = sig;
-  b.msg_blob = blob;
-  b.msg_off = off;
-  b.msg_len = len;
-  b.ktab = d->edg_ktab;
+  gvk_edk b = fill_edk(nullptr, d, n, U, gc.sorted ? so.perm : nullptr, slot, sig, blob, off, len, (uint8_t*)o8,
+                       ed_btab16(d, gc.btab16, st));
+  b.ktab = d->edg_ktab;                           // the per-batch arena
   b.kpub = d->edg_kpub;
   b.kok = d->edg_kok;
-  b.kcount = (uint32_t)U;
-  b.btab = d->edtab;
-  b.btab16 = ed_btab16(d, gc.btab16, st);
   b.rb = rb;
-  b.out8 = (uint8_t*)o8;
   CK(gvk_ed_keyed(&b, st));
   CK(gvk_ed_pack_bits((uint32_t)n, (const uint8_t*)o8, bits, st));
   d->ed_grouped_batches++;
@@ -698,105 +738,11 @@ struct AsyncState;                               // gv_submit_* / gv_wait (below
 struct gv_ctx {
   std::vector<Dev*> devs;
   AsyncState* async = nullptr;                    // created by the first gv_submit_*
-  size_t max_batch = size_t(1) << 20;
-  size_t lat_max = 8192;        // batches up to this size take a fused small-batch kernel (gv_lat.hip), larger ones the pipeline
-  size_t lat_sl_max = 2048;     // ... and up to this size the limb-sliced one (one signature per block); between the two the
-                                // four-lanes-per-signature kernel (0.50 ms flat to 8192): profiles/r02/lat_sliced/batch_curve*.json
-  // keyed batches (the key arena): the sliced keyed kernel takes 4 waves per
-  // signature and the 16-lanes-per-signature kernel beats the k4 pipeline to
-  // ~14k (profiles/r02/lat_sliced/keyed_curve.json).  Setting lat_max /
-  // lat_sl_max sets these too; lat_max_keyed / lat_sl_max_keyed only these.
-  size_t lat_max_keyed = 14336;
-  size_t lat_sl_max_keyed = 1536;
-  size_t pipe_chunk = 262144;   // host path: first chunk of the two-set copy/compute pipeline (0 = max_batch;
-                                // profiles/r03/hostpath_sweep.jsonl: 262144 x 4 steadiest on pageable input)
-  int pipe_growth = 4;          // host path: each later chunk at most this times the one before
-  int stage_pieces = 2;         // host path, pageable chunks of >= 65,536 items: staged in this many pieces, each
-                                // piece's H2D behind its copy (1 = one copy then one H2D; GV_STAGE_PIECES):
-                                // 121.4 / 129.4 / 126.2 / 126.8M/s at 1 / 2 / 4 / 8 (profiles/r04/hostpath/stage_pieces_ab.jsonl)
-  size_t async_chunk = 262144;  // submitted batches staged through the library (pageable, messages): fixed chunks
-  int async_growth = 1;         // of this size growing by async_growth (GV_ASYNC_CHUNK, GV_ASYNC_GROWTH;
-                                // "async_chunk" / "async_growth"): the copy of one chunk overlaps the others
-  bool async_whole = true;      // submitted batches read in place (the caller's pinned buffers): a slice behind
-                                // one still in flight is ONE chunk (its H2D and front run under the previous
-                                // ladder), a slice on an idle device takes the synchronous ramp (GV_ASYNC_WHOLE,
-                                // "async_whole").  1M pinned batches: 4.6 ms each steady vs 5.2 ms in 262,144-item
-                                // chunks (a 262,144-item ladder is 1,024 blocks = 1.33 rounds of the chip's 768
-                                // resident ones, and the next one only starts as it drains); pageable batches in
-                                // one chunk lose the copy overlap (143 vs 177M/s): profiles/r06/async/
-  bool host_ladder_stream = false;  // host chunks' ladders on the set's low-priority ladder stream (chunk_ladder;
-                                    // GV_HOST_LADDER_STREAM=1).  Measured off: async pinned 185 vs 157-167M/s,
-                                    // sync pinned 158-160 vs 150-152M/s (profiles/r05/async_ab.jsonl)
-  size_t lane_burst = 16;       // submitted batches: slices an async lane runs before it drains and releases the
-                                // device lock (GV_LANE_BURST)
-  bool lat_kw = true;           // keyed small batches on the wide arena's one-window tables (k_verify_lat16_kw)
-                                // when every slot has them, else the kn tables (GV_LAT_KW, "lat_kw")
-  bool h2d_serial = true;       // host slices: a chunk's H2D waits for the previous chunk's, so concurrent
-                                // transfers do not share the link and delay the chunk the GPU needs first
-                                // (GV_H2D_SERIAL)
-  bool gfull_item = true;       // the per-item (pub33, ungrouped) route takes G on the unsplit u1 too: 11 G
-                                // additions from the full-scalar tables instead of 14 (GV_GFULL_ITEM)
-  bool inv_small = true;        // k_scalar_inv folds fewer signatures per lane below 2^19 items (gvk_inv_m);
-                                // 0: GV_INV_M always (GV_INV_SMALL)
-  size_t slice_plain_first = 0; // host path, slices to be grouped: this many items first on the per-item pipeline,
-                                // submitted before the rest's keys are sent, grouped and tabulated (0 = off;
-                                // GV_SLICE_PLAIN_FIRST)
-  int stage_threads = 8;        // host path: staging threads per device, its slice's thread included (gv_open:
-                                // gvstage::stage_pool_threads -- half the process's CPUs, affinity capped by
-                                // the cgroup quota, split over the devices, 1..8 each)
-  bool time_kernels = false;
-  bool fault_inject = false;
-  bool lat_zero_copy = true;    // host-buffer batches on the sliced kernels read the pinned staging buffer and write
-                                // verdict bytes to pinned memory directly: no H2D, memset or D2H (GV_LAT_ZC=0: A/B)
-  bool lat_sliced = true;       // small batches on k_verify_lat_sl / k_verify_lat16_sl (GV_LAT_SLICED=0: the one-lane-field kernels, A/B)
-  size_t lat_rows_max = 512;     // pub33 small batches of at most this many: k_verify_lat_sl4 (rows of a wave on one accumulator, G from gtab6); 0: k_verify_lat_sl
-  bool keyed_k4 = true;         // keyed batches on k_ecmult_k4 (GV_KEYED_K4=0: the 125-doubling ladder, A/B)
-  bool gfull = true;            // k4 batches take G on the unsplit scalar: 11 25-bit windows instead of 14 20-bit
-                                // GLV windows (k_ecmult_k4<true>, 6 GiB of tables; GV_GFULL=0: A/B)
-  bool k6 = false;              // grouped batches on k_ecmult_k6: 6-bit Q windows on 32-entry key tables, the lambda
-                                // frame, G on the unsplit u1 in 24-bit windows (GV_K6=1)
-  int kg = 0;                   // grouped batches on k_ecmult_kn<5, kg>: k4's 16-entry 5-bit tables over kg groups
-                                // (one of GV_KG_NGS; 0 = k_ecmult_k4), G after the last doubling from the 24-bit
-                                // tables on the real curve (GV_KG, "kg"; takes precedence over k6).  Off: with
-                                // the unsplit key chain k4 stays ahead -- 223 vs 215-218M/s for kg 4 (its
-                                // ladder 2-3 % shorter, but at 126 VGPRs x 4 waves the next call's front kernels
-                                // no longer co-reside), 7 / 9 groups cut the ladder 10-17 % and cost more in the
-                                // front (217 / 210M/s; profiles/r06/ab/ab3, ab4)
-  int keys_wide = 2;            // ... and wide-window tables while device memory holds them (GV_KEYS_WIDE): 2 = one
-                                // GV_KW_QW-bit window per group (11: 12 groups of 1,024 entries, no doublings, 24 Q
-                                // additions), moving to two per group (6 groups, 11 doublings) when that no longer fits,
-                                // then to the GV_KWN_QW-bit layouts (keys_wide_qw); 1 = two per group; 0 = none
-  size_t keys_wide1_cap = SIZE_MAX;   // test hook: the one-window layout's slot capacity ("keys_wide1_cap")
-  int keys_wide_qw = 0;         // the wide arena's window width ("keys_wide_qw", GV_KEYS_WIDE_QW): 0 = the GV_KW_QW-bit
-                                // layouts, then the GV_KWN_QW-bit ones when those no longer fit (kWideLayouts);
-                                // GV_KW_QW / GV_KWN_QW = that width's two layouts only
-  size_t keys_wide_bytes = 0;   // the wide arena is never allocated larger than this ("keys_wide_mb", GV_KEYS_WIDE_MB;
-                                // 0 = no limit): past it the arena moves down the layouts, then to the k6 tables
-  bool keys_k6 = true;          // the resident arena (gv_keys_load) also holds k6 tables and its throughput batches
-                                // run k_ecmult_k6: the table build is paid once per key, not per batch (GV_KEYS_K6)
-  size_t key_cap = GV_KEY_CAP;  // the callers' key-arena reset point: growth doubles up to here ("key_cap", GV_KEY_CAP)
-  size_t ed_key_cap = GV_ED_KEY_CAP;   // the same for the ed25519 arena ("ed_key_cap", GV_ED_KEY_CAP)
-  size_t hbm_budget = SIZE_MAX; // bytes of optional device tables per device (G tables, key arenas; "hbm_budget_mb",
-                                // GV_HBM_BUDGET_MB): a table past it is not built and batches take the schedule
-                                // that needs less, with the same verdicts
-  bool pipeline_dev = true;     // pipelined device-resident calls on the context stream (dev_run; GV_PIPELINE=0: A/B)
-  bool two_ladders = true;      // ... whose ladders alternate two high-priority streams, so the next ladder starts in
-                                // the current one's tail (bitmap writes kept in call order; GV_TWO_LADDERS=0: A/B)
-  bool group_keys = true;       // pub33 throughput batches parse each distinct key once (group_keys; GV_GROUP_KEYS=0: A/B)
-  bool keys_scratch = true;     // key tables: forward entries through coalesced scratch rows (GV_KEYS_SCRATCH=0: A/B)
-  bool sort_keys = true;        // keyed k4 batches run their lanes in slot order (gv_sort.hip; GV_SORT_KEYS=0: A/B)
-  size_t group_min = 16384;     // ... batches of at least this many items
-  int group_div = 5;            // ... taking the keyed pipeline when distinct keys <= items / group_div (break-even ~4:
-                                // a key build ~18 ns vs ~4 ns saved per item, profiles/r03/group_ab)
+  gvopt::Options opt;                             // the tunables (gv_options.h)
   size_t keys = 0;              // key-arena slots in use (same on every device)
   std::atomic<uint64_t> keys_gen{0};  // gv_keys_reset calls
   std::atomic<uint64_t> keys_replaced{0};   // slots gv_keys_replace rewrote since gv_open ("keys_replaced")
   std::mutex keys_mu;
-  bool keys_index = false;      // gv_keys_load also keeps a device index of the arena, 33 key bytes -> slot (gv_kidx.h),
-                                // and gv_dev_verify_digests / _msgs route a throughput batch whose keys are all
-                                // resident onto the keyed pipeline ("keys_index", GV_KEYS_INDEX): taken by an arena
-                                // started from slot 0; 0 stops its use at once
-  uint64_t kidx_seed = 0;       // the index hash's seed, drawn at gv_open ("keys_index_seed": a test hook)
   std::atomic<uint64_t> kidx_hit{0}, kidx_miss{0};   // pub33 device batches routed keyed / that fell through
   std::atomic<uint64_t> kidx_launches{0};            // k_kidx_* launches since gv_open ("keys_index_launches")
   std::atomic<uint64_t> kidx_find_ns{0};             // time_kernels: the last routed lookup's k_kidx_find
@@ -806,31 +752,50 @@ struct gv_ctx {
   std::atomic<uint64_t> ed_keys_replaced{0};   // slots gv_ed_keys_replace rewrote since gv_open ("ed_keys_replaced")
   std::mutex ed_keys_mu;
   std::vector<uint8_t> ed_kpub;  // the raw keys per slot (large keyed batches run the throughput kernels on them)
-  bool ed_group = true;          // ed25519 throughput batches: in-batch key grouping + k_ed_keyed (GV_ED_GROUP=0: A/B)
-  size_t ed_group_min = 196608;  // ... from this many items (the key build's chain is ~1 ms of one-lane chains whatever
-                                 // the key count up to ~65k keys; the keyed kernel saves ~6.4 ns per item; host
-                                 // chunks of 262,144 qualify)
-  int ed_group_div = 16;         // ... with at most items / ed_group_div distinct keys
-  size_t ed_group_cap = 16384;   // ... and at most this many (72 KB of comb table per key)
-  bool ed_keys_split = true;     // ed25519 key tables: serial chain and table adds in two launches (GV_ED_KEYS_SPLIT=0: A/B)
-  bool ed_btab16 = true;         // k_ed_keyed's [s]B from the radix-2^16 table: 16 additions instead of 32 (GV_ED_BTAB16)
-  bool ed_group_r64 = true;      // grouped ed25519 key tables as radix-64 combs: 43 [h](-A) additions, not 64 (GV_ED_GROUP_R64)
-  bool ed_keyed = true;          // keyed ed25519 batches past ed_lat_max on k_ed_keyed (GV_ED_KEYED=0: the throughput kernels)
-  size_t ed_lat_max = 2048;      // keyed ed25519 batches up to this size take k_ed_lat_sl (one signature per block)
-  int ed_keys_wide = 0;          // the ed25519 arena also holds radix-2^6 or radix-2^8 combs of -A for k_ed_keyed
-                                 // (0 = none, 6, 8; "ed_keys_wide", GV_ED_KEYS_WIDE): taken by an arena started from
-                                 // slot 0; 0 stops their use at once
-  size_t ed_keys_wide_bytes = 0; // the wide ed25519 arena is never allocated larger than this ("ed_keys_wide_mb",
-                                 // GV_ED_KEYS_WIDE_MB; 0 = no limit)
   std::atomic<uint64_t> ed_keyed_wide{0};   // keyed batches / chunks that ran on wide tables since gv_open ("ed_keyed_wide")
-  size_t ed_unc_lat_max = 2048;  // uncached ed25519 host batches up to this size take k_ed_lat_unc (one signature per block)
 };
 
 namespace {
 
 EdGroupCfg ed_group_cfg(const gv_ctx* ctx) {
-  return EdGroupCfg{ctx->ed_group, ctx->ed_group_min, ctx->ed_group_div, ctx->ed_group_cap, ctx->sort_keys,
-                    ctx->ed_keys_split, ctx->ed_btab16, ctx->ed_group_r64};
+  return EdGroupCfg{ctx->opt.ed_group, ctx->opt.ed_group_min, ctx->opt.ed_group_div, ctx->opt.ed_group_cap, ctx->opt.sort_keys,
+                    ctx->opt.ed_keys_split, ctx->opt.ed_btab16, ctx->opt.ed_group_r64};
+}
+
+// k_ed_keyed reads d's wide tables when every slot of the arena has them
+// (option "ed_keys_wide" still on), else the radix-16 ones.
+bool ed_wide_serves(const gv_ctx* ctx, const Dev* d, size_t kcount) {
+  return ctx->opt.ed_keys_wide && d->ektabw && d->ekw_rb && kcount && d->ekeysw >= kcount && d->ekcapw >= kcount;
+}
+
+// One k_ed_keyed batch of n items against d's ed25519 arena of kcount slots:
+// its wide tables when they serve (counted in ed_keyed_wide), else the
+// radix-16 ones.  ctx null (ed_grouped): the keys sit in the per-batch arena
+// and the caller sets ktab / kpub / kok / rb.
+gvk_edk fill_edk(gv_ctx* ctx, const Dev* d, size_t n, size_t kcount, const uint32_t* perm, const uint32_t* slot,
+                 const uint8_t* sig, const uint8_t* blob, const uint64_t* off, const uint32_t* len, uint8_t* out8,
+                 const uint32_t* btab16) {
+  gvk_edk b;
+  memset(&b, 0, sizeof b);
+  b.n = (uint32_t)n;
+  b.perm = perm;
+  b.slot = slot;
+  b.sig64 = sig;
+  b.msg_blob = blob;
+  b.msg_off = off;
+  b.msg_len = len;
+  b.kcount = (uint32_t)kcount;
+  b.btab = d->edtab;
+  b.btab16 = btab16;
+  b.out8 = out8;
+  if (!ctx) return b;
+  const bool wide = ed_wide_serves(ctx, d, kcount);
+  b.ktab = wide ? d->ektabw : d->ektab;
+  b.rb = wide ? d->ekw_rb : 4;
+  b.kpub = d->ekpub;
+  b.kok = d->ekok;
+  if (wide) ctx->ed_keyed_wide.fetch_add(1);
+  return b;
 }
 
 // Optional device tables (the G tables past the 64 MiB GLV pair, the key
@@ -840,7 +805,7 @@ EdGroupCfg ed_group_cfg(const gv_ctx* ctx) {
 // schedule that needs less (k6 -> k4 -> the 125-doubling keyed ladder; the
 // full-scalar G tables -> the GLV G windows) with the same verdicts.
 uint32_t* opt_alloc(gv_ctx* ctx, Dev* d, size_t bytes) {
-  if (d->opt_bytes + bytes > ctx->hbm_budget) return nullptr;
+  if (d->opt_bytes + bytes > ctx->opt.hbm_budget) return nullptr;
   uint32_t* p = nullptr;
   if (hipMalloc(&p, bytes) != hipSuccess) {
     (void)hipGetLastError();
@@ -876,7 +841,7 @@ int gen_table(Set* s, hipStream_t st, GEN&& gen) {
 // then one sync each; ~0.5 s), or on first use after an option switched a
 // schedule on.  sync = false: enqueue only.
 int ensure_gtabf(gv_ctx* ctx, Dev* d, Set* s, hipStream_t st, bool sync = true) {
-  if (d->gtabf || !ctx->gfull || d->gtabf_failed) return GV_OK;
+  if (d->gtabf || !ctx->opt.gfull || d->gtabf_failed) return GV_OK;
   uint32_t* tf = opt_alloc(ctx, d, GV_GF_WORDS * 4);
   if (!tf) { d->gtabf_failed = true; return GV_OK; }
   int rc = gen_table(s, st, [&](uint32_t* sc) { return gvk_gen_gtablef(tf, sc, st); });
@@ -887,7 +852,7 @@ int ensure_gtabf(gv_ctx* ctx, Dev* d, Set* s, hipStream_t st, bool sync = true) 
 }
 
 int ensure_gtab4(gv_ctx* ctx, Dev* d, Set* s, hipStream_t st, bool sync = true) {
-  if (!ctx->keyed_k4) return GV_OK;
+  if (!ctx->opt.keyed_k4) return GV_OK;
   if (!d->gtab4 && !d->gtab4_failed) {
     uint32_t* t4 = opt_alloc(ctx, d, kGtab4Bytes);
     if (!t4) {
@@ -903,8 +868,8 @@ int ensure_gtab4(gv_ctx* ctx, Dev* d, Set* s, hipStream_t st, bool sync = true) 
 }
 
 // k_ecmult_k6's G tables.  A failure is remembered and keyed / grouped batches
-// stay on k4.  `want`: the schedule is on (ctx->k6 for the grouped route,
-// ctx->keys_k6 for the resident arena).
+// stay on k4.  `want`: the schedule is on (ctx->opt.k6 for the grouped route,
+// ctx->opt.keys_k6 for the resident arena).
 int ensure_gtab6(gv_ctx* ctx, Dev* d, Set* s, hipStream_t st, bool want, bool sync = true) {
   if (d->gtab6 || !want || d->gtab6_failed) return GV_OK;
   uint32_t* t6 = opt_alloc(ctx, d, GV_K6_GTAB_WORDS * 4);
@@ -932,7 +897,7 @@ int ensure_group_arena(gv_ctx* ctx, Dev* d, Set* s, size_t cap, int ent, int ng)
   s->g_ent = ent;
   s->g_ng = ng;
   const size_t eb = (size_t)ent * 4;
-  if (d->opt_bytes + group_arena_bytes(cap, ent, ng) > ctx->hbm_budget) return GV_ENOMEM;
+  if (d->opt_bytes + group_arena_bytes(cap, ent, ng) > ctx->opt.hbm_budget) return GV_ENOMEM;
   if (hipMalloc(&s->g_kqt, cap * eb) != hipSuccess || hipMalloc(&s->g_kzq, cap * 8 * 4) != hipSuccess ||
       hipMalloc(&s->g_kok, cap * 4) != hipSuccess ||
       hipMalloc(&s->g_kqt2, cap * (ng - 1) * eb) != hipSuccess ||
@@ -959,7 +924,7 @@ int group_keys(gv_ctx* ctx, Dev* d, Set* s, gvk_batch& b, size_t n, hipStream_t 
   const size_t C = b.C;
   size_t T = 512;
   while (T < 2 * n) T <<= 1;
-  const size_t capU = round_up(std::max<size_t>(C / ctx->group_div, 256), 256);
+  const size_t capU = round_up(std::max<size_t>(C / ctx->opt.group_div, 256), 256);
   uint32_t* q = s->qtab;
   uint32_t *rep = q, *uid = q + C, *kslot = q + 2 * C, *count = q + 3 * C, *table = q + 3 * C + 256;
   uint32_t* kx = table + T;
@@ -969,7 +934,7 @@ int group_keys(gv_ctx* ctx, Dev* d, Set* s, gvk_batch& b, size_t n, hipStream_t 
   const size_t room = used < total ? total - used : 0;
   if (gvk_keys_scratch_words((uint32_t)capU, GV_LGRP, GV_QTAB_N, 0) > room) return GV_OK;   // no room: pub33
   const bool k6_room = gvk_keys_scratch_words((uint32_t)capU, 4, GV_K6_NT, 0) <= room;
-  const int kgng = ctx->kg;                     // 0 or one of GV_KG_NGS
+  const int kgng = ctx->opt.kg;                     // 0 or one of GV_KG_NGS
   const bool kg_room = kgng && gvk_keys_scratch_words((uint32_t)capU, kgng, GV_QTAB_N, 0) <= room;
   if (!s->h_count && hipHostMalloc((void**)&s->h_count, 64, hipHostMallocDefault) != hipSuccess) {
     s->h_count = nullptr;
@@ -985,14 +950,14 @@ int group_keys(gv_ctx* ctx, Dev* d, Set* s, gvk_batch& b, size_t n, hipStream_t 
   CK(hipMemcpyAsync(s->h_count, count, 4, hipMemcpyDeviceToHost, st));
   CK(hipStreamSynchronize(st));
   const size_t U = *s->h_count;
-  if (U == 0 || U * ctx->group_div > n || U > capU) return GV_OK;   // many distinct keys: the pub33 pipeline
+  if (U == 0 || U * ctx->opt.group_div > n || U > capU) return GV_OK;   // many distinct keys: the pub33 pipeline
   // the layout: kg (5-bit windows over kgng groups) > k6 (6-bit, 4 groups) > k4,
   // each needing gtab6 (kg, k6) and its arena within the HBM budget
-  if (((ctx->k6 && k6_room) || kg_room) && (rc = ensure_gtab6(ctx, d, s, st, true))) return rc;
+  if (((ctx->opt.k6 && k6_room) || kg_room) && (rc = ensure_gtab6(ctx, d, s, st, true))) return rc;
   // the arena for the set's whole capacity when the budget holds it: a later,
   // larger chunk on this set does not regrow it (hipFree waits for the device)
   auto arena = [&](int ent, int ng) {
-    const size_t capA = round_up(std::max<size_t>(s->cap / ctx->group_div, 256), 256);
+    const size_t capA = round_up(std::max<size_t>(s->cap / ctx->opt.group_div, 256), 256);
     if (capA > capU && !(capA <= s->gcap && ent == s->g_ent && ng == s->g_ng)) {
       const int r = ensure_group_arena(ctx, d, s, capA, ent, ng);
       if (r != GV_ENOMEM) return r;
@@ -1004,7 +969,7 @@ int group_keys(gv_ctx* ctx, Dev* d, Set* s, gvk_batch& b, size_t n, hipStream_t 
     if (rc != GV_ENOMEM) return rc;
     kg = false;                                 // no room for kgng groups
   }
-  bool k6 = !kg && ctx->k6 && k6_room && d->gtab6;
+  bool k6 = !kg && ctx->opt.k6 && k6_room && d->gtab6;
   if (k6 && (rc = arena(GV_K6_KEY_WORDS, GV_LGRP))) {
     if (rc != GV_ENOMEM) return rc;
     k6 = false;                                 // no room for the 32-entry tables: k4
@@ -1019,7 +984,7 @@ int group_keys(gv_ctx* ctx, Dev* d, Set* s, gvk_batch& b, size_t n, hipStream_t 
   // the forward pass's entries in coalesced scratch rows after the ratio and
   // E rows, when they fit (else through the tables themselves)
   const int nt = k6 ? GV_K6_NT : GV_QTAB_N, ng = kg ? kgng : GV_LGRP;
-  const int with_qe = ctx->keys_scratch && gvk_keys_scratch_words((uint32_t)U, ng, nt, 1) <= room ? 1 : 0;
+  const int with_qe = ctx->opt.keys_scratch && gvk_keys_scratch_words((uint32_t)U, ng, nt, 1) <= room ? 1 : 0;
   if (kg)
     CK(gvk_keys_build_rows_kg((uint32_t)U, (uint32_t)capU, kx, kpfx, sc, with_qe, s->g_kqt, s->g_kzq,
                               (uint32_t)capU, s->g_kok, s->g_kqt2, s->g_kzq2, kgng, s->side));
@@ -1036,7 +1001,7 @@ int group_keys(gv_ctx* ctx, Dev* d, Set* s, gvk_batch& b, size_t n, hipStream_t 
   b.kslot = kslot; b.kqt = s->g_kqt; b.kzq = s->g_kzq; b.kok = s->g_kok;
   b.kC = (uint32_t)capU; b.kcount = (uint32_t)U;
   b.kqt2 = s->g_kqt2; b.gtab4 = d->gtab4;       // null gtab4: the 125-doubling keyed ladder
-  b.gtabf = ctx->gfull ? d->gtabf : nullptr;    // built by ensure_gtab4 above on first use
+  b.gtabf = ctx->opt.gfull ? d->gtabf : nullptr;    // built by ensure_gtab4 above on first use
   b.k6 = kg ? kgng : k6 ? 4 : 0; b.gtab6 = d->gtab6;
   b.kqw = kg ? 2 : 0;
   d->grouped_batches++;
@@ -1048,19 +1013,13 @@ int group_keys(gv_ctx* ctx, Dev* d, Set* s, gvk_batch& b, size_t n, hipStream_t 
 // `base` of the set's Q-table region (unused by the keyed pipeline past the
 // grouping rows); no room or the option off: item order.
 void plan_sort(gv_ctx* ctx, Set* s, gvk_batch& b, uint32_t* base) {
-  if (!ctx->sort_keys || !b.kslot || !(b.gtab4 || (b.k6 && b.gtab6))) return;
+  if (!ctx->opt.sort_keys || !b.kslot || !(b.gtab4 || (b.k6 && b.gtab6))) return;
   const size_t C = b.C, nb = (size_t)b.kcount + 1;
   const size_t tb = gvk_sort_temp_bytes((uint32_t)nb);
   uint32_t* p = s->qtab + round_up((size_t)(base - s->qtab), 64);
-  gvk_sort so;
-  so.pos = p; p += C;
-  so.perm = p; p += C;
-  so.kslot = p; p += C;
-  so.bits = (uint64_t*)p; p += C / 32;
-  so.cnt = p; p += round_up(nb, 64);
-  so.off = p; p += round_up(nb, 64);
-  so.temp = p; p += round_up(tb / 4 + 1, 64);
-  so.temp_bytes = tb;
+  gvk_sort so = carve_sort(p, C, nb, tb);
+  p += sort_words(C, nb, tb);
+  so.bits = (uint64_t*)p; p += C / 32;            // the slot-ordered accept bits, behind the scan scratch
   if ((size_t)(p - s->qtab) > (size_t)GV_QTAB_WORDS * C) return;
   b.srt = so;
 }
@@ -1106,7 +1065,7 @@ void kidx_stop(Dev* d) {
 }
 // The index covers the arena as it stands (an empty arena: every key misses).
 bool kidx_live(const gv_ctx* ctx, const Dev* d) {
-  if (!ctx->keys_index || d->kidx_failed || d->kidx_keys != ctx->keys) return false;
+  if (!ctx->opt.keys_index || d->kidx_failed || d->kidx_keys != ctx->keys) return false;
   return ctx->keys == 0 || (d->kidx_on && d->kidx_tab);
 }
 
@@ -1115,7 +1074,7 @@ int kidx_refill(gv_ctx* ctx, Dev* d, size_t count, hipStream_t st) {
   CK(hipMemsetAsync(d->kidx_tab, 0xFF, d->kidx_T * 4, st));
   CK(hipMemsetAsync(d->kidx_cnt, 0, 4, st));
   if (count) {
-    CK(gvk_kidx_put(d->kidx_tab, (uint32_t)d->kidx_T, d->kidx_rows, (uint32_t)count, 0, nullptr, ctx->kidx_seed,
+    CK(gvk_kidx_put(d->kidx_tab, (uint32_t)d->kidx_T, d->kidx_rows, (uint32_t)count, 0, nullptr, ctx->opt.kidx_seed,
                     d->kidx_cnt, st));
     ctx->kidx_launches++;
   }
@@ -1160,13 +1119,13 @@ int kidx_ensure(gv_ctx* ctx, Dev* d, size_t used, hipStream_t st) {
 int kidx_lookup(gv_ctx* ctx, Dev* d, size_t n, const uint8_t* pub, uint32_t* out, hipStream_t st, bool* all) {
   uint32_t* miss = d->kidx_cnt + 16;
   CK(hipMemsetAsync(miss, 0, 4, st));
-  const bool timed = ctx->time_kernels;
+  const bool timed = ctx->opt.time_kernels;
   if (timed) {
     for (hipEvent_t& e : d->kidx_ev)
       if (!e) CK(hipEventCreate(&e));
     CK(hipEventRecord(d->kidx_ev[0], st));
   }
-  CK(gvk_kidx_find(d->kidx_tab, (uint32_t)d->kidx_T, d->kidx_rows, (uint32_t)ctx->keys, ctx->kidx_seed, pub,
+  CK(gvk_kidx_find(d->kidx_tab, (uint32_t)d->kidx_T, d->kidx_rows, (uint32_t)ctx->keys, ctx->opt.kidx_seed, pub,
                    (uint32_t)n, out, miss, st));
   ctx->kidx_launches++;
   if (timed) CK(hipEventRecord(d->kidx_ev[1], st));
@@ -1187,23 +1146,64 @@ int kidx_lookup(gv_ctx* ctx, Dev* d, size_t n, const uint8_t* pub, uint32_t* out
 // it happens once -- not again when a larger chunk, a queued whole slice or a
 // host-buffer call follows device-resident calls of another size.
 size_t grow_items(const gv_ctx* ctx, size_t C) {
-  return ctx->pipe_chunk && C > ctx->pipe_chunk ? std::max(C, round_up(ctx->max_batch, 256)) : C;
+  return ctx->opt.pipe_chunk && C > ctx->opt.pipe_chunk ? std::max(C, round_up(ctx->opt.max_batch, 256)) : C;
 }
 
-// Launch the pipeline for n items whose inputs already sit on the device, on
-// set s's scratch, stream st.  The caller holds d->mu.
-// st_ecm (pipelined device-resident calls): the ladder runs there, after the
-// front kernels on st; the set's scratch is released on st_ecm.
-int launch(gv_ctx* ctx, Dev* d, Set* s, size_t n, const uint8_t* pub, const uint8_t* sig, const uint8_t* dig,
-           const uint8_t* blob, const uint64_t* off, const uint32_t* len, uint64_t* bits_out,
-           hipStream_t st, const uint32_t* kslot = nullptr, uint8_t* out8 = nullptr, hipStream_t st_ecm = nullptr,
-           const KeyArena* ka = nullptr, bool no_group = false, bool index = false) {
+// The tables of the resident arena (gv_keys_load) that serve a keyed batch:
+// the wide-window ones when every slot in use has them (their own arena: Z
+// rows of stride kcapw) and the caller's schedule reads their layout
+// (wide_ok), else the kn ones when every slot has those, else k4's.  The
+// kinds are gvk_lat's kn values.
+enum { kTabsK4 = 0, kTabsKn = 1, kTabsWide = 2 };
+struct ArenaTabs {
+  int kind;
+  const uint32_t *kqt, *kzq, *kqt2;
+  uint32_t kC;
+};
+ArenaTabs arena_tabs(const gv_ctx* ctx, const Dev* d, bool wide_ok) {
+  if (wide_ok && ctx->opt.keys_wide && d->kqtw && d->kw_ng && d->gtab6 && d->keysw >= ctx->keys)
+    return {kTabsWide, d->kqtw, d->kzqw, d->kqtw2, (uint32_t)d->kcapw};
+  if (ctx->opt.keys_k6 && d->kqt6 && d->gtab6 && d->keys6 >= ctx->keys)
+    return {kTabsKn, d->kqt6, d->kzq6, d->kqt62, (uint32_t)d->kcap};
+  return {kTabsK4, d->kqt, d->kzq, d->kqt2, (uint32_t)d->kcap};
+}
+
+// What launch() verifies: n items by key bytes (pub33) or by slot (kslot) of
+// the resident arena or of `ka`, digests (dig32) or messages (blob, off, len).
+struct Items {
+  size_t n = 0;
+  const uint8_t* pub33 = nullptr;
+  const uint32_t* kslot = nullptr;
+  const uint8_t *sig64 = nullptr, *dig32 = nullptr, *blob = nullptr;
+  const uint64_t* off = nullptr;
+  const uint32_t* len = nullptr;
+  const KeyArena* ka = nullptr;                   // a host slice's grouped keys, which kslot then indexes
+  bool no_group = false;                          // the per-item pub33 pipeline whatever the keys repeat
+  bool index = false;                             // pub33 throughput batches may route through the pubkey index
+};
+// Where the verdicts go: the accept bitmap (device) or, on the sliced
+// small-batch kernels, one byte per item (out8).  st_ecm (pipelined
+// device-resident calls): the ladder runs there, after the front kernels on
+// st; the set's scratch is released on st_ecm.
+struct LaunchOut {
+  uint64_t* bits = nullptr;
+  uint8_t* out8 = nullptr;
+  hipStream_t st_ecm = nullptr;
+};
+
+// Launch the pipeline for the items, whose inputs already sit on the device
+// (or in pinned host memory), on set s's scratch, stream st.  The caller
+// holds d->mu.
+int launch(gv_ctx* ctx, Dev* d, Set* s, const Items& it, const LaunchOut& out, hipStream_t st) {
+  const size_t n = it.n;
+  const uint32_t* kslot = it.kslot;             // (or the index's slots, below)
+  const KeyArena* ka = it.ka;
   if (n == 0 || n > kMaxItems) return GV_EINVAL;
   const size_t C = round_up(n, 256);
   int rc = ensure_cap(s, grow_items(ctx, C));
   if (rc) return rc;
   if (kslot && !ka) {                           // the arena always exists for a keyed batch
-    rc = ensure_keys(d, 1, ctx->keys, st, ctx->key_cap, ctx->hbm_budget, nullptr);
+    rc = ensure_keys(d, 1, ctx->keys, st, ctx->opt.key_cap, ctx->opt.hbm_budget, nullptr);
     if (rc) return rc;
   }
   rc = set_acquire(s, st);
@@ -1211,14 +1211,14 @@ int launch(gv_ctx* ctx, Dev* d, Set* s, size_t n, const uint8_t* pub, const uint
   gvk_batch b;
   memset(&b, 0, sizeof b);
   b.n = (uint32_t)n; b.C = (uint32_t)C;
-  b.pub33 = pub; b.sig64 = sig; b.dig32 = dig;
-  b.msg_blob = blob; b.msg_off = off; b.msg_len = len;
+  b.pub33 = it.pub33; b.sig64 = it.sig64; b.dig32 = it.dig32;
+  b.msg_blob = it.blob; b.msg_off = it.off; b.msg_len = it.len;
   b.gtab = d->gtab;
-  b.gtabf = ctx->gfull ? d->gtabf : nullptr;
+  b.gtabf = ctx->opt.gfull ? d->gtabf : nullptr;
   b.in_x = s->in_x; b.in_pfx = s->in_pfx; b.in_r = s->in_r; b.in_s = s->in_s; b.in_e = s->in_e;
   b.digits = s->digits; b.zq = s->zq; b.flags = s->flags; b.qtab = s->qtab;
-  b.bits = bits_out;
-  b.inv_m = ctx->inv_small ? 0u : (uint32_t)GV_INV_M;
+  b.bits = out.bits;
+  b.inv_m = ctx->opt.inv_small ? 0u : (uint32_t)GV_INV_M;
   const uint32_t* kzq2 = d->kzq2;
   // index (gv_dev_verify_digests / _msgs, option "keys_index"): a throughput
   // batch whose keys are all resident runs as the keyed call with those slots
@@ -1226,8 +1226,8 @@ int launch(gv_ctx* ctx, Dev* d, Set* s, size_t n, const uint8_t* pub, const uint
   // (free on the keyed pipeline; plan_sort starts past them).  Any miss: the
   // batch goes on as without the index.
   bool via_index = false;
-  if (index && pub && !kslot && n > ctx->lat_max && ctx->keys && kidx_live(ctx, d)) {
-    if ((rc = kidx_lookup(ctx, d, n, pub, s->qtab, st, &via_index))) return rc;
+  if (it.index && it.pub33 && !kslot && n > ctx->opt.lat_max && ctx->keys && kidx_live(ctx, d)) {
+    if ((rc = kidx_lookup(ctx, d, n, it.pub33, s->qtab, st, &via_index))) return rc;
     if (via_index) kslot = s->qtab;
     (via_index ? ctx->kidx_hit : ctx->kidx_miss)++;
   }
@@ -1249,7 +1249,7 @@ int launch(gv_ctx* ctx, Dev* d, Set* s, size_t n, const uint8_t* pub, const uint
     b.kqt2 = d->kqt2; b.gtab4 = d->gtab4;       // null: the 125-doubling keyed ladder
   }
   hipEvent_t* rs = nullptr;
-  if (ctx->time_kernels) {
+  if (ctx->opt.time_kernels) {
     rs = d->ring[d->ring_next];
     for (int i = 0; i < 6; ++i)
       if (!rs[i]) CK(hipEventCreate(&rs[i]));
@@ -1260,20 +1260,20 @@ int launch(gv_ctx* ctx, Dev* d, Set* s, size_t n, const uint8_t* pub, const uint
   }
   // k6 group tables (a grouped slice's chunks) are read by k_ecmult_k6 only:
   // such a chunk takes the pipeline whatever its size
-  const bool small = n <= (kslot ? ctx->lat_max_keyed : ctx->lat_max) && !b.k6 && !via_index;
-  const bool pipelined = st_ecm != nullptr && !small;
-  // the resident arena's k6 tables (every slot in use has them): throughput
-  // batches on k_ecmult_k6; the small-batch kernels keep the k4 tables
-  if (kslot && !ka && !small && ctx->keys_wide && d->kqtw && d->kw_ng && d->gtab6 && d->keysw >= ctx->keys) {
-    // the wide-window tables (their own arena: Z rows of stride kcapw)
-    b.kqt = d->kqtw; b.kzq = d->kzqw; b.kqt2 = d->kqtw2; b.kC = (uint32_t)d->kcapw;
-    b.k6 = d->kw_ng; b.kqw = 1; b.kwq = d->kw_qw; b.gtab6 = d->gtab6;
-  } else if (kslot && !ka && !small && ctx->keys_k6 && d->kqt6 && d->gtab6 && d->keys6 >= ctx->keys) {
-    b.kqt = d->kqt6; b.kzq = d->kzq6; b.kqt2 = d->kqt62;
-    b.k6 = GV_KN_ARENA_NG; b.gtab6 = d->gtab6;
+  const bool small = n <= (kslot ? ctx->opt.lat_max_keyed : ctx->opt.lat_max) && !b.k6 && !via_index;
+  const bool pipelined = out.st_ecm != nullptr && !small;
+  // the resident arena's wide or kn tables: throughput batches on
+  // k_ecmult_kn / k_ecmult_k6 (the small-batch kernels choose below)
+  if (kslot && !ka && !small) {
+    const ArenaTabs t = arena_tabs(ctx, d, true);
+    if (t.kind != kTabsK4) {
+      b.kqt = t.kqt; b.kzq = t.kzq; b.kqt2 = t.kqt2; b.kC = t.kC; b.gtab6 = d->gtab6;
+      b.k6 = t.kind == kTabsWide ? d->kw_ng : GV_KN_ARENA_NG;
+    }
+    if (t.kind == kTabsWide) { b.kqw = 1; b.kwq = d->kw_qw; }
   }
   if (pipelined) {
-    b.st_ecm = st_ecm;
+    b.st_ecm = out.st_ecm;
     b.ecm_ready = s->ecm_ready;
     b.bits_wait = d->bits_wait;
     b.bits_done = d->bits_rec;
@@ -1284,32 +1284,31 @@ int launch(gv_ctx* ctx, Dev* d, Set* s, size_t n, const uint8_t* pub, const uint
     gvk_lat lb;
     memset(&lb, 0, sizeof lb);
     lb.n = (uint32_t)n; lb.C = (uint32_t)C;
-    lb.pub33 = pub; lb.sig64 = sig; lb.dig32 = dig;
-    lb.msg_blob = blob; lb.msg_off = off; lb.msg_len = len;
-    lb.gtab = d->gtab; lb.e_soa = s->in_e; lb.bits = bits_out;
+    lb.pub33 = it.pub33; lb.sig64 = it.sig64; lb.dig32 = it.dig32;
+    lb.msg_blob = it.blob; lb.msg_off = it.off; lb.msg_len = it.len;
+    lb.gtab = d->gtab; lb.e_soa = s->in_e; lb.bits = out.bits;
     lb.ev[0] = b.ev[0];
-    if (!kslot && n <= ctx->lat_rows_max) lb.gtab6 = d->gtab6;   // k_verify_lat_sl4 (null: not built)
+    if (!kslot && n <= ctx->opt.lat_rows_max) lb.gtab6 = d->gtab6;   // k_verify_lat_sl4 (null: not built)
     if (kslot) {
       lb.pub33 = nullptr;
       lb.kslot = kslot; lb.kqt = b.kqt; lb.kzq = b.kzq; lb.kok = b.kok; lb.kC = b.kC; lb.kcount = b.kcount;
     }
-    const bool sliced = ctx->lat_sliced && n <= (kslot ? ctx->lat_sl_max_keyed : ctx->lat_sl_max);
-    if (out8 && !sliced) return GV_EINVAL;      // byte verdicts: the sliced kernels only
-    lb.out8 = out8;
+    const bool sliced = ctx->opt.lat_sliced && n <= (kslot ? ctx->opt.lat_sl_max_keyed : ctx->opt.lat_sl_max);
+    if (out.out8 && !sliced) return GV_EINVAL;  // byte verdicts: the sliced kernels only
+    lb.out8 = out.out8;
     d->routes[kslot ? GV_ROUTE_LAT_KEYED : GV_ROUTE_LAT]++;
     if (kslot) {                                // keyed: 16 lanes per signature (group tables)
       lb.kqt2 = b.kqt2; lb.kzq2 = kzq2; lb.glat = d->glat;
-      if (sliced && !ka && ctx->keys_wide && ctx->lat_kw && d->kqtw && d->kw_qw == GV_KW_QW &&
-          d->kw_ng == GV_KW_NG1 && d->gtab6 && d->keysw >= ctx->keys) {
-        // every slot has its GV_KW_QW-bit one-window wide tables:
-        // k_verify_lat16_kw (no doublings; their own arena: Z rows of stride
-        // kcapw); an arena of the narrow width takes the kn tables below
-        lb.kqt = d->kqtw; lb.kzq = d->kzqw; lb.kqt2 = d->kqtw2; lb.kzq2 = nullptr; lb.kC = (uint32_t)d->kcapw;
-        lb.gtab6 = d->gtab6; lb.kn = 2;
-      } else if (sliced && !ka && ctx->keys_k6 && d->kqt6 && d->gtab6 && d->keys6 >= ctx->keys) {
-        // every slot has its kn tables: k_verify_lat16_kn (6 doublings, G from the 24-bit tables)
-        lb.kqt = d->kqt6; lb.kzq = d->kzq6; lb.kqt2 = d->kqt62; lb.kzq2 = nullptr;
-        lb.gtab6 = d->gtab6; lb.kn = 1;
+      // every slot has its GV_KW_QW-bit one-window wide tables:
+      // k_verify_lat16_kw (no doublings; their own arena: Z rows of stride
+      // kcapw); an arena of another layout, or lat_kw off, takes the kn
+      // tables: k_verify_lat16_kn (6 doublings, G from the 24-bit tables)
+      if (sliced && !ka) {
+        const ArenaTabs t = arena_tabs(ctx, d, ctx->opt.lat_kw && d->kw_qw == GV_KW_QW && d->kw_ng == GV_KW_NG1);
+        if (t.kind != kTabsK4) {
+          lb.kqt = t.kqt; lb.kzq = t.kzq; lb.kqt2 = t.kqt2; lb.kzq2 = nullptr; lb.kC = t.kC;
+          lb.gtab6 = d->gtab6; lb.kn = t.kind;
+        }
       }
       if (sliced) CK(gvk_verify_lat16_sl(&lb, st));
       else CK(gvk_verify_lat16(&lb, st));
@@ -1326,13 +1325,13 @@ int launch(gv_ctx* ctx, Dev* d, Set* s, size_t n, const uint8_t* pub, const uint
     }
   } else {
     uint32_t* sort_base = s->qtab + (via_index ? C : 0);   // keyed: the Q-table region is free (past the looked-up slots)
-    if (!kslot && pub && ctx->group_keys && !no_group && n >= ctx->group_min) {
+    if (!kslot && it.pub33 && ctx->opt.group_keys && !it.no_group && n >= ctx->opt.group_min) {
       rc = group_keys(ctx, d, s, b, n, st, &sort_base);
       if (rc) return rc;
     }
     if (!b.kslot) {                               // the per-item route: G on the unsplit u1 (gfull_item)
-      if (ctx->gfull && ctx->gfull_item && (rc = ensure_gtabf(ctx, d, s, st))) return rc;
-      b.gtabf = ctx->gfull && ctx->gfull_item ? d->gtabf : nullptr;
+      if (ctx->opt.gfull && ctx->opt.gfull_item && (rc = ensure_gtabf(ctx, d, s, st))) return rc;
+      b.gtabf = ctx->opt.gfull && ctx->opt.gfull_item ? d->gtabf : nullptr;
     }
     plan_sort(ctx, s, b, sort_base);
     d->routes[b.kqw == 2 && b.gtab6               ? GV_ROUTE_KG
@@ -1352,7 +1351,7 @@ int launch(gv_ctx* ctx, Dev* d, Set* s, size_t n, const uint8_t* pub, const uint
     d->ring_next = (d->ring_next + 1) % Dev::kRing;
     d->ring_count = std::min(d->ring_count + 1, Dev::kRing);
   }
-  return set_release(s, pipelined ? st_ecm : st);
+  return set_release(s, pipelined ? out.st_ecm : st);
 }
 
 // Device-resident calls.  A caller stream: everything on it, in order.  The
@@ -1374,7 +1373,7 @@ int dev_run(gv_ctx* ctx, Dev* d, void* stream, size_t n, bool keyed, F&& fn) {
     order_after_pipeline(d, (hipStream_t)stream);
     return fn(&d->set[0], (hipStream_t)stream, (hipStream_t) nullptr);
   }
-  if (!ctx->pipeline_dev || n <= (keyed ? ctx->lat_max_keyed : ctx->lat_max)) {
+  if (!ctx->opt.pipeline_dev || n <= (keyed ? ctx->opt.lat_max_keyed : ctx->opt.lat_max)) {
     hipStream_t st = d->set[0].st;
     order_after_pipeline(d, st);
     const int rc = fn(&d->set[0], st, (hipStream_t) nullptr);
@@ -1388,21 +1387,30 @@ int dev_run(gv_ctx* ctx, Dev* d, void* stream, size_t n, bool keyed, F&& fn) {
   // two_ladders: set j's ladder on hi_st[j], so call k+1's ladder starts in
   // call k's tail (its front ran under call k's ladder); the bitmap writes
   // stay in call order through bits_ev.  Else one ladder stream.
-  hipStream_t hs = d->hi_st[ctx->two_ladders ? j : 0];
-  hipEvent_t& hd = d->hi_done[ctx->two_ladders ? j : 0];
+  hipStream_t hs = d->hi_st[ctx->opt.two_ladders ? j : 0];
+  hipEvent_t& hd = d->hi_done[ctx->opt.two_ladders ? j : 0];
   if (d->plain_used) CK(hipStreamWaitEvent(hs, d->plain_done, 0));
   // a gv_dev_keys_find enqueued on the context stream before this call: its
   // slots may be this call's d_slot, which the front kernels read
   if (d->kidx_found_used) CK(hipStreamWaitEvent(d->lo_st[j], d->kidx_found, 0));
-  d->bits_wait = (ctx->two_ladders && d->bits_used) ? d->bits_ev[j ^ 1] : nullptr;
-  d->bits_rec = ctx->two_ladders ? d->bits_ev[j] : nullptr;
+  d->bits_wait = (ctx->opt.two_ladders && d->bits_used) ? d->bits_ev[j ^ 1] : nullptr;
+  d->bits_rec = ctx->opt.two_ladders ? d->bits_ev[j] : nullptr;
   const int rc = fn(&d->set[j], d->lo_st[j], hs);
   d->bits_wait = d->bits_rec = nullptr;
   if (rc) return rc;
   CK(hipEventRecord(hd, hs));
-  d->hi_used[ctx->two_ladders ? j : 0] = true;
-  d->bits_used = ctx->two_ladders;
+  d->hi_used[ctx->opt.two_ladders ? j : 0] = true;
+  d->bits_used = ctx->opt.two_ladders;
   return GV_OK;
+}
+// A device-resident secp256k1 batch: the items' verdicts into the bitmap d_bits.
+int dev_launch(gv_ctx* ctx, Dev* d, void* stream, const Items& it, void* d_bits) {
+  return dev_run(ctx, d, stream, it.n, it.kslot != nullptr, [&](Set* s, hipStream_t st, hipStream_t se) {
+    LaunchOut out;
+    out.bits = (uint64_t*)d_bits;
+    out.st_ecm = se;
+    return launch(ctx, d, s, it, out, st);
+  });
 }
 
 struct HostBatch {
@@ -1489,8 +1497,8 @@ int harvest(Dev* d, Set* s, const HostBatch& hb) {
 // device-resident pipeline's stream priorities, dev_run).  Small batches run
 // one fused kernel on the set stream.
 hipStream_t chunk_ladder(const gv_ctx* ctx, Set* s, size_t cn, bool keyed) {
-  const size_t lmax = keyed ? ctx->lat_max_keyed : ctx->lat_max;
-  return ctx->host_ladder_stream && cn > lmax ? s->lad : nullptr;
+  const size_t lmax = keyed ? ctx->opt.lat_max_keyed : ctx->opt.lat_max;
+  return ctx->opt.host_ladder_stream && cn > lmax ? s->lad : nullptr;
 }
 // The set stream continues after the chunk's ladder (the bitmap's D2H).
 int ladder_join(Set* s) {
@@ -1517,7 +1525,7 @@ int submit(gv_ctx* ctx, Dev* d, Set* s, size_t c0, size_t cn, const HostBatch& h
   uint64_t bmin = 0;
   // h2d_serial: this chunk's copies start after the previous chunk's
   auto h2d_begin = [&]() -> int {
-    if (ctx->h2d_serial && d->last_h2d) CK(hipStreamWaitEvent(s->st, d->last_h2d, 0));
+    if (ctx->opt.h2d_serial && d->last_h2d) CK(hipStreamWaitEvent(s->st, d->last_h2d, 0));
     return GV_OK;
   };
   auto h2d_end = [&]() -> int {
@@ -1525,57 +1533,78 @@ int submit(gv_ctx* ctx, Dev* d, Set* s, size_t c0, size_t cn, const HostBatch& h
     d->last_h2d = s->h2d;
     return GV_OK;
   };
+  // zero-copy small batch: the sliced kernel reads pinned host memory (the
+  // caller's buffers or the staging buffer; messages too: its scalar wave
+  // hashes them) and writes one verdict byte per item to pinned memory (no
+  // H2D / memset / D2H)
+  const size_t lmax = keyed ? ctx->opt.lat_max_keyed : ctx->opt.lat_max;
+  const size_t slmax = keyed ? ctx->opt.lat_sl_max_keyed : ctx->opt.lat_sl_max;
+  const bool zc = ctx->opt.lat_zero_copy && ctx->opt.lat_sliced && cn <= slmax && cn <= lmax && !dslots;
+  auto mark_busy = [&]() { s->busy = true; s->zc = zc; s->c0 = c0; s->cn = cn; return GV_OK; };
+  // the chunk's items: keys or slots, signatures, and at `third` the digests
+  // or (messages) the offsets with the lengths behind them as in_layout puts them
+  auto items_at = [&](const uint8_t* key, const uint8_t* sig, const uint8_t* third, const uint8_t* blob) {
+    Items it;
+    it.n = cn;
+    if (keyed) it.kslot = (const uint32_t*)key;
+    else it.pub33 = key;
+    it.sig64 = sig;
+    if (msgs) {
+      it.blob = blob;
+      it.off = (const uint64_t*)third;
+      it.len = (const uint32_t*)(third + (L.len - L.third));
+    } else {
+      it.dig32 = third;
+    }
+    return it;
+  };
+  auto run_zero_copy = [&](const Items& it) -> int {
+    if ((rc = ensure_pinned(&s->h_out8, &s->h_out8_cap, cn))) return rc;
+    LaunchOut out;
+    out.out8 = s->h_out8;
+    if ((rc = launch(ctx, d, s, it, out, s->st))) return rc;
+    CK(hipEventRecord(s->done, s->st));
+    return mark_busy();
+  };
+  // the inputs are in d_in (H2D enqueued): kernels, then the bitmap's D2H
+  auto run_staged = [&]() -> int {
+    const uint8_t* din = s->d_in;
+    Items it = items_at(din, din + L.sig, din + L.third, s->d_blob);
+    if (dslots) it.kslot = dsl;
+    it.ka = hb.ka;
+    it.no_group = hb.plain;
+    LaunchOut out;
+    out.bits = s->bits;
+    out.st_ecm = chunk_ladder(ctx, s, cn, keyed);
+    if ((rc = launch(ctx, d, s, it, out, s->st)) || (rc = ladder_join(s))) return rc;
+    CK(hipMemcpyAsync(s->h_bits, s->bits, ((cn + 63) / 64) * 8, hipMemcpyDeviceToHost, s->st));
+    CK(hipEventRecord(s->done, s->st));
+    if ((rc = set_release(s, s->st))) return rc;
+    return mark_busy();
+  };
   if (hb.pinned && !msgs) {                 // the caller's pinned buffers: read in place, no staging
     const uint8_t* kp = keyed ? (const uint8_t*)(hb.slots + c0) : hb.pub33 + c0 * 33;
     const uint8_t* sp = hb.sig64 + c0 * 64;
     const uint8_t* dp = hb.dig32 + c0 * 32;
-    const size_t lmax = keyed ? ctx->lat_max_keyed : ctx->lat_max;
-    const size_t slmax = keyed ? ctx->lat_sl_max_keyed : ctx->lat_sl_max;
-    if (ctx->lat_zero_copy && ctx->lat_sliced && cn <= slmax && cn <= lmax && !dslots) {
-      if ((rc = ensure_pinned(&s->h_out8, &s->h_out8_cap, cn))) return rc;
-      rc = launch(ctx, d, s, cn, keyed ? nullptr : kp, sp, dp, nullptr, nullptr, nullptr, nullptr, s->st,
-                  keyed ? (const uint32_t*)kp : nullptr, s->h_out8);
-      if (rc) return rc;
-      CK(hipEventRecord(s->done, s->st));
-      s->busy = true;
-      s->zc = true;
-      s->c0 = c0;
-      s->cn = cn;
-      return GV_OK;
-    }
+    if (zc) return run_zero_copy(items_at(kp, sp, dp, nullptr));
     if ((rc = set_acquire(s, s->st)) || (rc = h2d_begin())) return rc;
     if (!dslots) CK(hipMemcpyAsync(s->d_in, kp, cn * (keyed ? 4 : 33), hipMemcpyHostToDevice, s->st));
     CK(hipMemcpyAsync(s->d_in + L.sig, sp, cn * 64, hipMemcpyHostToDevice, s->st));
     CK(hipMemcpyAsync(s->d_in + L.third, dp, cn * 32, hipMemcpyHostToDevice, s->st));
     if ((rc = h2d_end())) return rc;
-    const uint8_t* din = s->d_in;
-    rc = launch(ctx, d, s, cn, keyed ? nullptr : din, din + L.sig, din + L.third, nullptr, nullptr, nullptr, s->bits,
-                s->st, dslots ? dsl : keyed ? (const uint32_t*)din : nullptr, nullptr, chunk_ladder(ctx, s, cn, keyed),
-                hb.ka, hb.plain);
-    if (rc || (rc = ladder_join(s))) return rc;
-    CK(hipMemcpyAsync(s->h_bits, s->bits, ((cn + 63) / 64) * 8, hipMemcpyDeviceToHost, s->st));
-    CK(hipEventRecord(s->done, s->st));
-    if ((rc = set_release(s, s->st))) return rc;
-    s->busy = true;
-    s->zc = false;
-    s->c0 = c0;
-    s->cn = cn;
-    return GV_OK;
+    return run_staged();
   }
   // (grown: room for the largest layout, pub33 + digests, so a plain chunk
   // after keyed ones does not regrow it either)
   const size_t stage_bytes = grow_c > C ? in_layout(grow_c, false, false).total : L.total;
   if ((rc = ensure_pinned(&s->h_in, &s->h_in_cap, stage_bytes))) return rc;
   h = s->h_in;
-  const size_t lmax0 = keyed ? ctx->lat_max_keyed : ctx->lat_max;
-  const size_t slmax0 = keyed ? ctx->lat_sl_max_keyed : ctx->lat_sl_max;
-  const bool zc_path = ctx->lat_zero_copy && ctx->lat_sliced && cn <= slmax0 && cn <= lmax0 && !dslots;
   bool sent = false;
-  if (!msgs && !zc_path && ctx->stage_pieces > 1 && cn >= 65536) {
+  if (!msgs && !zc && ctx->opt.stage_pieces > 1 && cn >= 65536) {
     // large pageable chunk: staged in pieces, each piece's H2D right behind
     // its copy, so the transfer of piece i overlaps the staging of piece i+1
     if ((rc = set_acquire(s, s->st)) || (rc = h2d_begin())) return rc;
-    const size_t per = round_up((cn + ctx->stage_pieces - 1) / ctx->stage_pieces, 256);
+    const size_t per = round_up((cn + ctx->opt.stage_pieces - 1) / ctx->opt.stage_pieces, 256);
     const size_t kb = keyed ? 4 : 33;
     for (size_t a = 0; a < cn; a += per) {
       const size_t m = std::min(per, cn - a);
@@ -1601,12 +1630,7 @@ int submit(gv_ctx* ctx, Dev* d, Set* s, size_t c0, size_t cn, const HostBatch& h
     } else if (keyed) par_copy(d->pool, h, hb.slots + c0, cn * 4);
     else par_copy(d->pool, h, hb.pub33 + c0 * 33, cn * 33);
     par_copy(d->pool, h + L.sig, hb.sig64 + c0 * 64, cn * 64);
-    uint64_t lo = UINT64_MAX, hi = 0;
-    for (size_t i = c0; i < c0 + cn; ++i) {
-      lo = std::min<uint64_t>(lo, hb.off[i]);
-      hi = std::max<uint64_t>(hi, hb.off[i] + hb.len[i]);
-    }
-    if (lo > hi) lo = hi = 0;
+    const auto [lo, hi] = msg_range(hb.off, hb.len, c0, c0 + cn);
     bmin = lo;
     hb_bytes = hi - lo;
     uint64_t* ro = (uint64_t*)(h + L.third);
@@ -1616,25 +1640,7 @@ int submit(gv_ctx* ctx, Dev* d, Set* s, size_t c0, size_t cn, const HostBatch& h
     if ((rc = ensure_blob(s, hb_bytes))) return rc;
     par_copy(d->pool, s->h_blob, hb.blob + bmin, hb_bytes);
   }
-  const size_t lmax = keyed ? ctx->lat_max_keyed : ctx->lat_max;
-  const size_t slmax = keyed ? ctx->lat_sl_max_keyed : ctx->lat_sl_max;
-  if (ctx->lat_zero_copy && ctx->lat_sliced && cn <= slmax && cn <= lmax && !dslots) {
-    // zero-copy small batch: the kernel reads the pinned staging buffers
-    // (messages too: its scalar wave hashes them) and writes one verdict byte
-    // per item to pinned memory (no H2D / memset / D2H)
-    if ((rc = ensure_pinned(&s->h_out8, &s->h_out8_cap, cn))) return rc;
-    rc = launch(ctx, d, s, cn, keyed ? nullptr : h, h + L.sig, msgs ? nullptr : h + L.third,
-                msgs ? s->h_blob : nullptr, msgs ? (const uint64_t*)(h + L.third) : nullptr,
-                msgs ? (const uint32_t*)(h + L.len) : nullptr, nullptr, s->st,
-                keyed ? (const uint32_t*)h : nullptr, s->h_out8);
-    if (rc) return rc;
-    CK(hipEventRecord(s->done, s->st));
-    s->busy = true;
-    s->zc = true;
-    s->c0 = c0;
-    s->cn = cn;
-    return GV_OK;
-  }
+  if (zc) return run_zero_copy(items_at(h, h + L.sig, h + L.third, s->h_blob));
   if (!sent) {
     if ((rc = set_acquire(s, s->st)) || (rc = h2d_begin())) return rc;
     const size_t from = dslots ? L.sig : 0;   // device slots: no key region to send
@@ -1645,21 +1651,7 @@ int submit(gv_ctx* ctx, Dev* d, Set* s, size_t c0, size_t cn, const HostBatch& h
   } else if (msgs && hb_bytes) {
     CK(hipMemcpyAsync(s->d_blob, s->h_blob, hb_bytes, hipMemcpyHostToDevice, s->st));
   }
-  const uint8_t* din = s->d_in;
-  rc = launch(ctx, d, s, cn, keyed ? nullptr : din, din + L.sig, msgs ? nullptr : din + L.third,
-              msgs ? s->d_blob : nullptr, msgs ? (const uint64_t*)(din + L.third) : nullptr,
-              msgs ? (const uint32_t*)(din + L.len) : nullptr, s->bits, s->st,
-              dslots ? dsl : keyed ? (const uint32_t*)din : nullptr, nullptr, chunk_ladder(ctx, s, cn, keyed), hb.ka,
-              hb.plain);
-  if (rc || (rc = ladder_join(s))) return rc;
-  CK(hipMemcpyAsync(s->h_bits, s->bits, ((cn + 63) / 64) * 8, hipMemcpyDeviceToHost, s->st));
-  CK(hipEventRecord(s->done, s->st));
-  if ((rc = set_release(s, s->st))) return rc;
-  s->busy = true;
-  s->zc = false;
-  s->c0 = c0;
-  s->cn = cn;
-  return GV_OK;
+  return run_staged();
 }
 
 // Does a host slice repeat its keys enough for grouping?  Birthday count on a
@@ -1695,7 +1687,7 @@ bool worth_grouping(const uint8_t* pub33, size_t n, int div) {
 int slice_group(gv_ctx* ctx, Dev* d, size_t lo, size_t n, const HostBatch& hb, KeyArena* ka,
                 const uint32_t** d_slots, Set* g) {
   *d_slots = nullptr;
-  if (!worth_grouping(hb.pub33 + lo * 33, n, ctx->group_div)) return GV_OK;
+  if (!worth_grouping(hb.pub33 + lo * 33, n, ctx->opt.group_div)) return GV_OK;
   const size_t C = round_up(n, 256);
   int rc = ensure_cap(g, grow_items(ctx, C));
   if (rc) return rc;
@@ -1744,23 +1736,23 @@ std::vector<Worker*> workers(const gv_ctx* ctx) {
 std::vector<size_t> chunk_ramp(const gv_ctx* ctx, size_t count, bool pipelined, bool async = false) {
   std::vector<size_t> sz;
   if (pipelined) {
-    const size_t first = async ? ctx->async_chunk : ctx->pipe_chunk;
-    const size_t growth = async ? (size_t)ctx->async_growth : (size_t)ctx->pipe_growth;
-    size_t c = std::min(first, ctx->max_batch), left = count;
+    const size_t first = async ? ctx->opt.async_chunk : ctx->opt.pipe_chunk;
+    const size_t growth = async ? (size_t)ctx->opt.async_growth : (size_t)ctx->opt.pipe_growth;
+    size_t c = std::min(first, ctx->opt.max_batch), left = count;
     while (left) {
       const size_t take = std::min(left, c);
       sz.push_back(take);
       left -= take;
-      c = std::min(ctx->max_batch, c * growth);
+      c = std::min(ctx->opt.max_batch, c * growth);
     }
     const size_t m = sz.size();             // a runt tail joins the chunk before it
-    if (m >= 2 && 2 * sz[m - 1] < sz[m - 2] && sz[m - 1] + sz[m - 2] <= ctx->max_batch) {
+    if (m >= 2 && 2 * sz[m - 1] < sz[m - 2] && sz[m - 1] + sz[m - 2] <= ctx->opt.max_batch) {
       sz[m - 2] += sz[m - 1];
       sz.pop_back();
     }
   } else {
-    const size_t nch = (count + ctx->max_batch - 1) / ctx->max_batch;
-    const size_t chunk = std::min(ctx->max_batch, round_up((count + nch - 1) / nch, 256));
+    const size_t nch = (count + ctx->opt.max_batch - 1) / ctx->opt.max_batch;
+    const size_t chunk = std::min(ctx->opt.max_batch, round_up((count + nch - 1) / nch, 256));
     for (size_t c0 = 0; c0 < count; c0 += chunk) sz.push_back(std::min(chunk, count - c0));
   }
   return sz;
@@ -1783,12 +1775,12 @@ int run_slice(gv_ctx* ctx, Dev* d, size_t lo, size_t hi, const HostBatch& hb) {
     }
   } timer{d, n, t_begin};
   d->last_h2d = nullptr;                          // no earlier chunk of this slice
-  const bool pipelined = n > (hb.slots ? ctx->lat_max_keyed : ctx->lat_max) && ctx->pipe_chunk;
+  const bool pipelined = n > (hb.slots ? ctx->opt.lat_max_keyed : ctx->opt.lat_max) && ctx->opt.pipe_chunk;
   auto chunk_sizes = [&](size_t count) { return chunk_ramp(ctx, count, pipelined); };
   std::vector<size_t> sizes = chunk_sizes(n);
   int rc = GV_OK;
   // a pub33 slice big enough for the pipeline: group its keys once for all chunks
-  const bool try_group = hb.pub33 && !hb.slots && ctx->group_keys && n >= ctx->group_min && sizes.size() > 1;
+  const bool try_group = hb.pub33 && !hb.slots && ctx->opt.group_keys && n >= ctx->opt.group_min && sizes.size() > 1;
   // ... and with slice_plain_first, its first items run the per-item pub33
   // pipeline (their own key parse and Q tables), submitted BEFORE the
   // grouping: their H2D and kernels run while the rest of the slice's keys
@@ -1796,8 +1788,8 @@ int run_slice(gv_ctx* ctx, Dev* d, size_t lo, size_t hi, const HostBatch& hb) {
   // start instead of waiting for the key tables
   HostBatch hp = hb;
   hp.plain = true;
-  const size_t np = try_group && pipelined && ctx->slice_plain_first
-                        ? std::min(round_up(ctx->slice_plain_first, 256), round_up(n / 4, 256)) : 0;
+  const size_t np = try_group && pipelined && ctx->opt.slice_plain_first
+                        ? std::min(round_up(ctx->opt.slice_plain_first, 256), round_up(n / 4, 256)) : 0;
   int k = 0;
   if (np) {
     if ((rc = submit(ctx, d, &d->set[0], lo, np, hp))) return rc;
@@ -1852,7 +1844,7 @@ int ed_slice(gv_ctx* ctx, Dev* d, size_t lo, size_t hi, const EdHost& hb) {
   std::lock_guard<std::mutex> lk(d->mu);
   CK(hipSetDevice(d->id));
   hipStream_t st = d->set[0].st;
-  const size_t chunk = std::min<size_t>(ctx->max_batch, 262144);
+  const size_t chunk = std::min<size_t>(ctx->opt.max_batch, 262144);
   for (size_t c0 = lo; c0 < hi; c0 += chunk) {
     const size_t cn = std::min(chunk, hi - c0), C = round_up(cn, 256);
     int rc = ed_ensure(d, C, st);
@@ -1862,12 +1854,7 @@ int ed_slice(gv_ctx* ctx, Dev* d, size_t lo, size_t hi, const EdHost& hb) {
     if ((rc = ensure_pinned(&d->ed.h_bits, &d->ed.h_bits_cap, C / 8))) return rc;
     if (d->ed.last_st) CK(hipEventSynchronize(d->ed.last));      // the staging buffers are free
     uint8_t* h = d->ed.h_in;
-    uint64_t lo_b = UINT64_MAX, hi_b = 0;
-    for (size_t i = c0; i < c0 + cn; ++i) {
-      lo_b = std::min<uint64_t>(lo_b, hb.off[i]);
-      hi_b = std::max<uint64_t>(hi_b, hb.off[i] + hb.len[i]);
-    }
-    if (lo_b > hi_b) lo_b = hi_b = 0;
+    const auto [lo_b, hi_b] = msg_range(hb.off, hb.len, c0, c0 + cn);
     const size_t nb = hi_b - lo_b;
     if ((rc = ensure_pinned(&d->ed.h_blob, &d->ed.h_blob_cap, nb))) return rc;
     if (nb > d->ed.blob_cap) {
@@ -1888,7 +1875,7 @@ int ed_slice(gv_ctx* ctx, Dev* d, size_t lo, size_t hi, const EdHost& hb) {
     CK(hipMemcpyAsync(d->ed.d_in, h, L.total, hipMemcpyHostToDevice, st));
     if (nb) CK(hipMemcpyAsync(d->ed.d_blob, d->ed.h_blob, nb, hipMemcpyHostToDevice, st));
     const uint8_t* din = d->ed.d_in;
-    rc = ed_launch(ctx->time_kernels, d, cn, din, din + L.sig, d->ed.d_blob, (const uint64_t*)(din + L.off),
+    rc = ed_launch(ctx->opt.time_kernels, d, cn, din, din + L.sig, d->ed.d_blob, (const uint64_t*)(din + L.off),
                    (const uint32_t*)(din + L.len), d->ed.bits, st, ed_group_cfg(ctx));
     if (rc) return rc;
     CK(hipMemcpyAsync(d->ed.h_bits, d->ed.bits, ((cn + 63) / 64) * 8, hipMemcpyDeviceToHost, st));
@@ -1901,7 +1888,7 @@ int ed_slice(gv_ctx* ctx, Dev* d, size_t lo, size_t hi, const EdHost& hb) {
 
 int run_ed_host(gv_ctx* ctx, size_t n, const EdHost& hb) {
   if (!ctx) return GV_EINVAL;
-  if (ctx->fault_inject) return GV_EFAULT;
+  if (ctx->opt.fault_inject) return GV_EFAULT;
   if (n == 0) return GV_OK;
   if (!hb.pub32 || !hb.sig64 || !hb.off || !hb.len || !hb.out_ok) return GV_EINVAL;
   for (size_t i = 0; i < n; ++i)
@@ -1912,7 +1899,7 @@ int run_ed_host(gv_ctx* ctx, size_t n, const EdHost& hb) {
 
 int run_host(gv_ctx* ctx, size_t n, const HostBatch& hb_in) {
   if (!ctx) return GV_EINVAL;
-  if (ctx->fault_inject) return GV_EFAULT;
+  if (ctx->opt.fault_inject) return GV_EFAULT;
   if (n == 0) return GV_OK;
   if ((!hb_in.pub33 && !hb_in.slots) || !hb_in.sig64 || (!hb_in.out_ok && !hb_in.out_bits)) return GV_EINVAL;
   if (!hb_in.dig32 && (!hb_in.blob || !hb_in.off || !hb_in.len)) return GV_EINVAL;
@@ -1995,7 +1982,7 @@ void lane_stream(gv_ctx* ctx, AsyncState* as, size_t k, Dev* d) {
     // after lane_burst slices the lane drains and lets go of d->mu (the
     // Lanes loop calls it again while the queue holds slices): a caller that
     // keeps the queue full cannot starve synchronous calls on this device
-    if (taken >= ctx->lane_burst || !as->pop(k, sl)) break;
+    if (taken >= ctx->opt.lane_burst || !as->pop(k, sl)) break;
     const bool behind = !act.empty();             // an earlier slice's chunks still in flight
     act.emplace_back();
     ActiveSlice& a = act.back();
@@ -2003,11 +1990,11 @@ void lane_stream(gv_ctx* ctx, AsyncState* as, size_t k, Dev* d) {
     a.hr = sl.job->hb;
     const size_t lo = sl.lo, n = sl.hi - sl.lo;
     const HostBatch& hb = sl.job->hb;
-    const bool pipelined = n > (hb.slots ? ctx->lat_max_keyed : ctx->lat_max) && ctx->pipe_chunk;
+    const bool pipelined = n > (hb.slots ? ctx->opt.lat_max_keyed : ctx->opt.lat_max) && ctx->opt.pipe_chunk;
     const bool in_place = hb.pinned;               // read from the caller's pinned buffers, no staging
-    const std::vector<size_t> sizes = ctx->async_whole && in_place ? chunk_ramp(ctx, n, pipelined && !behind)
+    const std::vector<size_t> sizes = ctx->opt.async_whole && in_place ? chunk_ramp(ctx, n, pipelined && !behind)
                                                                    : chunk_ramp(ctx, n, pipelined, true);
-    const bool try_group = hb.pub33 && !hb.slots && ctx->group_keys && n >= ctx->group_min && sizes.size() > 1;
+    const bool try_group = hb.pub33 && !hb.slots && ctx->opt.group_keys && n >= ctx->opt.group_min && sizes.size() > 1;
     if (try_group) {
       Set* g = &d->gset[gflip];
       gflip ^= 1;
@@ -2068,7 +2055,7 @@ struct AsyncQuiesce : gvasync::Lanes<HostBatch>::Quiesce {
 int submit_host(gv_ctx* ctx, size_t n, const HostBatch& hb_in, uint64_t* ticket) {
   if (!ctx || !ticket) return GV_EINVAL;
   *ticket = 0;
-  if (ctx->fault_inject) return GV_EFAULT;
+  if (ctx->opt.fault_inject) return GV_EFAULT;
   if (n > 0) {
     if ((!hb_in.pub33 && !hb_in.slots) || !hb_in.sig64 || (!hb_in.out_ok && !hb_in.out_bits)) return GV_EINVAL;
     if (!hb_in.dig32 && (!hb_in.blob || !hb_in.off || !hb_in.len)) return GV_EINVAL;
@@ -2107,15 +2094,6 @@ void free_set(Set& s) {
   if (s.st) (void)hipStreamDestroy(s.st);
 }
 
-bool parse_size_env(const char* name, size_t* out) {
-  const char* v = getenv(name);
-  if (!v) return false;
-  const long long x = atoll(v);
-  if (x < 256 || (unsigned long long)x > kMaxItems) return false;
-  *out = round_up((size_t)x, 256);
-  return true;
-}
-
 }  // namespace
 
 extern "C" {
@@ -2130,8 +2108,8 @@ extern "C" {
 // default because the ~6 GB it holds per device would come out of the HBM
 // budget that the resident key arena sizes itself from.
 static int presize_devices(gv_ctx* ctx) {
-  const size_t C = round_up(ctx->max_batch, 256);
-  const size_t capU = round_up(std::max<size_t>(C / ctx->group_div, 256), 256);
+  const size_t C = round_up(ctx->opt.max_batch, 256);
+  const size_t capU = round_up(std::max<size_t>(C / ctx->opt.group_div, 256), 256);
   for (Dev* d : ctx->devs) {
     if (hipSetDevice(d->id) != hipSuccess) return GV_EHIP;
     for (Set& s : d->set) {
@@ -2172,84 +2150,19 @@ int gv_open(const int* dev_ids, int n_dev, gv_ctx** out) {
     if (hipGetDeviceProperties(&prop, id) != hipSuccess || prop.warpSize != 64) return GV_ENODEV;
   }
   gv_ctx* ctx = new gv_ctx();
-  parse_size_env("GV_MAX_BATCH", &ctx->max_batch);
-  if (const char* k4 = getenv("GV_KEYED_K4")) ctx->keyed_k4 = strcmp(k4, "0") != 0;
-  if (const char* k6 = getenv("GV_K6")) ctx->k6 = strcmp(k6, "0") != 0;
-  if (const char* kg = getenv("GV_KG")) {
-    const int v = atoi(kg);
-    if (kg_layout_ok(v)) ctx->kg = v;
-  }
-  if (const char* gf = getenv("GV_GFULL")) ctx->gfull = strcmp(gf, "0") != 0;
-  if (const char* tl = getenv("GV_TWO_LADDERS")) ctx->two_ladders = strcmp(tl, "0") != 0;
-  if (const char* ks = getenv("GV_KEYS_SCRATCH")) ctx->keys_scratch = strcmp(ks, "0") != 0;
-  if (const char* sk = getenv("GV_SORT_KEYS")) ctx->sort_keys = strcmp(sk, "0") != 0;
-  if (const char* ek = getenv("GV_ED_KEYED")) ctx->ed_keyed = strcmp(ek, "0") != 0;
-  if (const char* eg = getenv("GV_ED_GROUP")) ctx->ed_group = strcmp(eg, "0") != 0;
-  if (const char* es = getenv("GV_ED_KEYS_SPLIT")) ctx->ed_keys_split = strcmp(es, "0") != 0;
-  if (const char* eb = getenv("GV_ED_BTAB16")) ctx->ed_btab16 = strcmp(eb, "0") != 0;
-  if (const char* er = getenv("GV_ED_GROUP_R64")) ctx->ed_group_r64 = strcmp(er, "0") != 0;
-  if (const char* ls = getenv("GV_LAT_SLICED")) ctx->lat_sliced = strcmp(ls, "0") != 0;
-  if (const char* lr = getenv("GV_LAT_ROWS_MAX")) ctx->lat_rows_max = (size_t)strtoull(lr, nullptr, 10);
-  if (const char* zc = getenv("GV_LAT_ZC")) ctx->lat_zero_copy = strcmp(zc, "0") != 0;
-  if (const char* pl = getenv("GV_PIPELINE")) ctx->pipeline_dev = strcmp(pl, "0") != 0;
-  if (const char* gk = getenv("GV_GROUP_KEYS")) ctx->group_keys = strcmp(gk, "0") != 0;
-  if (const char* sp = getenv("GV_STAGE_PIECES")) ctx->stage_pieces = std::max(1, atoi(sp));
-  if (const char* pf = getenv("GV_SLICE_PLAIN_FIRST")) ctx->slice_plain_first = strtoull(pf, nullptr, 10);
-  if (const char* is = getenv("GV_INV_SMALL")) ctx->inv_small = strcmp(is, "0") != 0;
-  if (const char* gi = getenv("GV_GFULL_ITEM")) ctx->gfull_item = strcmp(gi, "0") != 0;
-  if (const char* hs = getenv("GV_H2D_SERIAL")) ctx->h2d_serial = strcmp(hs, "0") != 0;
-  if (const char* lk = getenv("GV_LAT_KW")) ctx->lat_kw = strcmp(lk, "0") != 0;
-  if (const char* lb = getenv("GV_LANE_BURST")) ctx->lane_burst = (size_t)std::max(1, atoi(lb));
-  if (const char* kk = getenv("GV_KEYS_K6")) ctx->keys_k6 = strcmp(kk, "0") != 0;
-  if (const char* kk = getenv("GV_KEYS_WIDE")) {
-    const int v = atoi(kk);
-    if (v >= 0 && v <= 2) ctx->keys_wide = v;
-  }
-  if (const char* kq = getenv("GV_KEYS_WIDE_QW")) {
-    const int v = atoi(kq);
-    if (v == 0 || gvk_kw_width_ok(v)) ctx->keys_wide_qw = v;
-  }
-  if (const char* km = getenv("GV_KEYS_WIDE_MB")) {
-    const long long v = atoll(km);
-    if (v >= 0 && v <= (long long)(SIZE_MAX >> 20)) ctx->keys_wide_bytes = (size_t)v << 20;
-  }
-  if (const char* hl = getenv("GV_HOST_LADDER_STREAM")) ctx->host_ladder_stream = strcmp(hl, "0") != 0;
-  parse_size_env("GV_ASYNC_CHUNK", &ctx->async_chunk);
-  if (const char* ag = getenv("GV_ASYNC_GROWTH")) ctx->async_growth = std::max(1, std::min(64, atoi(ag)));
-  if (const char* aw = getenv("GV_ASYNC_WHOLE")) ctx->async_whole = strcmp(aw, "0") != 0;
-  if (const char* kc = getenv("GV_KEY_CAP")) {
-    const long long v = atoll(kc);
-    if (v >= 256 && (unsigned long long)v <= kMaxItems) ctx->key_cap = (size_t)v;
-  }
-  if (const char* kc = getenv("GV_ED_KEY_CAP")) {
-    const long long v = atoll(kc);
-    if (v >= 256 && (unsigned long long)v <= kMaxItems) ctx->ed_key_cap = (size_t)v;
-  }
-  if (const char* ew = getenv("GV_ED_KEYS_WIDE")) {
-    const int v = atoi(ew);
-    if (v == 0 || v == 6 || v == 8) ctx->ed_keys_wide = v;
-  }
-  if (const char* ki = getenv("GV_KEYS_INDEX")) ctx->keys_index = !strcmp(ki, "1");
+  gvopt::opt_from_env(ctx->opt, getenv);          // every GV_* option variable, by its row's rule
   {                                             // the index hash's seed: not computable from outside the process
     std::random_device rd;
-    ctx->kidx_seed = ((uint64_t)rd() << 32) ^ (uint64_t)rd() ^
+    ctx->opt.kidx_seed = ((uint64_t)rd() << 32) ^ (uint64_t)rd() ^
                      (uint64_t)std::chrono::steady_clock::now().time_since_epoch().count() * 0x9E3779B97F4A7C15ull ^
                      (uint64_t)(uintptr_t)ctx;
   }
-  if (const char* em = getenv("GV_ED_KEYS_WIDE_MB")) {
-    const long long v = atoll(em);
-    if (v >= 0 && v <= (long long)(SIZE_MAX >> 20)) ctx->ed_keys_wide_bytes = (size_t)v << 20;
-  }
-  if (const char* hb = getenv("GV_HBM_BUDGET_MB")) {
-    const long long v = atoll(hb);
-    if (v > 0) ctx->hbm_budget = (size_t)v << 20;
-  }
-  ctx->stage_threads = gvstage::stage_pool_threads(host_cpus(), (int)ids.size());
+  ctx->opt.stage_threads = gvstage::stage_pool_threads(host_cpus(), (int)ids.size());
   for (size_t k = 0; k < ids.size(); ++k) {
     Dev* d = new Dev();
     d->id = ids[k];
     ctx->devs.push_back(d);
-    d->pool = new Pool(ctx->stage_threads - 1);
+    d->pool = new Pool(ctx->opt.stage_threads - 1);
     if (k > 0) d->worker = new Worker();
     bool ok = hipSetDevice(d->id) == hipSuccess;
     // Stream priorities of the pipelined device-resident calls (env
@@ -2303,7 +2216,7 @@ int gv_open(const int* dev_ids, int n_dev, gv_ctx** out) {
       if (hipSetDevice(d->id) != hipSuccess) { gv_close(ctx); return GV_EHIP; }
       Set* s = &d->set[0];
       int rc = ensure_gtab4(ctx, d, s, s->st, false);
-      if (!rc) rc = ensure_gtab6(ctx, d, s, s->st, ctx->k6 || ctx->keys_k6, false);
+      if (!rc) rc = ensure_gtab6(ctx, d, s, s->st, ctx->opt.k6 || ctx->opt.keys_k6, false);
       if (rc) { gv_close(ctx); return rc; }
     }
     for (Dev* d : ctx->devs)
@@ -2408,7 +2321,7 @@ int gv_verify_msgs_bits(gv_ctx* ctx, size_t n, const uint8_t* pub33, const uint8
 static int dev_common(gv_ctx* ctx, int slot, size_t n, const void* pub, const void* sig, void* bits,
                       Dev** dout) {
   if (!ctx) return GV_EINVAL;
-  if (ctx->fault_inject) return GV_EFAULT;
+  if (ctx->opt.fault_inject) return GV_EFAULT;
   if (slot < 0 || slot >= (int)ctx->devs.size()) return GV_ENODEV;
   if (n == 0) return GV_OK;
   if (!pub || !sig || !bits) return GV_EINVAL;
@@ -2458,10 +2371,10 @@ int gv_dev_verify_digests(gv_ctx* ctx, int dev_slot, size_t n, const void* d_pub
   if (!d_dig32 || ((uintptr_t)d_dig32 & 3)) return GV_EINVAL;
   std::lock_guard<std::mutex> lk(d->mu);
   CK(hipSetDevice(d->id));
-  return dev_run(ctx, d, stream, n, false, [&](Set* s, hipStream_t st, hipStream_t se) {
-    return launch(ctx, d, s, n, (const uint8_t*)d_pub33, (const uint8_t*)d_sig64, (const uint8_t*)d_dig32, nullptr,
-                  nullptr, nullptr, (uint64_t*)d_bits, st, nullptr, nullptr, se, nullptr, false, true);
-  });
+  Items it;
+  it.n = n; it.pub33 = (const uint8_t*)d_pub33; it.sig64 = (const uint8_t*)d_sig64; it.dig32 = (const uint8_t*)d_dig32;
+  it.index = true;
+  return dev_launch(ctx, d, stream, it, d_bits);
 }
 
 int gv_dev_verify_msgs(gv_ctx* ctx, int dev_slot, size_t n, const void* d_pub33, const void* d_sig64,
@@ -2473,11 +2386,11 @@ int gv_dev_verify_msgs(gv_ctx* ctx, int dev_slot, size_t n, const void* d_pub33,
   if (!d_msg_blob || !d_msg_off || !d_msg_len) return GV_EINVAL;
   std::lock_guard<std::mutex> lk(d->mu);
   CK(hipSetDevice(d->id));
-  return dev_run(ctx, d, stream, n, false, [&](Set* s, hipStream_t st, hipStream_t se) {
-    return launch(ctx, d, s, n, (const uint8_t*)d_pub33, (const uint8_t*)d_sig64, nullptr,
-                  (const uint8_t*)d_msg_blob, (const uint64_t*)d_msg_off, (const uint32_t*)d_msg_len,
-                  (uint64_t*)d_bits, st, nullptr, nullptr, se, nullptr, false, true);
-  });
+  Items it;
+  it.n = n; it.pub33 = (const uint8_t*)d_pub33; it.sig64 = (const uint8_t*)d_sig64;
+  it.blob = (const uint8_t*)d_msg_blob; it.off = (const uint64_t*)d_msg_off; it.len = (const uint32_t*)d_msg_len;
+  it.index = true;
+  return dev_launch(ctx, d, stream, it, d_bits);
 }
 
 // ---- ed25519
@@ -2492,12 +2405,7 @@ int ed_unc_small(gv_ctx* ctx, size_t n, const EdHost& hb) {
   hipStream_t st = d->set[0].st;
   int rc = ed_ensure(d, 256, st);                 // the resident comb table of B
   if (rc) return rc;
-  uint64_t lo = UINT64_MAX, hi = 0;
-  for (size_t i = 0; i < n; ++i) {
-    lo = std::min<uint64_t>(lo, hb.off[i]);
-    hi = std::max<uint64_t>(hi, hb.off[i] + hb.len[i]);
-  }
-  if (lo > hi) lo = hi = 0;
+  const auto [lo, hi] = msg_range(hb.off, hb.len, 0, n);
   const size_t o_sig = round_up(n * 32, 64), o_off = o_sig + n * 64, o_len = o_off + n * 8, o_out = o_len + n * 4,
                o_blob = round_up(o_out + n, 64), total = o_blob + (hi - lo);
   if ((rc = ensure_pinned(&d->edl_h, &d->edl_h_cap, total))) return rc;
@@ -2508,16 +2416,9 @@ int ed_unc_small(gv_ctx* ctx, size_t n, const EdHost& hb) {
   for (size_t i = 0; i < n; ++i) ro[i] = hb.off[i] - lo;
   memcpy(h + o_len, hb.len, n * 4);
   if (hi > lo) memcpy(h + o_blob, hb.blob + lo, hi - lo);
-  gvk_edl b;
-  memset(&b, 0, sizeof b);
-  b.n = (uint32_t)n;
-  b.pub32 = h;
-  b.sig64 = h + o_sig;
-  b.msg_blob = h + o_blob;
-  b.msg_off = (const uint64_t*)(h + o_off);
-  b.msg_len = (const uint32_t*)(h + o_len);
-  b.btab = d->edtab;
-  b.out8 = h + o_out;
+  gvk_edl b = fill_edl(d, n, 0, nullptr, h + o_sig, h + o_blob, (const uint64_t*)(h + o_off),
+                       (const uint32_t*)(h + o_len), h + o_out);
+  b.pub32 = h;                                    // uncached: the keys themselves (k_ed_lat_unc reads no arena)
   d->routes[GV_ROUTE_ED_LAT]++;
   CK(gvk_ed_lat_unc(&b, st));
   CK(hipStreamSynchronize(st));
@@ -2530,7 +2431,7 @@ int gv_verify_ed25519_msgs(gv_ctx* ctx, size_t n, const uint8_t* pub32, const ui
                            const uint8_t* msg_blob, const uint64_t* msg_off, const uint32_t* msg_len,
                            uint8_t* out_ok) {
   const EdHost hb{pub32, sig64, msg_blob, msg_off, msg_len, out_ok};
-  if (ctx && !ctx->fault_inject && n && n <= ctx->ed_unc_lat_max && pub32 && sig64 && msg_off && msg_len && out_ok) {
+  if (ctx && !ctx->opt.fault_inject && n && n <= ctx->opt.ed_unc_lat_max && pub32 && sig64 && msg_off && msg_len && out_ok) {
     for (size_t i = 0; i < n; ++i)
       if (msg_len[i] && !msg_blob) return GV_EINVAL;
     return ed_unc_small(ctx, n, hb);
@@ -2549,7 +2450,7 @@ int gv_dev_verify_ed25519_msgs(gv_ctx* ctx, int dev_slot, size_t n, const void* 
   CK(hipSetDevice(d->id));
   hipStream_t st = stream ? (hipStream_t)stream : d->set[0].st;
   order_after_pipeline(d, st);
-  return ed_launch(ctx->time_kernels, d, n, (const uint8_t*)d_pub32, (const uint8_t*)d_sig64, (const uint8_t*)d_msg_blob,
+  return ed_launch(ctx->opt.time_kernels, d, n, (const uint8_t*)d_pub32, (const uint8_t*)d_sig64, (const uint8_t*)d_msg_blob,
                    (const uint64_t*)d_msg_off, (const uint32_t*)d_msg_len, (uint64_t*)d_bits, st, ed_group_cfg(ctx));
 }
 
@@ -2570,7 +2471,7 @@ hipError_t stage_slots(Set* s, size_t C, const uint32_t* slots, size_t cn, hipSt
 // key are ~12x its (GV_KN_ARENA_NG groups of 32 entries): smaller chunks.
 int build_k4k6(gv_ctx* ctx, Dev* d, Set* s, hipStream_t st, const uint8_t* pub33, size_t n, size_t base,
                const uint32_t* slots, bool k4, bool k6) {
-  const size_t step = k6 ? std::min<size_t>(ctx->max_batch, 32768) : ctx->max_batch;
+  const size_t step = k6 ? std::min<size_t>(ctx->opt.max_batch, 32768) : ctx->opt.max_batch;
   int rc;
   for (size_t c0 = 0; c0 < n; c0 += step) {
     const size_t cn = std::min(step, n - c0);
@@ -2588,13 +2489,13 @@ int build_k4k6(gv_ctx* ctx, Dev* d, Set* s, hipStream_t st, const uint8_t* pub33
     const uint32_t b0 = slots ? 0u : (uint32_t)(base + c0);
     if (k4) {
       const size_t room = (size_t)GV_QTAB_WORDS * s->cap;
-      const int qe4 = ctx->keys_scratch && gvk_keys_scratch_words((uint32_t)cn, GV_LGRP, GV_QTAB_N, 1) <= room;
+      const int qe4 = ctx->opt.keys_scratch && gvk_keys_scratch_words((uint32_t)cn, GV_LGRP, GV_QTAB_N, 1) <= room;
       CK(gvk_keys_build(s->d_in, (uint32_t)cn, (uint32_t)C, s->in_x, s->in_pfx, s->in_r, s->in_s, s->in_e, s->qtab,
                         qe4, b0, d_slots, d->kqt, d->kzq, (uint32_t)d->kcap, d->kok, d->kqt2, d->kzq2, st));
     }
     if (k6)
       CK(gvk_keys_build6(s->d_in, (uint32_t)cn, (uint32_t)C, s->in_x, s->in_pfx, s->in_r, s->in_s, s->in_e, s->qtab,
-                         ctx->keys_scratch ? 1 : 0, b0, d_slots, d->kqt6, d->kzq6, (uint32_t)d->kcap, d->kok,
+                         ctx->opt.keys_scratch ? 1 : 0, b0, d_slots, d->kqt6, d->kzq6, (uint32_t)d->kcap, d->kok,
                          d->kqt62, d->kzq62, st));
     if ((rc = set_release(s, st))) return rc;
     CK(hipStreamSynchronize(st));              // the caller's pub33 chunk is read by then
@@ -2609,12 +2510,12 @@ int build_k4k6(gv_ctx* ctx, Dev* d, Set* s, hipStream_t st, const uint8_t* pub33
 // rides behind its pub33 in the staged-input region).  The caller holds d->mu.
 int build_wide(gv_ctx* ctx, Dev* d, Set* s, hipStream_t st, const uint8_t* pub33, size_t n, size_t base,
                const uint32_t* slots = nullptr) {
-  const size_t stepw = std::min<size_t>(ctx->max_batch, std::max<size_t>(256, 32768 / (size_t)d->kw_ng / 256 * 256));
+  const size_t stepw = std::min<size_t>(ctx->opt.max_batch, std::max<size_t>(256, 32768 / (size_t)d->kw_ng / 256 * 256));
   int rc;
   for (size_t c0 = 0; c0 < n; c0 += stepw) {
     const size_t cn = std::min(stepw, n - c0);
     const size_t C = round_up(cn, 256);
-    const int qew = ctx->keys_scratch ? 1 : 0;
+    const int qew = ctx->opt.keys_scratch ? 1 : 0;
     const size_t ww = gvk_keys_scratch_words((uint32_t)cn, d->kw_ng, gvk_kw_nt(d->kw_qw), qew);
     const size_t Cs = std::max(C, round_up(ww / GV_QTAB_WORDS + 1, 256));
     if ((rc = ensure_cap(s, Cs))) return rc;
@@ -2639,8 +2540,8 @@ int build_wide(gv_ctx* ctx, Dev* d, Set* s, hipStream_t st, const uint8_t* pub33
 int kidx_write(gv_ctx* ctx, Dev* d, Set* s, hipStream_t st, const uint8_t* pub33, size_t n, size_t base,
                const uint32_t* slots, bool put) {
   int rc;
-  for (size_t c0 = 0; c0 < n; c0 += ctx->max_batch) {
-    const size_t cn = std::min(ctx->max_batch, n - c0);
+  for (size_t c0 = 0; c0 < n; c0 += ctx->opt.max_batch) {
+    const size_t cn = std::min(ctx->opt.max_batch, n - c0);
     const size_t C = round_up(cn, 256);
     if ((rc = ensure_cap(s, C))) return rc;
     if ((rc = set_acquire(s, st))) return rc;
@@ -2651,7 +2552,7 @@ int kidx_write(gv_ctx* ctx, Dev* d, Set* s, hipStream_t st, const uint8_t* pub33
     CK(gvk_kidx_rows(s->d_in, (uint32_t)cn, b0, d_slots, d->kidx_rows, st));
     ctx->kidx_launches++;
     if (put) {
-      CK(gvk_kidx_put(d->kidx_tab, (uint32_t)d->kidx_T, d->kidx_rows, (uint32_t)cn, b0, d_slots, ctx->kidx_seed,
+      CK(gvk_kidx_put(d->kidx_tab, (uint32_t)d->kidx_T, d->kidx_rows, (uint32_t)cn, b0, d_slots, ctx->opt.kidx_seed,
                       d->kidx_cnt, st));
       ctx->kidx_launches++;
     }
@@ -2741,7 +2642,7 @@ int gv_keys_load(gv_ctx* ctx, size_t n, const uint8_t* pub33, uint32_t* slot_out
       d->kidx_keys = 0;
       d->kidx_left_out = 0;
       d->kidx_failed = false;
-      d->kidx_on = ctx->keys_index;             // the arena takes the option here
+      d->kidx_on = ctx->opt.keys_index;             // the arena takes the option here
     }
     // an earlier load that failed on a later device left this one's index ahead
     // of the arena (rows of keys no slot holds): no index until gv_keys_reset
@@ -2749,10 +2650,10 @@ int gv_keys_load(gv_ctx* ctx, size_t n, const uint8_t* pub33, uint32_t* slot_out
     // the k6 tables too when their G tables exist (or can be built) and the
     // arena has room for them (else k4 only: the k4 route serves the slots)
     int rc = ensure_gtab4(ctx, d, s, st);
-    if (!rc) rc = ensure_gtab6(ctx, d, s, st, ctx->keys_k6 || ctx->keys_wide);
+    if (!rc) rc = ensure_gtab6(ctx, d, s, st, ctx->opt.keys_k6 || ctx->opt.keys_wide);
     if (rc) return rc;
-    bool k6 = ctx->keys_k6 && d->gtab6 && d->keys6 == base;
-    if ((rc = ensure_keys(d, base + n, base, st, ctx->key_cap, ctx->hbm_budget, &k6))) return rc;
+    bool k6 = ctx->opt.keys_k6 && d->gtab6 && d->keys6 == base;
+    if ((rc = ensure_keys(d, base + n, base, st, ctx->opt.key_cap, ctx->opt.hbm_budget, &k6))) return rc;
     if ((rc = build_k4k6(ctx, d, s, st, pub33, n, base, nullptr, true, k6))) return rc;
     if (k6) d->keys6 = base + n;
     // the wide-window tables: while every earlier slot has them and memory
@@ -2763,9 +2664,9 @@ int gv_keys_load(gv_ctx* ctx, size_t n, const uint8_t* pub33, uint32_t* slot_out
     // one 11-bit window per group (12 tables of 64 KiB per key), two (6), one
     // 9-bit window per group (15 tables of 16 KiB), two (8): the loaded slots'
     // keys are read back from the k4 tables and rebuilt from slot 0.
-    if (ctx->keys_wide && d->gtab6 && d->keysw == base && !d->kw_full) {
-      const int only_qw = ctx->keys_wide_qw;
-      int li = wide_layout_next(0, only_qw, ctx->keys_wide == 2 ? 1 : 2);
+    if (ctx->opt.keys_wide && d->gtab6 && d->keysw == base && !d->kw_full) {
+      const int only_qw = ctx->opt.keys_wide_qw;
+      int li = wide_layout_next(0, only_qw, ctx->opt.keys_wide == 2 ? 1 : 2);
       if (base != 0 && d->kw_ng) {                // a running arena keeps its layout
         li = kWideLayoutCount;
         for (int i = 0; i < kWideLayoutCount; ++i)
@@ -2776,11 +2677,11 @@ int gv_keys_load(gv_ctx* ctx, size_t n, const uint8_t* pub33, uint32_t* slot_out
         d->kw_ng = kWideLayouts[li].ng;
       }
       // the ed25519 arena's growth to ed_key_cap is reserved too (72 KB per key)
-      const size_t ed_room = (ctx->ed_key_cap > d->ekcap ? ctx->ed_key_cap - d->ekcap : 0) *
+      const size_t ed_room = (ctx->opt.ed_key_cap > d->ekcap ? ctx->opt.ed_key_cap - d->ekcap : 0) *
                              ((size_t)GV_EDK_WORDS + 8 + 1) * 4;
       bool ok = li < kWideLayoutCount &&
-                ensure_keys_wide(d, base + n, base, st, ctx->key_cap, ctx->hbm_budget, ed_room,
-                                 ctx->keys_wide_bytes, ctx->keys_wide1_cap);
+                ensure_keys_wide(d, base + n, base, st, ctx->opt.key_cap, ctx->opt.hbm_budget, ed_room,
+                                 ctx->opt.keys_wide_bytes, ctx->opt.keys_wide1_cap);
       // (a failed read-back only stops the wide tables: the k6 ones serve)
       std::vector<uint8_t> old_pub;
       bool moved = false;
@@ -2791,7 +2692,7 @@ int gv_keys_load(gv_ctx* ctx, size_t n, const uint8_t* pub33, uint32_t* slot_out
         d->kw_qw = kWideLayouts[li].qw;
         d->kw_ng = kWideLayouts[li].ng;
         if (!back) break;
-        ok = ensure_keys_wide(d, base + n, 0, st, ctx->key_cap, ctx->hbm_budget, ed_room, ctx->keys_wide_bytes);
+        ok = ensure_keys_wide(d, base + n, 0, st, ctx->opt.key_cap, ctx->opt.hbm_budget, ed_room, ctx->opt.keys_wide_bytes);
       }
       // a failed rebuild only stops the wide tables (the k6 / k4 ones serve
       // every slot): never a gv_keys_load error
@@ -2807,7 +2708,7 @@ int gv_keys_load(gv_ctx* ctx, size_t n, const uint8_t* pub33, uint32_t* slot_out
     }
     // the pubkey index, while every earlier slot is in it: a refused
     // allocation or a failed launch only stops it on this device
-    if (ctx->keys_index && d->kidx_on && !d->kidx_failed && d->kidx_keys == base) {
+    if (ctx->opt.keys_index && d->kidx_on && !d->kidx_failed && d->kidx_keys == base) {
       if (kidx_load(ctx, d, s, st, pub33, n, base) != GV_OK) kidx_stop(d);
       else d->kidx_keys = base + n;
     }
@@ -2937,7 +2838,7 @@ int ed_build(gv_ctx* ctx, Dev* d, hipStream_t st, const uint8_t* pub32, size_t n
   uint8_t* dp = nullptr;
   const size_t o_sl = round_up(n * 32, 256), o_wb = o_sl + (slots ? round_up(n * 4, 256) : 0);
   const size_t wb_bytes = n * 64 * 36 * 4;
-  const bool split = ctx->ed_keys_split && wb_bytes <= ((size_t)1 << 30);
+  const bool split = ctx->opt.ed_keys_split && wb_bytes <= ((size_t)1 << 30);
   if (hipMalloc(&dp, o_wb + (split ? wb_bytes : 0)) != hipSuccess) return GV_ENOMEM;
   const bool ok = hipMemcpyAsync(dp, pub32, n * 32, hipMemcpyHostToDevice, st) == hipSuccess &&
                   (!slots || hipMemcpyAsync(dp + o_sl, slots, n * 4, hipMemcpyHostToDevice, st) == hipSuccess) &&
@@ -2971,18 +2872,18 @@ void free_ed_keys_wide(Dev* d) {
 // ed_key_cap, 8 GiB of batch scratch), or when an allocation fails.
 bool ensure_ed_keys_wide(gv_ctx* ctx, Dev* d, size_t need, size_t used, hipStream_t st) {
   if (need <= d->ekcapw) return true;
-  const size_t cap_limit = ctx->ed_key_cap;
+  const size_t cap_limit = ctx->opt.ed_key_cap;
   const size_t grow = d->ekcapw >= cap_limit ? need
                                              : std::min<size_t>(2 * d->ekcapw, std::max<size_t>(need, cap_limit));
   const size_t cap = round_up(std::max<size_t>({need, grow, 256}), 256);
   const size_t slot_b = ed_wide_slot_bytes(d->ekw_rb);
   if (!slot_b) return false;
-  if (ctx->ed_keys_wide_bytes && cap * slot_b > ctx->ed_keys_wide_bytes) return false;
-  if (d->opt_bytes + cap * slot_b > ctx->hbm_budget) return false;
+  if (ctx->opt.ed_keys_wide_bytes && cap * slot_b > ctx->opt.ed_keys_wide_bytes) return false;
+  if (d->opt_bytes + cap * slot_b > ctx->opt.hbm_budget) return false;
   size_t free_b = 0, total_b = 0;
   if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) return false;
-  const size_t reserve = (ctx->key_cap > d->kcap ? ctx->key_cap - d->kcap : 0) * key_slot_bytes(true) +
-                         (ctx->ed_key_cap > d->ekcap ? ctx->ed_key_cap - d->ekcap : 0) *
+  const size_t reserve = (ctx->opt.key_cap > d->kcap ? ctx->opt.key_cap - d->kcap : 0) * key_slot_bytes(true) +
+                         (ctx->opt.ed_key_cap > d->ekcap ? ctx->opt.ed_key_cap - d->ekcap : 0) *
                              ((size_t)GV_EDK_WORDS + 8 + 1) * 4 +
                          (size_t(8) << 30);
   if (free_b < cap * slot_b + reserve) return false;
@@ -3057,18 +2958,18 @@ int gv_ed_keys_load(gv_ctx* ctx, size_t n, const uint8_t* pub32, uint32_t* slot_
     if (base == 0) {                            // after gv_ed_keys_reset the slots are rewritten from 0
       d->ekeysw = 0;
       d->ekw_full = false;
-      if (d->ekw_rb != ctx->ed_keys_wide) {     // the option is read again: another radix, or none
+      if (d->ekw_rb != ctx->opt.ed_keys_wide) {     // the option is read again: another radix, or none
         free_ed_keys_wide(d);
-        d->ekw_rb = ctx->ed_keys_wide;
+        d->ekw_rb = ctx->opt.ed_keys_wide;
       }
     }
-    rc = ensure_ed_keys(d, base + n, base, st, ctx->ed_key_cap);
+    rc = ensure_ed_keys(d, base + n, base, st, ctx->opt.ed_key_cap);
     if (!rc) rc = ed_build(ctx, d, st, pub32, n, base, nullptr);
     if (rc) return rc;
     // the wide tables while every earlier slot has them and memory holds the
     // grown arena; a refusal or a failed build frees them and stops them until
     // gv_ed_keys_reset (every slot keeps its radix-16 table): never an error
-    if (ctx->ed_keys_wide && d->ekw_rb && d->ekeysw == base && !d->ekw_full) {
+    if (ctx->opt.ed_keys_wide && d->ekw_rb && d->ekeysw == base && !d->ekw_full) {
       if (ensure_ed_keys_wide(ctx, d, base + n, base, st) && ed_build_wide(d, st, pub32, n, base, nullptr) == GV_OK) {
         d->ekeysw = base + n;
       } else {
@@ -3192,12 +3093,6 @@ int ensure_dev(uint8_t** p, size_t* cap, size_t bytes) {
   return GV_OK;
 }
 
-// k_ed_keyed reads d's wide tables when every slot of the arena has them
-// (option "ed_keys_wide" still on), else the radix-16 ones.
-bool ed_wide_serves(const gv_ctx* ctx, const Dev* d, size_t kcount) {
-  return ctx->ed_keys_wide && d->ektabw && d->ekw_rb && kcount && d->ekeysw >= kcount && d->ekcapw >= kcount;
-}
-
 // Items [lo, hi) of a large keyed ed25519 batch on one device (k_ed_keyed):
 // chunks alternate between two buffers / streams, so the host staging of
 // chunk i + 1 (slots, signatures, offsets, messages into pinned memory) runs
@@ -3208,7 +3103,7 @@ int ed_keyed_slice(gv_ctx* ctx, Dev* d, size_t lo, size_t hi, const EdKeyedHost&
   int rc = ed_ensure(d, 256, d->set[0].st);       // the resident comb table of B
   if (rc) return rc;
   const size_t n = hi - lo;
-  const size_t chunk = std::min<size_t>(ctx->max_batch, n > 131072 ? round_up((n + 3) / 4, 256) : n);
+  const size_t chunk = std::min<size_t>(ctx->opt.max_batch, n > 131072 ? round_up((n + 3) / 4, 256) : n);
   const size_t nb = kcount + 1, tb = gvk_sort_temp_bytes((uint32_t)nb);
   struct Pending { size_t c0 = 0, cn = 0, o_out = 0; bool busy = false; } pend[2];
   auto finish = [&](int k) -> int {                // chunk on buffer k: wait, copy the verdicts out
@@ -3223,15 +3118,10 @@ int ed_keyed_slice(gv_ctx* ctx, Dev* d, size_t lo, size_t hi, const EdKeyedHost&
     if (rc) return rc;
     hipStream_t st = d->set[k].st;
     const size_t cn = std::min(chunk, hi - c0);
-    uint64_t lo_b = UINT64_MAX, hi_b = 0;
-    for (size_t i = c0; i < c0 + cn; ++i) {
-      lo_b = std::min<uint64_t>(lo_b, hb.off[i]);
-      hi_b = std::max<uint64_t>(hi_b, hb.off[i] + hb.len[i]);
-    }
-    if (lo_b > hi_b) lo_b = hi_b = 0;
+    const auto [lo_b, hi_b] = msg_range(hb.off, hb.len, c0, c0 + cn);
     const size_t o_sig = round_up(cn * 4, 256), o_off = o_sig + cn * 64, o_len = o_off + cn * 8,
                  o_out = o_len + cn * 4, o_blob = round_up(o_out + cn, 256), total = o_blob + (hi_b - lo_b);
-    const size_t C = round_up(cn, 256), sw = 3 * C + 2 * round_up(nb, 64) + round_up(tb / 4 + 1, 64);
+    const size_t C = round_up(cn, 256), sw = sort_words(C, nb, tb);
     if ((rc = ensure_pinned(&d->edk_h[k], &d->edk_h_cap[k], total))) return rc;
     if ((rc = ensure_dev(&d->edk_d[k], &d->edk_d_cap[k], total))) return rc;
     if ((rc = ensure_dev((uint8_t**)&d->edk_s[k], &d->edk_s_cap[k], sw * 4))) return rc;
@@ -3245,37 +3135,12 @@ int ed_keyed_slice(gv_ctx* ctx, Dev* d, size_t lo, size_t hi, const EdKeyedHost&
     if (hi_b > lo_b) par_copy(d->pool, h + o_blob, hb.blob + lo_b, hi_b - lo_b);
     uint8_t* dd = d->edk_d[k];
     CK(hipMemcpyAsync(dd, h, total, hipMemcpyHostToDevice, st));
-    uint32_t* p = d->edk_s[k];
-    gvk_sort so;
-    so.pos = p; p += C;
-    so.perm = p; p += C;
-    so.kslot = p; p += C;
-    so.bits = nullptr;
-    so.cnt = p; p += round_up(nb, 64);
-    so.off = p; p += round_up(nb, 64);
-    so.temp = p;
-    so.temp_bytes = tb;
-    if (ctx->sort_keys) CK(gvk_sort_slots(&so, (uint32_t)cn, (const uint32_t*)dd, (uint32_t)kcount, st));
-    gvk_edk b;
-    memset(&b, 0, sizeof b);
-    b.n = (uint32_t)cn;
-    b.perm = ctx->sort_keys ? so.perm : nullptr;
-    b.slot = (const uint32_t*)dd;
-    b.sig64 = dd + o_sig;
-    b.msg_blob = dd + o_blob;
-    b.msg_off = (const uint64_t*)(dd + o_off);
-    b.msg_len = (const uint32_t*)(dd + o_len);
-    const bool wide = ed_wide_serves(ctx, d, kcount);
-    b.ktab = wide ? d->ektabw : d->ektab;
-    b.rb = wide ? d->ekw_rb : 4;
-    b.kpub = d->ekpub;
-    b.kok = d->ekok;
-    b.kcount = (uint32_t)kcount;
-    b.btab = d->edtab;
-    b.btab16 = ed_btab16(d, ctx->ed_btab16, st);
-    b.out8 = dd + o_out;
+    const gvk_sort so = carve_sort(d->edk_s[k], C, nb, tb);
+    if (ctx->opt.sort_keys) CK(gvk_sort_slots(&so, (uint32_t)cn, (const uint32_t*)dd, (uint32_t)kcount, st));
+    const gvk_edk b = fill_edk(ctx, d, cn, kcount, ctx->opt.sort_keys ? so.perm : nullptr, (const uint32_t*)dd, dd + o_sig,
+                               dd + o_blob, (const uint64_t*)(dd + o_off), (const uint32_t*)(dd + o_len), dd + o_out,
+                               ed_btab16(d, ctx->opt.ed_btab16, st));
     CK(gvk_ed_keyed(&b, st));
-    if (wide) ctx->ed_keyed_wide.fetch_add(1);
     CK(hipMemcpyAsync(h + o_out, dd + o_out, cn, hipMemcpyDeviceToHost, st));
     pend[k] = Pending{c0, cn, o_out, true};
     return GV_OK;
@@ -3298,7 +3163,7 @@ int gv_verify_ed25519_msgs_keyed(gv_ctx* ctx, size_t n, const uint32_t* slot, co
                                  const uint8_t* msg_blob, const uint64_t* msg_off, const uint32_t* msg_len,
                                  uint8_t* out_ok) {
   if (!ctx) return GV_EINVAL;
-  if (ctx->fault_inject) return GV_EFAULT;
+  if (ctx->opt.fault_inject) return GV_EFAULT;
   if (n == 0) return GV_OK;
   if (!slot || !sig64 || !msg_off || !msg_len || !out_ok) return GV_EINVAL;
   for (size_t i = 0; i < n; ++i)
@@ -3310,7 +3175,7 @@ int gv_verify_ed25519_msgs_keyed(gv_ctx* ctx, size_t n, const uint32_t* slot, co
   std::lock_guard<std::mutex> kl(ctx->ed_keys_mu);
   const size_t kcount = ctx->ed_keys;
   {
-    if (n > ctx->ed_lat_max && kcount && ctx->ed_keyed) {
+    if (n > ctx->opt.ed_lat_max && kcount && ctx->opt.ed_keyed) {
       // large batches: one signature per lane against the key tables
       // (k_ed_keyed), split over the devices like run_ed_host
       const EdKeyedHost hb{slot, sig64, msg_blob, msg_off, msg_len, out_ok};
@@ -3318,7 +3183,7 @@ int gv_verify_ed25519_msgs_keyed(gv_ctx* ctx, size_t n, const uint32_t* slot, co
         return ed_keyed_slice(ctx, ctx->devs[k], lo, hi, hb, kcount);
       });
     }
-    if (n > ctx->ed_lat_max || kcount == 0) {
+    if (n > ctx->opt.ed_lat_max || kcount == 0) {
       // large batches (ed_keyed 0): the throughput kernels over the slots' raw keys
       std::vector<uint8_t> pub(n * 32, 0);
       for (size_t i = 0; i < n; ++i)
@@ -3336,12 +3201,7 @@ int gv_verify_ed25519_msgs_keyed(gv_ctx* ctx, size_t n, const uint32_t* slot, co
   hipStream_t st = d->set[0].st;
   int rc = ed_ensure(d, 256, st);                 // the resident comb table of B
   if (rc) return rc;
-  uint64_t lo = UINT64_MAX, hi = 0;
-  for (size_t i = 0; i < n; ++i) {
-    lo = std::min<uint64_t>(lo, msg_off[i]);
-    hi = std::max<uint64_t>(hi, msg_off[i] + msg_len[i]);
-  }
-  if (lo > hi) lo = hi = 0;
+  const auto [lo, hi] = msg_range(msg_off, msg_len, 0, n);
   // zero-copy: the kernel reads the pinned inputs and writes verdict bytes
   const size_t o_sig = round_up(n * 4, 64), o_off = o_sig + n * 64, o_len = o_off + n * 8, o_out = o_len + n * 4,
                o_blob = round_up(o_out + n, 64), total = o_blob + (hi - lo);
@@ -3353,20 +3213,8 @@ int gv_verify_ed25519_msgs_keyed(gv_ctx* ctx, size_t n, const uint32_t* slot, co
   for (size_t i = 0; i < n; ++i) ro[i] = msg_off[i] - lo;
   memcpy(h + o_len, msg_len, n * 4);
   if (hi > lo) memcpy(h + o_blob, msg_blob + lo, hi - lo);
-  gvk_edl b;
-  memset(&b, 0, sizeof b);
-  b.n = (uint32_t)n;
-  b.slot = (const uint32_t*)h;
-  b.sig64 = h + o_sig;
-  b.msg_blob = h + o_blob;
-  b.msg_off = (const uint64_t*)(h + o_off);
-  b.msg_len = (const uint32_t*)(h + o_len);
-  b.ktab = d->ektab;
-  b.kpub = d->ekpub;
-  b.kok = d->ekok;
-  b.kcount = (uint32_t)kcount;
-  b.btab = d->edtab;
-  b.out8 = h + o_out;
+  const gvk_edl b = fill_edl(d, n, kcount, (const uint32_t*)h, h + o_sig, h + o_blob, (const uint64_t*)(h + o_off),
+                             (const uint32_t*)(h + o_len), h + o_out);
   CK(gvk_ed_lat(&b, st));
   CK(hipStreamSynchronize(st));
   memcpy(out_ok, h + o_out, n);
@@ -3400,10 +3248,10 @@ int gv_dev_verify_ed25519_msgs_keyed(gv_ctx* ctx, int dev_slot, size_t n, const 
   }
   if ((rc = ed_ensure(d, 256, st))) return rc;    // the resident comb table of B
   if (!d->edkd_last) CK(hipEventCreateWithFlags(&d->edkd_last, hipEventDisableTiming));
-  const bool small = n <= ctx->ed_lat_max;
-  const bool sorted = !small && ctx->sort_keys;
+  const bool small = n <= ctx->opt.ed_lat_max;
+  const bool sorted = !small && ctx->opt.sort_keys;
   const size_t C = round_up(n, 256), nb = kcount + 1, tb = gvk_sort_temp_bytes((uint32_t)nb);
-  const size_t sw = sorted ? 3 * C + 2 * round_up(nb, 64) + round_up(tb / 4 + 1, 64) : 0;
+  const size_t sw = sorted ? sort_words(C, nb, tb) : 0;
   if (C + sw * 4 > d->edkd_s_cap) {               // the scratch grows: the last batch on it first
     if (d->edkd_last_st) CK(hipEventSynchronize(d->edkd_last));
     if ((rc = ensure_dev(&d->edkd_s, &d->edkd_s_cap, C + sw * 4))) return rc;
@@ -3411,56 +3259,21 @@ int gv_dev_verify_ed25519_msgs_keyed(gv_ctx* ctx, int dev_slot, size_t n, const 
   if (d->edkd_last_st && d->edkd_last_st != st) CK(hipStreamWaitEvent(st, d->edkd_last, 0));
   uint8_t* out8 = d->edkd_s;
   if (small) {
-    gvk_edl b;
-    memset(&b, 0, sizeof b);
-    b.n = (uint32_t)n;
-    b.slot = (const uint32_t*)d_slot;
-    b.sig64 = (const uint8_t*)d_sig64;
-    b.msg_blob = (const uint8_t*)d_msg_blob;
-    b.msg_off = (const uint64_t*)d_msg_off;
-    b.msg_len = (const uint32_t*)d_msg_len;
-    b.ktab = d->ektab;
-    b.kpub = d->ekpub;
-    b.kok = d->ekok;
-    b.kcount = (uint32_t)kcount;
-    b.btab = d->edtab;
-    b.out8 = out8;
+    const gvk_edl b = fill_edl(d, n, kcount, (const uint32_t*)d_slot, (const uint8_t*)d_sig64,
+                               (const uint8_t*)d_msg_blob, (const uint64_t*)d_msg_off, (const uint32_t*)d_msg_len, out8);
     CK(gvk_ed_lat(&b, st));
   } else {
-    const uint32_t* btab16 = ed_btab16(d, ctx->ed_btab16, st);
-    gvk_sort so;
-    memset(&so, 0, sizeof so);
+    const uint32_t* btab16 = ed_btab16(d, ctx->opt.ed_btab16, st);
+    const uint32_t* perm = nullptr;
     if (sorted) {
-      uint32_t* p = (uint32_t*)(d->edkd_s + C);
-      so.pos = p; p += C;
-      so.perm = p; p += C;
-      so.kslot = p; p += C;
-      so.cnt = p; p += round_up(nb, 64);
-      so.off = p; p += round_up(nb, 64);
-      so.temp = p;
-      so.temp_bytes = tb;
+      const gvk_sort so = carve_sort((uint32_t*)(d->edkd_s + C), C, nb, tb);
       CK(gvk_sort_slots(&so, (uint32_t)n, (const uint32_t*)d_slot, (uint32_t)kcount, st));
+      perm = so.perm;
     }
-    const bool wide = ed_wide_serves(ctx, d, kcount);
-    gvk_edk b;
-    memset(&b, 0, sizeof b);
-    b.n = (uint32_t)n;
-    b.perm = sorted ? so.perm : nullptr;
-    b.slot = (const uint32_t*)d_slot;
-    b.sig64 = (const uint8_t*)d_sig64;
-    b.msg_blob = (const uint8_t*)d_msg_blob;
-    b.msg_off = (const uint64_t*)d_msg_off;
-    b.msg_len = (const uint32_t*)d_msg_len;
-    b.ktab = wide ? d->ektabw : d->ektab;
-    b.rb = wide ? d->ekw_rb : 4;
-    b.kpub = d->ekpub;
-    b.kok = d->ekok;
-    b.kcount = (uint32_t)kcount;
-    b.btab = d->edtab;
-    b.btab16 = btab16;
-    b.out8 = out8;
+    const gvk_edk b = fill_edk(ctx, d, n, kcount, perm, (const uint32_t*)d_slot, (const uint8_t*)d_sig64,
+                               (const uint8_t*)d_msg_blob, (const uint64_t*)d_msg_off, (const uint32_t*)d_msg_len, out8,
+                               btab16);
     CK(gvk_ed_keyed(&b, st));
-    if (wide) ctx->ed_keyed_wide.fetch_add(1);
   }
   CK(gvk_ed_pack_bits((uint32_t)n, out8, (uint64_t*)d_bits, st));
   CK(hipEventRecord(d->edkd_last, st));
@@ -3547,7 +3360,7 @@ int gv_keys_point(gv_ctx* ctx, size_t n, const uint32_t* slots, uint8_t* out_xy6
   std::lock_guard<std::mutex> lk(d->mu);
   CK(hipSetDevice(d->id));
   hipStream_t st = d->set[0].st;
-  int rc = ensure_keys(d, 1, ctx->keys, st, ctx->key_cap, ctx->hbm_budget, nullptr);
+  int rc = ensure_keys(d, 1, ctx->keys, st, ctx->opt.key_cap, ctx->opt.hbm_budget, nullptr);
   if (rc) return rc;
   uint8_t* buf = nullptr;
   const size_t sb = round_up(n * 4, 256), xb = round_up(n * 64, 256);
@@ -3581,7 +3394,7 @@ int gv_keys_find(gv_ctx* ctx, size_t n, const uint8_t* pub33, uint32_t* slot_out
   if (hipMalloc(&buf, pb + n * 4) != hipSuccess) return GV_ENOMEM;
   int rc = GV_OK;
   if (hipMemcpyAsync(buf, pub33, n * 33, hipMemcpyHostToDevice, st) != hipSuccess ||
-      gvk_kidx_find(d->kidx_tab, (uint32_t)d->kidx_T, d->kidx_rows, (uint32_t)ctx->keys, ctx->kidx_seed, buf,
+      gvk_kidx_find(d->kidx_tab, (uint32_t)d->kidx_T, d->kidx_rows, (uint32_t)ctx->keys, ctx->opt.kidx_seed, buf,
                     (uint32_t)n, (uint32_t*)(buf + pb), nullptr, st) != hipSuccess ||
       hipMemcpyAsync(slot_out, buf + pb, n * 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
       hipStreamSynchronize(st) != hipSuccess)
@@ -3614,7 +3427,7 @@ int gv_dev_keys_find(gv_ctx* ctx, int dev_slot, size_t n, const void* d_pub33, v
       }
       return GV_OK;
     }
-    CK(gvk_kidx_find(d->kidx_tab, (uint32_t)d->kidx_T, d->kidx_rows, (uint32_t)ctx->keys, ctx->kidx_seed,
+    CK(gvk_kidx_find(d->kidx_tab, (uint32_t)d->kidx_T, d->kidx_rows, (uint32_t)ctx->keys, ctx->opt.kidx_seed,
                      (const uint8_t*)d_pub33, (uint32_t)n, (uint32_t*)d_slot_out, nullptr, st));
     ctx->kidx_launches++;
     if (!stream) {
@@ -3646,283 +3459,104 @@ int gv_dev_verify_digests_keyed(gv_ctx* ctx, int dev_slot, size_t n, const void*
   if (!d_dig32 || ((uintptr_t)d_dig32 & 3)) return GV_EINVAL;
   std::lock_guard<std::mutex> lk(d->mu);
   CK(hipSetDevice(d->id));
-  return dev_run(ctx, d, stream, n, true, [&](Set* s, hipStream_t st, hipStream_t se) {
-    return launch(ctx, d, s, n, nullptr, (const uint8_t*)d_sig64, (const uint8_t*)d_dig32, nullptr, nullptr, nullptr,
-                  (uint64_t*)d_bits, st, (const uint32_t*)d_slot, nullptr, se);
-  });
+  Items it;
+  it.n = n; it.kslot = (const uint32_t*)d_slot; it.sig64 = (const uint8_t*)d_sig64; it.dig32 = (const uint8_t*)d_dig32;
+  return dev_launch(ctx, d, stream, it, d_bits);
 }
 
 int gv_get_option(gv_ctx* ctx, const char* key, long long* val) {
   if (!ctx || !key || !val) return GV_EINVAL;
+  if (const gvopt::Row* r = gvopt::opt_find(key)) {   // the tunables (gv_options.h)
+    if (!r->readable) return GV_EINVAL;
+    *val = gvopt::opt_read(ctx->opt, *r);
+    return GV_OK;
+  }
+  // read-only live values
   const struct {
     const char* k;
     long long v;
-  } opts[] = {{"kg", ctx->kg},
-              {"k6", ctx->k6},
-              {"gfull", ctx->gfull},
-              {"keys_k6", ctx->keys_k6},
-              {"keys_wide", ctx->keys_wide},
-              {"group_keys", ctx->group_keys},
-              {"sort_keys", ctx->sort_keys},
-              {"pipeline_dev", ctx->pipeline_dev},
-              {"two_ladders", ctx->two_ladders},
-              {"key_cap", (long long)ctx->key_cap},
-              {"max_batch", (long long)ctx->max_batch},
-              {"async_chunk", (long long)ctx->async_chunk},
-              {"async_growth", ctx->async_growth},
-              {"async_whole", ctx->async_whole},
-              {"lat_kw", ctx->lat_kw},
-              {"keys_wide_qw", ctx->keys_wide_qw},
-              {"keys_wide_mb", (long long)(ctx->keys_wide_bytes >> 20)},
-              {"keys_replaced", (long long)ctx->keys_replaced.load()},   // read-only: gv_keys_replace's slots so far
+  } live[] = {{"keys_replaced", (long long)ctx->keys_replaced.load()},   // gv_keys_replace's slots so far
               {"ed_keys_replaced", (long long)ctx->ed_keys_replaced.load()},   // the same for gv_ed_keys_replace
-              {"ed_keys_wide", ctx->ed_keys_wide},
-              {"ed_keys_wide_mb", (long long)(ctx->ed_keys_wide_bytes >> 20)},
-              {"ed_keyed_wide", (long long)ctx->ed_keyed_wide.load()},   // read-only: keyed batches / chunks on wide tables
-              {"keys_index", ctx->keys_index},
-              {"keys_index_hit", (long long)ctx->kidx_hit.load()},     // read-only: pub33 device batches routed keyed
-              {"keys_index_miss", (long long)ctx->kidx_miss.load()},   // read-only: ... that fell through on a miss
-              {"keys_index_launches", (long long)ctx->kidx_launches.load()},   // read-only: k_kidx_* launches so far
-              {"keys_index_find_ns", (long long)ctx->kidx_find_ns.load()},     // read-only: the last routed lookup's
-                                                                               // kernel ("time_kernels" on)
-              {"kw_qw", GV_KW_QW},                   // read-only: the wide arena's window width (build)
-              {"kwn_qw", GV_KWN ? GV_KWN_QW : 0}};   // read-only: its narrow width (build; 0: not compiled)
-  // read-only: the first device's wide arena as gv_keys_load left it -- its
-  // window width (0: no slot has wide tables) and its groups
-  if (!strcmp(key, "kw_arena_qw") || !strcmp(key, "kw_arena_ng")) {
-    if (ctx->devs.empty()) return GV_EINVAL;
-    Dev* d = ctx->devs[0];
-    std::lock_guard<std::mutex> lk(d->mu);
-    const bool live = d->kqtw && d->keysw;
-    *val = !live ? 0 : !strcmp(key, "kw_arena_qw") ? d->kw_qw : d->kw_ng;
-    return GV_OK;
-  }
-  // read-only: the first device's pubkey index -- whether it covers the arena,
-  // the slots in it, the keys its probe bound left out, its table words
-  if (!strcmp(key, "keys_index_live") || !strcmp(key, "keys_index_keys") || !strcmp(key, "keys_index_left_out") ||
-      !strcmp(key, "keys_index_words")) {
-    if (ctx->devs.empty()) return GV_EINVAL;
-    Dev* d = ctx->devs[0];
-    std::lock_guard<std::mutex> lk(d->mu);
-    const bool has = d->kidx_tab && !d->kidx_failed;
-    *val = !strcmp(key, "keys_index_live")       ? (long long)kidx_live(ctx, d)
-           : !strcmp(key, "keys_index_keys")     ? (long long)(has ? d->kidx_keys : 0)
-           : !strcmp(key, "keys_index_left_out") ? (long long)(has ? d->kidx_left_out : 0)
-                                                 : (long long)(has ? d->kidx_T : 0);
-    return GV_OK;
-  }
-  // read-only: the first device's wide ed25519 arena as gv_ed_keys_load left
-  // it -- its radix bits (0: no slot has wide tables) and the slots that have them
-  if (!strcmp(key, "ed_kw_rb") || !strcmp(key, "ed_kw_keys")) {
-    if (ctx->devs.empty()) return GV_EINVAL;
-    std::lock_guard<std::mutex> kl(ctx->ed_keys_mu);
-    Dev* d = ctx->devs[0];
-    std::lock_guard<std::mutex> lk(d->mu);
-    const bool live = d->ektabw && d->ekeysw;
-    *val = !live ? 0 : !strcmp(key, "ed_kw_rb") ? d->ekw_rb : (long long)d->ekeysw;
-    return GV_OK;
-  }
-  for (const auto& o : opts)
+              {"ed_keyed_wide", (long long)ctx->ed_keyed_wide.load()},   // keyed batches / chunks on wide tables
+              {"keys_index_hit", (long long)ctx->kidx_hit.load()},     // pub33 device batches routed keyed
+              {"keys_index_miss", (long long)ctx->kidx_miss.load()},   // ... that fell through on a miss
+              {"keys_index_launches", (long long)ctx->kidx_launches.load()},   // k_kidx_* launches so far
+              {"keys_index_find_ns", (long long)ctx->kidx_find_ns.load()},     // the last routed lookup's kernel
+                                                                               // ("time_kernels" on)
+              {"kw_qw", GV_KW_QW},                   // the wide arena's window width (build)
+              {"kwn_qw", GV_KWN ? GV_KWN_QW : 0}};   // its narrow width (build; 0: not compiled)
+  for (const auto& o : live)
     if (!strcmp(key, o.k)) {
       *val = o.v;
       return GV_OK;
     }
-  return GV_EINVAL;
+  // the first device's wide arena as gv_keys_load left it -- its window width
+  // (0: no slot has wide tables) and its groups; its pubkey index -- whether
+  // it covers the arena, the slots in it, the keys its probe bound left out,
+  // its table words; its wide ed25519 arena as gv_ed_keys_load left it -- its
+  // radix bits (0: no slot has wide tables) and the slots that have them
+  const bool ed = !strcmp(key, "ed_kw_rb") || !strcmp(key, "ed_kw_keys");
+  static const char* const kDev[] = {"kw_arena_qw", "kw_arena_ng", "keys_index_live", "keys_index_keys",
+                                     "keys_index_left_out", "keys_index_words"};
+  if (!ed && std::none_of(std::begin(kDev), std::end(kDev), [&](const char* k) { return !strcmp(key, k); }))
+    return GV_EINVAL;
+  if (ctx->devs.empty()) return GV_EINVAL;
+  std::unique_lock<std::mutex> kl;
+  if (ed) kl = std::unique_lock<std::mutex>(ctx->ed_keys_mu);
+  Dev* d = ctx->devs[0];
+  std::lock_guard<std::mutex> lk(d->mu);
+  const bool kw = d->kqtw && d->keysw, has = d->kidx_tab && !d->kidx_failed, ekw = d->ektabw && d->ekeysw;
+  *val = !strcmp(key, "kw_arena_qw")           ? (kw ? d->kw_qw : 0)
+         : !strcmp(key, "kw_arena_ng")         ? (kw ? d->kw_ng : 0)
+         : !strcmp(key, "keys_index_live")     ? (long long)kidx_live(ctx, d)
+         : !strcmp(key, "keys_index_keys")     ? (long long)(has ? d->kidx_keys : 0)
+         : !strcmp(key, "keys_index_left_out") ? (long long)(has ? d->kidx_left_out : 0)
+         : !strcmp(key, "keys_index_words")    ? (long long)(has ? d->kidx_T : 0)
+         : !strcmp(key, "ed_kw_rb")            ? (ekw ? d->ekw_rb : 0)
+                                               : (long long)(ekw ? d->ekeysw : 0);
+  return GV_OK;
+}
+
+// Every device lock, taken in device order (returned held); drain: the
+// pipelined ladders of every device have finished and the next pipelined call
+// waits for no earlier bitmap, so no call launches on a mix of old and new
+// option state.
+static int quiesce_all(gv_ctx* ctx, bool drain, std::vector<std::unique_lock<std::mutex>>* held) {
+  for (Dev* d : ctx->devs) held->emplace_back(d->mu);
+  if (!drain) return GV_OK;
+  for (Dev* d : ctx->devs) {
+    CK(hipSetDevice(d->id));
+    for (hipStream_t t : d->hi_st) CK(hipStreamSynchronize(t));
+    d->bits_used = false;
+  }
+  return GV_OK;
 }
 
 int gv_set_option(gv_ctx* ctx, const char* key, long long val) {
   if (!ctx || !key) return GV_EINVAL;
-  if (!strcmp(key, "lat_max") || !strcmp(key, "lat_max_keyed")) {
-    if (val < 0 || (unsigned long long)val > kMaxItems) return GV_EINVAL;
-    if (!strcmp(key, "lat_max")) ctx->lat_max = (size_t)val;
-    ctx->lat_max_keyed = (size_t)val;
-  } else if (!strcmp(key, "lat_sl_max") || !strcmp(key, "lat_sl_max_keyed")) {
-    if (val < 0 || (unsigned long long)val > kMaxItems) return GV_EINVAL;
-    if (!strcmp(key, "lat_sl_max")) ctx->lat_sl_max = (size_t)val;
-    ctx->lat_sl_max_keyed = (size_t)val;
-  } else if (!strcmp(key, "ed_unc_lat_max")) {
-    if (val < 0 || (unsigned long long)val > kMaxItems) return GV_EINVAL;
-    ctx->ed_unc_lat_max = (size_t)val;
-  } else if (!strcmp(key, "ed_lat_max")) {
-    if (val < 0 || (unsigned long long)val > kMaxItems) return GV_EINVAL;
-    ctx->ed_lat_max = (size_t)val;
-  } else if (!strcmp(key, "lat_zero_copy")) {
-    if (val != 0 && val != 1) return GV_EINVAL;
-    ctx->lat_zero_copy = val != 0;
-  } else if (!strcmp(key, "lat_sliced")) {
-    if (val != 0 && val != 1) return GV_EINVAL;
-    ctx->lat_sliced = val != 0;
-  } else if (!strcmp(key, "lat_rows_max")) {
-    if (val < 0 || (unsigned long long)val > kMaxItems) return GV_EINVAL;
-    ctx->lat_rows_max = (size_t)val;
-  } else if (!strcmp(key, "max_batch")) {
-    if (val < 256 || (unsigned long long)val > kMaxItems) return GV_EINVAL;
-    ctx->max_batch = round_up((size_t)val, 256);
-  } else if (!strcmp(key, "pipe_chunk")) {
-    if (val != 0 && (val < 256 || (unsigned long long)val > kMaxItems)) return GV_EINVAL;
-    ctx->pipe_chunk = val ? round_up((size_t)val, 256) : 0;
-  } else if (!strcmp(key, "pipe_growth")) {
-    if (val < 1 || val > 64) return GV_EINVAL;
-    ctx->pipe_growth = (int)val;
-  } else if (!strcmp(key, "stage_threads")) {
-    if (val < 1 || val > 64) return GV_EINVAL;
-    std::vector<std::unique_lock<std::mutex>> held;   // no device stages while its pool is replaced
-    for (Dev* d : ctx->devs) held.emplace_back(d->mu);
-    ctx->stage_threads = (int)val;
+  const gvopt::Row* r = gvopt::opt_find(key);
+  if (!r || !gvopt::opt_check(*r, val)) return GV_EINVAL;
+  // the row's effect, held until the value is stored
+  std::vector<std::unique_lock<std::mutex>> held;
+  std::unique_lock<std::mutex> kl;
+  switch (r->fx) {
+    case gvopt::FX_NONE: break;
+    case gvopt::FX_QUIESCE:
+    case gvopt::FX_POOLS:                         // (no drain: no device stages while its pool is replaced)
+      if (int rc = quiesce_all(ctx, r->fx == gvopt::FX_QUIESCE, &held)) return rc;
+      break;
+    case gvopt::FX_ED_KEYS_MU: kl = std::unique_lock<std::mutex>(ctx->ed_keys_mu); break;
+    case gvopt::FX_KEYS_EMPTY:
+      kl = std::unique_lock<std::mutex>(ctx->keys_mu);
+      if (ctx->keys != 0) return GV_EINVAL;
+      break;
+  }
+  gvopt::opt_store(ctx->opt, *r, val);
+  if (r->fx == gvopt::FX_POOLS)
     for (Dev* d : ctx->devs) {
       delete d->pool;
       d->pool = new Pool((int)val - 1);
     }
-  } else if (!strcmp(key, "stage_pieces")) {
-    if (val < 1 || val > 64) return GV_EINVAL;
-    ctx->stage_pieces = (int)val;
-  } else if (!strcmp(key, "h2d_serial")) {
-    if (val != 0 && val != 1) return GV_EINVAL;
-    ctx->h2d_serial = val != 0;
-  } else if (!strcmp(key, "gfull_item")) {
-    if (val != 0 && val != 1) return GV_EINVAL;
-    ctx->gfull_item = val != 0;
-  } else if (!strcmp(key, "inv_small")) {
-    if (val != 0 && val != 1) return GV_EINVAL;
-    ctx->inv_small = val != 0;
-  } else if (!strcmp(key, "slice_plain_first")) {
-    if (val < 0 || (unsigned long long)val > kMaxItems) return GV_EINVAL;
-    ctx->slice_plain_first = (size_t)val;
-  } else if (!strcmp(key, "group_keys")) {
-    if (val != 0 && val != 1) return GV_EINVAL;
-    ctx->group_keys = val != 0;
-  } else if (!strcmp(key, "group_min")) {
-    if (val < 256 || (unsigned long long)val > kMaxItems) return GV_EINVAL;
-    ctx->group_min = (size_t)val;
-  } else if (!strcmp(key, "group_div")) {
-    if (val < 2 || val > 1024) return GV_EINVAL;
-    ctx->group_div = (int)val;
-  } else if (!strcmp(key, "ed_btab16")) {
-    if (val != 0 && val != 1) return GV_EINVAL;
-    ctx->ed_btab16 = val != 0;
-  } else if (!strcmp(key, "ed_group_r64")) {
-    if (val != 0 && val != 1) return GV_EINVAL;
-    ctx->ed_group_r64 = val != 0;
-  } else if (!strcmp(key, "ed_keys_split")) {
-    if (val != 0 && val != 1) return GV_EINVAL;
-    ctx->ed_keys_split = val != 0;
-  } else if (!strcmp(key, "ed_group")) {
-    if (val != 0 && val != 1) return GV_EINVAL;
-    ctx->ed_group = val != 0;
-  } else if (!strcmp(key, "ed_group_min")) {
-    if (val < 256 || (unsigned long long)val > kMaxItems) return GV_EINVAL;
-    ctx->ed_group_min = (size_t)val;
-  } else if (!strcmp(key, "ed_keyed")) {
-    if (val != 0 && val != 1) return GV_EINVAL;
-    ctx->ed_keyed = val != 0;
-  } else if (!strcmp(key, "ed_keys_wide")) {
-    // the radix of an arena started from slot 0 from now on (a running arena
-    // keeps its tables until gv_ed_keys_reset); 0 stops their use at once
-    if (val != 0 && val != 6 && val != 8) return GV_EINVAL;
-    std::lock_guard<std::mutex> kl(ctx->ed_keys_mu);
-    ctx->ed_keys_wide = (int)val;
-  } else if (!strcmp(key, "ed_keys_wide_mb")) {
-    if (val < 0 || (unsigned long long)val > (SIZE_MAX >> 20)) return GV_EINVAL;
-    std::lock_guard<std::mutex> kl(ctx->ed_keys_mu);
-    ctx->ed_keys_wide_bytes = (size_t)val << 20;
-  } else if (!strcmp(key, "keys_wide")) {
-    // the layout of an arena started from slot 0 from now on (a running arena
-    // keeps its layout until gv_keys_reset); 0 stops its use at once
-    if (val < 0 || val > 2) return GV_EINVAL;
-    std::vector<std::unique_lock<std::mutex>> held;
-    for (Dev* d : ctx->devs) held.emplace_back(d->mu);
-    for (Dev* d : ctx->devs) {
-      CK(hipSetDevice(d->id));
-      for (hipStream_t t : d->hi_st) CK(hipStreamSynchronize(t));
-      d->bits_used = false;
-    }
-    ctx->keys_wide = (int)val;
-  } else if (!strcmp(key, "keys_index")) {
-    // taken by an arena started from slot 0 from now on (a running arena keeps
-    // what it has until gv_keys_reset); 0 stops the use of the index at once
-    if (val != 0 && val != 1) return GV_EINVAL;
-    std::vector<std::unique_lock<std::mutex>> held;
-    for (Dev* d : ctx->devs) held.emplace_back(d->mu);
-    for (Dev* d : ctx->devs) {
-      CK(hipSetDevice(d->id));
-      for (hipStream_t t : d->hi_st) CK(hipStreamSynchronize(t));
-      d->bits_used = false;
-    }
-    ctx->keys_index = val != 0;
-  } else if (!strcmp(key, "keys_index_seed")) {
-    // test hook: the index hash's seed, while no key is in the arena
-    std::lock_guard<std::mutex> kl(ctx->keys_mu);
-    if (ctx->keys != 0) return GV_EINVAL;
-    ctx->kidx_seed = (uint64_t)val;
-  } else if (!strcmp(key, "kg")) {
-    if (!kg_layout_ok((int)val)) return GV_EINVAL;
-    std::vector<std::unique_lock<std::mutex>> held;
-    for (Dev* d : ctx->devs) held.emplace_back(d->mu);
-    for (Dev* d : ctx->devs) {
-      CK(hipSetDevice(d->id));
-      for (hipStream_t t : d->hi_st) CK(hipStreamSynchronize(t));
-      d->bits_used = false;
-    }
-    ctx->kg = (int)val;
-  } else if (!strcmp(key, "keys_wide_qw")) {
-    // the widths an arena started from slot 0 may take from now on
-    if (val != 0 && (val < 0 || val > 32 || !gvk_kw_width_ok((int)val))) return GV_EINVAL;
-    ctx->keys_wide_qw = (int)val;
-  } else if (!strcmp(key, "keys_wide_mb")) {
-    if (val < 0 || (unsigned long long)val > (SIZE_MAX >> 20)) return GV_EINVAL;
-    ctx->keys_wide_bytes = (size_t)val << 20;
-  } else if (!strcmp(key, "keys_wide1_cap")) {
-    if (val < 0) return GV_EINVAL;
-    ctx->keys_wide1_cap = val == 0 ? SIZE_MAX : (size_t)val;
-  } else if (!strcmp(key, "two_ladders") || !strcmp(key, "gfull") || !strcmp(key, "k6") ||
-             !strcmp(key, "keys_k6")) {
-    // schedule switches: every device lock held across the drain and the
-    // write, so no pipelined call launches on a mix of old and new state
-    if (val != 0 && val != 1) return GV_EINVAL;
-    std::vector<std::unique_lock<std::mutex>> held;
-    for (Dev* d : ctx->devs) held.emplace_back(d->mu);
-    for (Dev* d : ctx->devs) {
-      CK(hipSetDevice(d->id));
-      for (hipStream_t t : d->hi_st) CK(hipStreamSynchronize(t));
-      d->bits_used = false;
-    }
-    bool& flag = !strcmp(key, "two_ladders") ? ctx->two_ladders : !strcmp(key, "gfull") ? ctx->gfull
-                 : !strcmp(key, "k6") ? ctx->k6 : ctx->keys_k6;
-    flag = val != 0;
-  } else if (!strcmp(key, "async_chunk")) {
-    if (val < 256 || (unsigned long long)val > kMaxItems) return GV_EINVAL;
-    ctx->async_chunk = round_up((size_t)val, 256);
-  } else if (!strcmp(key, "lat_kw")) {
-    if (val != 0 && val != 1) return GV_EINVAL;
-    ctx->lat_kw = val != 0;
-  } else if (!strcmp(key, "async_whole")) {
-    if (val != 0 && val != 1) return GV_EINVAL;
-    ctx->async_whole = val != 0;
-  } else if (!strcmp(key, "async_growth")) {
-    if (val < 1 || val > 64) return GV_EINVAL;
-    ctx->async_growth = (int)val;
-  } else if (!strcmp(key, "host_ladder_stream")) {
-    if (val != 0 && val != 1) return GV_EINVAL;
-    ctx->host_ladder_stream = val != 0;
-  } else if (!strcmp(key, "key_cap") || !strcmp(key, "ed_key_cap")) {
-    if (val < 256 || (unsigned long long)val > kMaxItems) return GV_EINVAL;
-    (!strcmp(key, "key_cap") ? ctx->key_cap : ctx->ed_key_cap) = (size_t)val;
-  } else if (!strcmp(key, "hbm_budget_mb")) {
-    if (val < 0) return GV_EINVAL;
-    ctx->hbm_budget = val == 0 ? SIZE_MAX : (size_t)val << 20;
-  } else if (!strcmp(key, "sort_keys")) {
-    if (val != 0 && val != 1) return GV_EINVAL;
-    ctx->sort_keys = val != 0;
-  } else if (!strcmp(key, "pipeline_dev")) {
-    if (val != 0 && val != 1) return GV_EINVAL;
-    ctx->pipeline_dev = val != 0;
-  } else if (!strcmp(key, "time_kernels")) {
-    ctx->time_kernels = val != 0;
-  } else if (!strcmp(key, "fault_inject")) {
-    ctx->fault_inject = val != 0;
-  } else {
-    return GV_EINVAL;
-  }
   return GV_OK;
 }
 
@@ -3936,7 +3570,7 @@ static int stage_ms(hipEvent_t* e, float ms[4]) {
 
 int gv_last_stage_ms(gv_ctx* ctx, int dev_slot, float* unpack_ms, float* prep_ms, float* ecmult_ms) {
   if (!ctx || dev_slot < 0 || dev_slot >= (int)ctx->devs.size()) return GV_EINVAL;
-  if (!ctx->time_kernels) return GV_EINVAL;
+  if (!ctx->opt.time_kernels) return GV_EINVAL;
   Dev* d = ctx->devs[dev_slot];
   if (d->last < 0) return GV_EINVAL;
   CK(hipSetDevice(d->id));
