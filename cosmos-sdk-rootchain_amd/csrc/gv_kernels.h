@@ -421,17 +421,17 @@ hipError_t gvk_gen_gtablef(uint32_t* gtabf, uint32_t* base_scratch, hipStream_t 
 uint32_t gvk_keys_lanes(uint32_t n, int ng);
 size_t gvk_keys_scratch_words(uint32_t n, int ng, int nt, int with_qe);
 // k6 key tables (4 groups of 32 entries) of n keys already unpacked into rows
-// in_x / in_pfx (stride C), slots 0..n-1.  kqt: n x GV_K6_KEY_WORDS, kqt2:
-// 3 n x GV_K6_KEY_WORDS.
+// in_x / in_pfx (stride C), slots base..base+n-1.  kqt: (base + n) x
+// GV_K6_KEY_WORDS, kqt2: 3 (base + n) x GV_K6_KEY_WORDS.
 hipError_t gvk_keys_build_rows6(uint32_t n, uint32_t C, const uint32_t* in_x, const uint32_t* in_pfx,
-                                uint32_t* scratch, int with_qe, uint32_t* kqt, uint32_t* kzq, uint32_t kC,
+                                uint32_t* scratch, int with_qe, uint32_t base, uint32_t* kqt, uint32_t* kzq, uint32_t kC,
                                 uint32_t* kok, uint32_t* kqt2, uint32_t* kzq2, hipStream_t st);
 // kg key tables (ng groups of 16 entries, ng one of GV_KG_NGS) of n keys
-// already unpacked, slots 0..n-1.  kqt: n x GV_KEY_WORDS, kqt2: (ng - 1) n x
-// GV_KEY_WORDS, kzq2: (ng - 1) x 8 rows of stride kC.
+// already unpacked, slots base..base+n-1.  kqt: (base + n) x GV_KEY_WORDS,
+// kqt2: (ng - 1) (base + n) x GV_KEY_WORDS, kzq2: (ng - 1) x 8 rows of stride kC.
 hipError_t gvk_keys_build_rows_kg(uint32_t n, uint32_t C, const uint32_t* in_x, const uint32_t* in_pfx,
-                                  uint32_t* scratch, int with_qe, uint32_t* kqt, uint32_t* kzq, uint32_t kC,
-                                  uint32_t* kok, uint32_t* kqt2, uint32_t* kzq2, int ng, hipStream_t st);
+                                  uint32_t* scratch, int with_qe, uint32_t base, uint32_t* kqt, uint32_t* kzq,
+                                  uint32_t kC, uint32_t* kok, uint32_t* kqt2, uint32_t* kzq2, int ng, hipStream_t st);
 hipError_t gvk_verify_lat(const gvk_lat* b, hipStream_t st);
 hipError_t gvk_verify_lat16(const gvk_lat* b, hipStream_t st);
 hipError_t gvk_verify_lat_sl(const gvk_lat* b, hipStream_t st);
@@ -442,17 +442,18 @@ hipError_t gvk_verify(const gvk_batch* b, hipStream_t st);
 hipError_t gvk_unpack(const uint8_t* pub33, const uint8_t* sig64, const uint8_t* dig32, uint32_t n, uint32_t C,
                       uint32_t* x, uint32_t* pfx, uint32_t* r, uint32_t* s, uint32_t* e, hipStream_t st);
 // In-batch key grouping (gv_kernels.hip k_dedupe*): rep / uid / kslot (n
-// words each), table (tslots = power of two >= 2n words), count (1 word); the
+// words each), table (tslots = power of two >= 2n words), count (2 words: the
+// distinct keys, and a second word cleared for the caller); the
 // first capU distinct keys' (prefix, x) go to key rows kx (8 rows) / kpfx of
-// stride CU.
+// stride CU.  kslot null: the items' slots are left to the caller (gvk_group_map).
 hipError_t gvk_dedupe(uint32_t n, uint32_t C, const uint32_t* x, const uint32_t* pfx, uint32_t* table, uint32_t tslots,
                       uint32_t* rep, uint32_t* uid, uint32_t* count, uint32_t* kslot, uint32_t capU, uint32_t CU,
                       uint32_t* kx, uint32_t* kpfx, hipStream_t st);
 // The k4 key tables (4 groups of 16 entries) of n keys already unpacked into
-// rows in_x / in_pfx (stride C), slots 0..n-1 (scratch: gvk_keys_scratch_words).
+// rows in_x / in_pfx (stride C), slots base..base+n-1 (scratch: gvk_keys_scratch_words).
 hipError_t gvk_keys_build_rows(uint32_t n, uint32_t C, const uint32_t* in_x, const uint32_t* in_pfx,
-                               uint32_t* scratch, int with_qe, uint32_t* kqt, uint32_t* kzq, uint32_t kC,
-                               uint32_t* kok, uint32_t* kqt2, uint32_t* kzq2, hipStream_t st);
+                               uint32_t* scratch, int with_qe, uint32_t base, uint32_t* kqt, uint32_t* kzq,
+                               uint32_t kC, uint32_t* kok, uint32_t* kqt2, uint32_t* kzq2, hipStream_t st);
 // Parse n keys (device pub33) into arena slots base..base+n-1 (k4 tables).
 // Scratch: the batch rows in_x, in_pfx (and r, s, e as k_unpack targets) of
 // stride C and gvk_keys_scratch_words(n, 4, GV_QTAB_N, with_qe) words.
@@ -482,6 +483,25 @@ hipError_t gvk_kidx_put(uint32_t* table, uint32_t tslots, const uint32_t* rows, 
                         const uint32_t* slots, uint64_t seed, uint32_t* left_out, hipStream_t st);
 hipError_t gvk_kidx_find(const uint32_t* table, uint32_t tslots, const uint32_t* rows, uint32_t count, uint64_t seed,
                          const uint8_t* pub33, uint32_t n, uint32_t* slot_out, uint32_t* miss, hipStream_t st);
+// The grouped route's per-set key-table cache (option "group_reuse"; DESIGN
+// section 4.1k): the same rows / table over a set's per-batch arena.
+// gvk_group_find: one lane per distinct key u < min(*ucount, capU) of the
+// batch (key rows kx / kpfx of stride CU >= capU, capU a multiple of 256):
+// row[u] = the cache row below `count` holding its 9 words, else count + m with
+// miss[m] = u and *mcount += 1 (row, miss: capU words).
+// gvk_group_put: new key m < n (batch key list[m]; null list: m) -> cache row
+// base + m, which then enters the table; with mx its (prefix, x) also goes to
+// column m of mx / mpfx (stride CU), the build's dense input.
+// gvk_group_map: kslot[g] = row[uid[rep[g]]] (null row: uid[rep[g]], as
+// k_dedupe_map), 0xFFFFFFFF for a key with no id.
+hipError_t gvk_group_find(const uint32_t* table, uint32_t tslots, const uint32_t* rows, uint32_t count, uint64_t seed,
+                          const uint32_t* kx, const uint32_t* kpfx, uint32_t CU, const uint32_t* ucount, uint32_t capU,
+                          uint32_t* row, uint32_t* miss, uint32_t* mcount, hipStream_t st);
+hipError_t gvk_group_put(uint32_t* table, uint32_t tslots, uint32_t* rows, uint64_t seed, const uint32_t* kx,
+                         const uint32_t* kpfx, uint32_t CU, const uint32_t* list, uint32_t n, uint32_t base,
+                         uint32_t* mx, uint32_t* mpfx, hipStream_t st);
+hipError_t gvk_group_map(uint32_t n, const uint32_t* rep, const uint32_t* uid, const uint32_t* row, uint32_t* kslot,
+                         hipStream_t st);
 hipError_t gvk_debug(int op, uint32_t n, const uint32_t* in, uint32_t* out, hipStream_t st);
 
 // gv_debug_sl_op: the limb-sliced layers, one item per 64-lane wave.

@@ -2436,19 +2436,19 @@ size_t gvk_keys_scratch_words(uint32_t n, int ng, int nt, int with_qe) {
 }
 
 hipError_t gvk_keys_build_rows6(uint32_t n, uint32_t C, const uint32_t* in_x, const uint32_t* in_pfx,
-                                uint32_t* scratch, int with_qe, uint32_t* kqt, uint32_t* kzq, uint32_t kC,
+                                uint32_t* scratch, int with_qe, uint32_t base, uint32_t* kqt, uint32_t* kzq, uint32_t kC,
                                 uint32_t* kok, uint32_t* kqt2, uint32_t* kzq2, hipStream_t st) {
-  return keys_tables_launch<GV_K6_QW, 4>(n, C, in_x, in_pfx, scratch, with_qe, 0u, kqt, kzq, kC, kok, kqt2, kzq2, st);
+  return keys_tables_launch<GV_K6_QW, 4>(n, C, in_x, in_pfx, scratch, with_qe, base, kqt, kzq, kC, kok, kqt2, kzq2, st);
 }
 
 hipError_t gvk_keys_build_rows_kg(uint32_t n, uint32_t C, const uint32_t* in_x, const uint32_t* in_pfx,
-                                  uint32_t* scratch, int with_qe, uint32_t* kqt, uint32_t* kzq, uint32_t kC,
-                                  uint32_t* kok, uint32_t* kqt2, uint32_t* kzq2, int ng, hipStream_t st) {
+                                  uint32_t* scratch, int with_qe, uint32_t base, uint32_t* kqt, uint32_t* kzq,
+                                  uint32_t kC, uint32_t* kok, uint32_t* kqt2, uint32_t* kzq2, int ng, hipStream_t st) {
   switch (ng) {
-    case 4: return keys_tables_launch<GV_QW, 4>(n, C, in_x, in_pfx, scratch, with_qe, 0u, kqt, kzq, kC, kok, kqt2, kzq2, st);
-    case 6: return keys_tables_launch<GV_QW, 6>(n, C, in_x, in_pfx, scratch, with_qe, 0u, kqt, kzq, kC, kok, kqt2, kzq2, st);
-    case 7: return keys_tables_launch<GV_QW, 7>(n, C, in_x, in_pfx, scratch, with_qe, 0u, kqt, kzq, kC, kok, kqt2, kzq2, st);
-    case 9: return keys_tables_launch<GV_QW, 9>(n, C, in_x, in_pfx, scratch, with_qe, 0u, kqt, kzq, kC, kok, kqt2, kzq2, st);
+    case 4: return keys_tables_launch<GV_QW, 4>(n, C, in_x, in_pfx, scratch, with_qe, base, kqt, kzq, kC, kok, kqt2, kzq2, st);
+    case 6: return keys_tables_launch<GV_QW, 6>(n, C, in_x, in_pfx, scratch, with_qe, base, kqt, kzq, kC, kok, kqt2, kzq2, st);
+    case 7: return keys_tables_launch<GV_QW, 7>(n, C, in_x, in_pfx, scratch, with_qe, base, kqt, kzq, kC, kok, kqt2, kzq2, st);
+    case 9: return keys_tables_launch<GV_QW, 9>(n, C, in_x, in_pfx, scratch, with_qe, base, kqt, kzq, kC, kok, kqt2, kzq2, st);
     default: return hipErrorInvalidValue;
   }
 }
@@ -2543,19 +2543,19 @@ hipError_t gvk_dedupe(uint32_t n, uint32_t C, const uint32_t* x, const uint32_t*
                       uint32_t* kx, uint32_t* kpfx, hipStream_t st) {
   const dim3 blk(256), grd((n + 255) / 256);
   if (hipMemsetAsync(table, 0xFF, (size_t)tslots * 4, st) != hipSuccess ||
-      hipMemsetAsync(count, 0, 4, st) != hipSuccess)
+      hipMemsetAsync(count, 0, 8, st) != hipSuccess)    // (the second word: the caller's, gvk_group_find's misses)
     return hipErrorUnknown;
   hipLaunchKernelGGL(gv::k_dedupe, grd, blk, 0, st, n, C, x, pfx, table, tslots - 1, rep);
   hipLaunchKernelGGL(gv::k_dedupe_assign, grd, blk, 0, st, n, C, x, pfx, (const uint32_t*)rep, uid, count, capU, CU,
                      kx, kpfx);
-  hipLaunchKernelGGL(gv::k_dedupe_map, grd, blk, 0, st, n, (const uint32_t*)rep, (const uint32_t*)uid, kslot);
+  if (kslot) hipLaunchKernelGGL(gv::k_dedupe_map, grd, blk, 0, st, n, (const uint32_t*)rep, (const uint32_t*)uid, kslot);
   return hipGetLastError();
 }
 
 hipError_t gvk_keys_build_rows(uint32_t n, uint32_t C, const uint32_t* in_x, const uint32_t* in_pfx,
-                               uint32_t* scratch, int with_qe, uint32_t* kqt, uint32_t* kzq, uint32_t kC,
-                               uint32_t* kok, uint32_t* kqt2, uint32_t* kzq2, hipStream_t st) {
-  return keys_tables_launch<GV_QW, GV_LGRP>(n, C, in_x, in_pfx, scratch, with_qe, 0u, kqt, kzq, kC, kok, kqt2, kzq2,
+                               uint32_t* scratch, int with_qe, uint32_t base, uint32_t* kqt, uint32_t* kzq,
+                               uint32_t kC, uint32_t* kok, uint32_t* kqt2, uint32_t* kzq2, hipStream_t st) {
+  return keys_tables_launch<GV_QW, GV_LGRP>(n, C, in_x, in_pfx, scratch, with_qe, base, kqt, kzq, kC, kok, kqt2, kzq2,
                                             st);
 }
 

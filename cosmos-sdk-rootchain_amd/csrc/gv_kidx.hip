@@ -1,7 +1,8 @@
 // gv_kidx.hip -- kernels of the resident key arena's pubkey index (option
 // "keys_index"; gv_kidx.h holds the hash, the probe sequence, insert and
-// lookup).  All three are one lane per key or item, memory-bound and tiny
-// beside a table build or a ladder.
+// lookup), and of the grouped route's per-set key-table cache over the same
+// routines (option "group_reuse").  All are one lane per key or item,
+// memory-bound and tiny beside a table build or a ladder.
 #include <hip/hip_runtime.h>
 #include "gv_kernels.h"
 #include "gv_kidx.h"
@@ -55,6 +56,77 @@ __global__ __launch_bounds__(256) void k_kidx_find(const u32* table, u32 tmask, 
   }
   wave_count(g < n && slot == GV_KIDX_EMPTY, miss);
 }
+
+// ---- the grouped route's per-set key-table cache (option "group_reuse";
+// DESIGN section 4.1k): the same rows, table and routines over the set's
+// per-batch arena, whose row r holds the tables of the key in rows[r].
+//
+// k_group_find: one lane per distinct key u of the batch (kx / kpfx of stride
+// CU as k_dedupe_assign left them; *ucount keys, the lanes past it and past
+// capU do nothing).  A key whose 9 words are in the cache's first `count` rows
+// gets row[u] = that row; every other key takes the next miss number m (one
+// atomic per wave, as k_dedupe_assign): miss[m] = u, row[u] = count + m, the
+// row its tables are built into when the host appends (count + m may lie past
+// the arena: the host then flushes and reads neither list).
+__global__ __launch_bounds__(256) void k_group_find(const u32* table, u32 tmask, const u32* rows, u32 count,
+                                                     uint64_t seed, const u32* kx, const u32* kpfx, u32 CU,
+                                                     const u32* ucount, u32 capU, u32* row, u32* miss, u32* mcount) {
+  const u32 u = blockIdx.x * blockDim.x + threadIdx.x;
+  const u32 U = min(*ucount, capU);
+  const bool live = u < U;
+  u32 r = 0;
+  if (live) {
+    u32 key[GV_KIDX_ROW];
+    key[0] = kpfx[u];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) key[1 + i] = kx[(size_t)i * CU + u];
+    r = gv_kidx_find(table, tmask, rows, count, key, seed);
+  }
+  const bool missed = live && r == GV_KIDX_EMPTY;
+  const uint64_t m = __ballot(missed);
+  if (m != 0) {                                          // wave-uniform
+    const u32 lane = threadIdx.x & 63u, leader = (u32)__builtin_ctzll(m);
+    u32 b0 = 0;
+    if (lane == leader) b0 = atomicAdd(mcount, (u32)__builtin_popcountll(m));
+    b0 = (u32)__shfl((int)b0, (int)leader);
+    if (missed) {
+      const u32 mi = b0 + (u32)__builtin_popcountll(m & ((1ull << lane) - 1ull));
+      miss[mi] = u;
+      r = count + mi;
+    }
+  }
+  if (live) row[u] = r;
+}
+
+// k_group_put: new key m (batch key list[m], or m itself with a null list) ->
+// cache row base + m, and, with mx, key column m of the build's input rows mx
+// / mpfx (stride CU): the missed keys gathered dense.  The rows enter the table
+// in a launch of their own (k_kidx_put reads other lanes' rows).
+__global__ __launch_bounds__(256) void k_group_put(const u32* kx, const u32* kpfx, u32 CU, const u32* list, u32 n,
+                                                    u32 base, u32* rows, u32* mx, u32* mpfx) {
+  const u32 m = blockIdx.x * blockDim.x + threadIdx.x;
+  if (m >= n) return;
+  const u32 u = list ? list[m] : m;
+  u32* out = rows + (size_t)(base + m) * GV_KIDX_ROW;
+  const u32 pre = kpfx[u];
+  out[0] = pre;
+  if (mx) mpfx[m] = pre;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    const u32 w = kx[(size_t)i * CU + u];
+    out[1 + i] = w;
+    if (mx) mx[(size_t)i * CU + m] = w;
+  }
+}
+
+// k_dedupe_map through the cache: item g's slot is the cache row of its key
+// (null row: the key's id, the row a flushed cache builds it into).
+__global__ __launch_bounds__(256) void k_group_map(u32 n, const u32* rep, const u32* uid, const u32* row, u32* kslot) {
+  const u32 g = blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= n) return;
+  const u32 r = rep[g];
+  kslot[g] = r == 0xFFFFFFFFu ? 0xFFFFFFFFu : row ? row[uid[r]] : uid[r];
+}
 }  // namespace gv
 
 extern "C" {
@@ -80,6 +152,34 @@ hipError_t gvk_kidx_find(const uint32_t* table, uint32_t tslots, const uint32_t*
   if (tslots == 0 || (tslots & (tslots - 1))) return hipErrorInvalidValue;
   hipLaunchKernelGGL(gv::k_kidx_find, dim3((n + 255) / 256), dim3(256), 0, st, table, tslots - 1, rows, count, seed,
                      pub33, n, slot_out, miss);
+  return hipGetLastError();
+}
+
+hipError_t gvk_group_find(const uint32_t* table, uint32_t tslots, const uint32_t* rows, uint32_t count, uint64_t seed,
+                          const uint32_t* kx, const uint32_t* kpfx, uint32_t CU, const uint32_t* ucount, uint32_t capU,
+                          uint32_t* row, uint32_t* miss, uint32_t* mcount, hipStream_t st) {
+  if (tslots == 0 || (tslots & (tslots - 1)) || capU == 0 || capU % 256 || capU > CU) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(gv::k_group_find, dim3(capU / 256), dim3(256), 0, st, table, tslots - 1, rows, count, seed, kx,
+                     kpfx, CU, ucount, capU, row, miss, mcount);
+  return hipGetLastError();
+}
+
+hipError_t gvk_group_put(uint32_t* table, uint32_t tslots, uint32_t* rows, uint64_t seed, const uint32_t* kx,
+                         const uint32_t* kpfx, uint32_t CU, const uint32_t* list, uint32_t n, uint32_t base,
+                         uint32_t* mx, uint32_t* mpfx, hipStream_t st) {
+  if (n == 0) return hipSuccess;
+  if (tslots == 0 || (tslots & (tslots - 1)) || n > CU) return hipErrorInvalidValue;
+  const dim3 blk(256), grd((n + 255) / 256);
+  hipLaunchKernelGGL(gv::k_group_put, grd, blk, 0, st, kx, kpfx, CU, list, n, base, rows, mx, mpfx);
+  hipLaunchKernelGGL(gv::k_kidx_put, grd, blk, 0, st, table, tslots - 1, (const uint32_t*)rows, n, base,
+                     (const uint32_t*)nullptr, seed, (uint32_t*)nullptr);
+  return hipGetLastError();
+}
+
+hipError_t gvk_group_map(uint32_t n, const uint32_t* rep, const uint32_t* uid, const uint32_t* row, uint32_t* kslot,
+                         hipStream_t st) {
+  if (n == 0) return hipSuccess;
+  hipLaunchKernelGGL(gv::k_group_map, dim3((n + 255) / 256), dim3(256), 0, st, n, rep, uid, row, kslot);
   return hipGetLastError();
 }
 }

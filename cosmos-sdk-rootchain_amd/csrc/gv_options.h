@@ -114,6 +114,9 @@ struct Options {
   bool two_ladders = true;      // ... whose ladders alternate two high-priority streams, so the next ladder starts in
                                 // the current one's tail (bitmap writes kept in call order; GV_TWO_LADDERS=0: A/B)
   bool group_keys = true;       // pub33 throughput batches parse each distinct key once (group_keys; GV_GROUP_KEYS=0: A/B)
+  bool group_reuse = true;      // ... and a set keeps the tables of the keys it has built: a later batch on the set
+                                // builds only the keys it has not seen (the set's arena as a cache, filled then
+                                // flushed; "group_reuse", GV_GROUP_REUSE=0: every call rebuilds)
   bool keys_scratch = true;     // key tables: forward entries through coalesced scratch rows (GV_KEYS_SCRATCH=0: A/B)
   bool sort_keys = true;        // keyed k4 batches run their lanes in slot order (gv_sort.hip; GV_SORT_KEYS=0: A/B)
   size_t group_min = 16384;     // ... batches of at least this many items
@@ -275,10 +278,19 @@ constexpr Row kRows[] = {
     {nullptr, GVO(keys_scratch), A_BOOL, 0, 1, X_ASIS, FX_NONE, false, "GV_KEYS_SCRATCH", E_NOT0},
     {nullptr, GVO(lane_burst), A_RANGE, 1, kMaxItems, X_ASIS, FX_NONE, false, "GV_LANE_BURST", E_MIN1},
 };
+// Rows added after the table was recorded: tests/golden/options_parent.json
+// pins kRows' keys and variables one to one (tests/test_options_host.py), so a
+// later option stands here.  Same columns, same rules: opt_find and
+// opt_from_env read both.
+constexpr Row kRowsLater[] = {
+    {"group_reuse", GVO(group_reuse), A_BOOL, 0, 1, X_ASIS, FX_QUIESCE, true, "GV_GROUP_REUSE", E_NOT0},
+};
 #undef GVO
 
 static inline const Row* opt_find(const char* key) {
   for (const Row& r : kRows)
+    if (r.name && !strcmp(key, r.name)) return &r;
+  for (const Row& r : kRowsLater)
     if (r.name && !strcmp(key, r.name)) return &r;
   return nullptr;
 }
@@ -333,9 +345,9 @@ static inline long long opt_read(const Options& o, const Row& r) {
 // getenv, or a test's stand-in.
 template <class G>
 static inline void opt_from_env(Options& o, G&& getenv_fn) {
-  for (const Row& r : kRows) {
+  auto one = [&](const Row& r) {
     const char* s = r.env ? getenv_fn(r.env) : nullptr;
-    if (!s) continue;
+    if (!s) return;
     const int iv = atoi(s);
     switch (r.env_rule) {
       case E_NONE: break;
@@ -347,7 +359,9 @@ static inline void opt_from_env(Options& o, G&& getenv_fn) {
       case E_MIN1: opt_store(o, r, iv < 1 ? 1 : iv); break;
       case E_RAW_U: o.*r.f.z = (size_t)strtoull(s, nullptr, 10); break;
     }
-  }
+  };
+  for (const Row& r : kRows) one(r);
+  for (const Row& r : kRowsLater) one(r);
 }
 
 }  // namespace gvopt

@@ -138,6 +138,18 @@ struct Set {
   uint32_t *g_kqt = nullptr, *g_kzq = nullptr, *g_kok = nullptr, *g_kqt2 = nullptr, *g_kzq2 = nullptr;
   size_t gcap = 0;
   int g_ent = 0, g_ng = 0;                        // the arena's layout: words per group table, groups per key
+  // the arena as a cache of key tables (option "group_reuse"; DESIGN section
+  // 4.1k): rows [0, g_count) hold the tables of the keys whose raw rows
+  // (GV_KIDX_ROW words, gv_kidx.h) are in g_rows, g_idx the open-addressing
+  // table over them (g_T words, one block with g_rows).  g_live: the rows, the
+  // table and g_count describe what the arena holds; g_route: the schedule the
+  // tables were built for (GV_ROUTE_*) -- with g_ent, g_ng and the allocation
+  // (ensure_group_arena clears g_live) the cache's validity tag
+  uint32_t *g_rows = nullptr, *g_idx = nullptr;
+  size_t g_T = 0, g_count = 0;
+  bool g_live = false;
+  int g_route = -1;
+  uint64_t g_seed = 0;                            // the table's hash seed (ctx->opt.kidx_seed when it was filled)
   uint32_t* h_count = nullptr;                    // pinned: the distinct-key count read back
   // pinned host staging
   uint8_t* h_in = nullptr;
@@ -744,6 +756,9 @@ struct gv_ctx {
   std::atomic<uint64_t> keys_replaced{0};   // slots gv_keys_replace rewrote since gv_open ("keys_replaced")
   std::mutex keys_mu;
   std::atomic<uint64_t> kidx_hit{0}, kidx_miss{0};   // pub33 device batches routed keyed / that fell through
+  // the grouped route's key-table cache (option "group_reuse"): keys whose tables were reused / built by calls
+  // with the option on, caches flushed, k_group_* launches ("group_reuse_hit", "_built", "_reset", "_launches")
+  std::atomic<uint64_t> grp_hit{0}, grp_built{0}, grp_reset{0}, grp_launches{0};
   std::atomic<uint64_t> kidx_launches{0};            // k_kidx_* launches since gv_open ("keys_index_launches")
   std::atomic<uint64_t> kidx_find_ns{0};             // time_kernels: the last routed lookup's k_kidx_find
   // ed25519 key arena (gv_ed_keys_load), same on every device
@@ -885,13 +900,19 @@ int ensure_gtab6(gv_ctx* ctx, Dev* d, Set* s, hipStream_t st, bool want, bool sy
 // group tables), charged to the HBM budget like the other optional tables.
 // ent: words per group table (GV_KEY_WORDS: 16 entries; GV_K6_KEY_WORDS: 32),
 // ng: groups per key (4; the kg layouts GV_KG_NGS).
+// ... and, per key, its raw row and its share of the cache's table
+// (kidx_table_words below: a power of two >= 2 cap).
+size_t kidx_table_words(size_t cap);
 size_t group_arena_bytes(size_t cap, int ent, int ng) {
-  return cap * ((size_t)ent * 4 * ng + 8 * 4 * ng + 4);
+  return cap * ((size_t)ent * 4 * ng + 8 * 4 * ng + 4) + (cap * GV_KIDX_ROW + kidx_table_words(cap)) * 4;
 }
 int ensure_group_arena(gv_ctx* ctx, Dev* d, Set* s, size_t cap, int ent, int ng) {
   if (cap <= s->gcap && ent == s->g_ent && ng == s->g_ng) return GV_OK;
-  for (uint32_t** p : {&s->g_kqt, &s->g_kzq, &s->g_kok, &s->g_kqt2, &s->g_kzq2})
+  for (uint32_t** p : {&s->g_kqt, &s->g_kzq, &s->g_kok, &s->g_kqt2, &s->g_kzq2, &s->g_rows})
     if (*p) { (void)hipFree(*p); *p = nullptr; }
+  s->g_idx = nullptr;
+  s->g_live = false;                              // a new allocation holds no tables
+  s->g_count = 0;
   if (s->gcap) d->opt_bytes -= std::min(d->opt_bytes, group_arena_bytes(s->gcap, s->g_ent, s->g_ng));
   s->gcap = 0;
   s->g_ent = ent;
@@ -901,12 +922,15 @@ int ensure_group_arena(gv_ctx* ctx, Dev* d, Set* s, size_t cap, int ent, int ng)
   if (hipMalloc(&s->g_kqt, cap * eb) != hipSuccess || hipMalloc(&s->g_kzq, cap * 8 * 4) != hipSuccess ||
       hipMalloc(&s->g_kok, cap * 4) != hipSuccess ||
       hipMalloc(&s->g_kqt2, cap * (ng - 1) * eb) != hipSuccess ||
-      hipMalloc(&s->g_kzq2, cap * (ng - 1) * 8 * 4) != hipSuccess) {
+      hipMalloc(&s->g_kzq2, cap * (ng - 1) * 8 * 4) != hipSuccess ||
+      hipMalloc(&s->g_rows, (cap * GV_KIDX_ROW + kidx_table_words(cap)) * 4) != hipSuccess) {
     (void)hipGetLastError();
-    for (uint32_t** p : {&s->g_kqt, &s->g_kzq, &s->g_kok, &s->g_kqt2, &s->g_kzq2})
+    for (uint32_t** p : {&s->g_kqt, &s->g_kzq, &s->g_kok, &s->g_kqt2, &s->g_kzq2, &s->g_rows})
       if (*p) { (void)hipFree(*p); *p = nullptr; }
     return GV_ENOMEM;
   }
+  s->g_T = kidx_table_words(cap);
+  s->g_idx = s->g_rows + cap * GV_KIDX_ROW;
   s->gcap = cap;
   d->opt_bytes += group_arena_bytes(cap, ent, ng);
   return GV_OK;
@@ -916,20 +940,35 @@ int ensure_group_arena(gv_ctx* ctx, Dev* d, Set* s, size_t cap, int ent, int ng)
 // for the pub33 pipeline, inputs on the device): the SoA rows are unpacked,
 // the items grouped by key (k_dedupe*), and when the batch has at most
 // n / group_div distinct keys their tables are built once into the set's
-// batch arena and b is switched to the keyed pipeline with the key id as
-// slot.  Scratch: the set's per-lane Q-table region (unused by the keyed
-// pipeline; the pub33 pipeline rewrites it).  One 4-byte read-back (the
-// distinct-key count) decides the route.
+// batch arena and b is switched to the keyed pipeline with the key's arena
+// row as slot.  Scratch: the set's per-lane Q-table region (unused by the
+// keyed pipeline; the pub33 pipeline rewrites it).  One read-back (the
+// distinct-key count and, with it, the count of keys the set's cache does not
+// hold) decides the route and what is built.
+//
+// group_reuse: the arena's rows [0, g_count) keep the
+// tables of the keys of earlier batches on this set.  k_group_find looks the
+// batch's distinct keys up before the read-back; the keys it missed are built
+// into rows [g_count, g_count + M) and entered (k_group_put), and the items'
+// slots are the rows (k_group_map).  When the rows do not fit, or the tables
+// at hand are another schedule's, the cache is flushed: this call builds all
+// its keys into rows [0, U) as a call without the option does, and enters
+// them.  g_count is committed once every launch is enqueued; an error on the
+// way leaves the cache dropped (the next call starts cold).
 int group_keys(gv_ctx* ctx, Dev* d, Set* s, gvk_batch& b, size_t n, hipStream_t st, uint32_t** used_end = nullptr) {
   const size_t C = b.C;
   size_t T = 512;
   while (T < 2 * n) T <<= 1;
   const size_t capU = round_up(std::max<size_t>(C / ctx->opt.group_div, 256), 256);
+  const bool reuse = ctx->opt.group_reuse;
+  const uint64_t seed = ctx->opt.kidx_seed;
   uint32_t* q = s->qtab;
   uint32_t *rep = q, *uid = q + C, *kslot = q + 2 * C, *count = q + 3 * C, *table = q + 3 * C + 256;
   uint32_t* kx = table + T;
   uint32_t* kpfx = kx + 8 * capU;
-  uint32_t* sc = kpfx + capU;                   // the key-table build's scratch rows (gvk_keys_scratch_words)
+  // group_reuse: each distinct key's cache row, the keys missed, their (x, prefix) gathered dense for the build
+  uint32_t *krow = kpfx + capU, *miss = krow + capU, *mx = miss + capU, *mpfx = mx + 8 * capU;
+  uint32_t* sc = reuse ? mpfx + capU : kpfx + capU;   // the key-table build's scratch rows (gvk_keys_scratch_words)
   const size_t used = (size_t)(sc - q), total = (size_t)GV_QTAB_WORDS * C;
   const size_t room = used < total ? total - used : 0;
   if (gvk_keys_scratch_words((uint32_t)capU, GV_LGRP, GV_QTAB_N, 0) > room) return GV_OK;   // no room: pub33
@@ -945,12 +984,29 @@ int group_keys(gv_ctx* ctx, Dev* d, Set* s, gvk_batch& b, size_t n, hipStream_t 
   // item order or (keyed, key-ordered lanes) in slot order
   CK(gvk_unpack(b.pub33, nullptr, nullptr, (uint32_t)n, (uint32_t)C, b.in_x, b.in_pfx, b.in_r, b.in_s, b.in_e, st));
   b.unpacked = 2;
-  CK(gvk_dedupe((uint32_t)n, (uint32_t)C, b.in_x, b.in_pfx, table, (uint32_t)T, rep, uid, count, kslot,
-                (uint32_t)capU, (uint32_t)capU, kx, kpfx, st));
-  CK(hipMemcpyAsync(s->h_count, count, 4, hipMemcpyDeviceToHost, st));
+  if (!reuse) s->g_live = false;                  // this call overwrites rows [0, U)
+  const bool looked = reuse && s->g_live && s->g_seed == seed;
+  // (a lookup in flight: the items' slots follow the decision, in one pass -- k_group_map)
+  CK(gvk_dedupe((uint32_t)n, (uint32_t)C, b.in_x, b.in_pfx, table, (uint32_t)T, rep, uid, count,
+                looked ? nullptr : kslot, (uint32_t)capU, (uint32_t)capU, kx, kpfx, st));
+  // a failure from here on drops the cache, unless the batch leaves for the
+  // pub33 pipeline with the arena untouched (keep) or all is enqueued (commit)
+  struct Drop {
+    Set* s;
+    bool armed;
+    ~Drop() { if (armed) s->g_live = false; }
+  } drop{s, false};
+  if (looked) {
+    drop.armed = true;                            // (count[1], the misses: cleared by gvk_dedupe)
+    CK(gvk_group_find(s->g_idx, (uint32_t)s->g_T, s->g_rows, (uint32_t)s->g_count, seed, kx, kpfx,
+                      (uint32_t)capU, count, (uint32_t)capU, krow, miss, count + 1, st));
+    ctx->grp_launches++;
+  }
+  CK(hipMemcpyAsync(s->h_count, count, looked ? 8 : 4, hipMemcpyDeviceToHost, st));
   CK(hipStreamSynchronize(st));
   const size_t U = *s->h_count;
-  if (U == 0 || U * ctx->opt.group_div > n || U > capU) return GV_OK;   // many distinct keys: the pub33 pipeline
+  auto keep = [&] { drop.armed = false; return GV_OK; };
+  if (U == 0 || U * ctx->opt.group_div > n || U > capU) return keep();   // many distinct keys: the pub33 pipeline
   // the layout: kg (5-bit windows over kgng groups) > k6 (6-bit, 4 groups) > k4,
   // each needing gtab6 (kg, k6) and its arena within the HBM budget
   if (((ctx->opt.k6 && k6_room) || kg_room) && (rc = ensure_gtab6(ctx, d, s, st, true))) return rc;
@@ -976,36 +1032,77 @@ int group_keys(gv_ctx* ctx, Dev* d, Set* s, gvk_batch& b, size_t n, hipStream_t 
   }
   if (!kg && !k6 && (rc = ensure_gtab4(ctx, d, s, st))) return rc;
   if (!kg && !k6 && (rc = arena(GV_KEY_WORDS, GV_LGRP)))
-    return rc == GV_ENOMEM ? GV_OK : rc;
-  // the tables are built on the set's side stream while k_scalar_inv (which
-  // does not read keys) runs on st: both are one wave per SIMD or so
-  CK(hipEventRecord(s->fork, st));
-  CK(hipStreamWaitEvent(s->side, s->fork, 0));
-  // the forward pass's entries in coalesced scratch rows after the ratio and
-  // E rows, when they fit (else through the tables themselves)
+    return rc == GV_ENOMEM ? GV_OK : rc;        // (a refused arena was freed first: the cache is dropped)
+  // what is built, and where: the keys the lookup missed behind the rows in
+  // use, or -- a cold, flushed or switched-off cache -- every key from row 0
+  const int route = kg ? GV_ROUTE_KG : k6 ? GV_ROUTE_K6 : GV_ROUTE_K4;
+  const uint32_t kC = (uint32_t)(reuse ? s->gcap : capU);
+  bool append = looked && s->g_live && s->g_route == route;   // (g_live: the arena was not reallocated above)
+  if (append && s->g_count + s->h_count[1] > s->gcap) append = false;
+  const size_t M = append ? s->h_count[1] : U, base = append ? s->g_count : 0;
+  const uint32_t *bx = append ? mx : kx, *bpfx = append ? mpfx : kpfx;
+  if (reuse) {
+    drop.armed = true;
+    if (!append) {
+      if (s->g_live && s->g_count) ctx->grp_reset++;
+      s->g_live = false;
+      CK(hipMemsetAsync(s->g_idx, 0xFF, s->g_T * 4, st));
+    }
+    CK(gvk_group_put(s->g_idx, (uint32_t)s->g_T, s->g_rows, seed, kx, kpfx, (uint32_t)capU,
+                     append ? miss : nullptr, (uint32_t)M, (uint32_t)base, append ? mx : nullptr,
+                     append ? mpfx : nullptr, st));
+    if (M) ctx->grp_launches += 2;
+    if (looked) {
+      CK(gvk_group_map((uint32_t)n, rep, uid, append ? krow : nullptr, kslot, st));
+      ctx->grp_launches++;
+    }
+  }
   const int nt = k6 ? GV_K6_NT : GV_QTAB_N, ng = kg ? kgng : GV_LGRP;
-  const int with_qe = ctx->opt.keys_scratch && gvk_keys_scratch_words((uint32_t)U, ng, nt, 1) <= room ? 1 : 0;
-  if (kg)
-    CK(gvk_keys_build_rows_kg((uint32_t)U, (uint32_t)capU, kx, kpfx, sc, with_qe, s->g_kqt, s->g_kzq,
-                              (uint32_t)capU, s->g_kok, s->g_kqt2, s->g_kzq2, kgng, s->side));
-  else if (k6)
-    CK(gvk_keys_build_rows6((uint32_t)U, (uint32_t)capU, kx, kpfx, sc, with_qe, s->g_kqt, s->g_kzq, (uint32_t)capU,
-                            s->g_kok, s->g_kqt2, s->g_kzq2, s->side));
-  else
-    CK(gvk_keys_build_rows((uint32_t)U, (uint32_t)capU, kx, kpfx, sc, with_qe, s->g_kqt, s->g_kzq, (uint32_t)capU,
-                           s->g_kok, s->g_kqt2, s->g_kzq2, s->side));
-  if (used_end) *used_end = sc + gvk_keys_scratch_words((uint32_t)U, ng, nt, with_qe);
-  CK(hipEventRecord(s->keys_done, s->side));
-  b.keys_ready = s->keys_done;
+  int with_qe = 0;
+  if (M) {
+    // the tables are built on the set's side stream while k_scalar_inv (which
+    // does not read keys) runs on st: both are one wave per SIMD or so
+    CK(hipEventRecord(s->fork, st));
+    CK(hipStreamWaitEvent(s->side, s->fork, 0));
+    // the forward pass's entries in coalesced scratch rows after the ratio and
+    // E rows, when they fit (else through the tables themselves)
+    with_qe = ctx->opt.keys_scratch && gvk_keys_scratch_words((uint32_t)M, ng, nt, 1) <= room ? 1 : 0;
+    if (kg)
+      CK(gvk_keys_build_rows_kg((uint32_t)M, (uint32_t)capU, bx, bpfx, sc, with_qe, (uint32_t)base, s->g_kqt,
+                                s->g_kzq, kC, s->g_kok, s->g_kqt2, s->g_kzq2, kgng, s->side));
+    else if (k6)
+      CK(gvk_keys_build_rows6((uint32_t)M, (uint32_t)capU, bx, bpfx, sc, with_qe, (uint32_t)base, s->g_kqt, s->g_kzq,
+                              kC, s->g_kok, s->g_kqt2, s->g_kzq2, s->side));
+    else
+      CK(gvk_keys_build_rows((uint32_t)M, (uint32_t)capU, bx, bpfx, sc, with_qe, (uint32_t)base, s->g_kqt, s->g_kzq,
+                             kC, s->g_kok, s->g_kqt2, s->g_kzq2, s->side));
+    CK(hipEventRecord(s->keys_done, s->side));
+    b.keys_ready = s->keys_done;
+  } else {
+    // nothing to build: the rows were built on the side stream by earlier
+    // calls on this set, whose ladders waited for them -- and so does this one,
+    // should such a call have failed before its ladder was enqueued
+    CK(hipStreamWaitEvent(st, s->keys_done, 0));
+  }
+  if (used_end) *used_end = sc + (M ? gvk_keys_scratch_words((uint32_t)M, ng, nt, with_qe) : 0);
   b.pub33 = nullptr;
   b.kslot = kslot; b.kqt = s->g_kqt; b.kzq = s->g_kzq; b.kok = s->g_kok;
-  b.kC = (uint32_t)capU; b.kcount = (uint32_t)U;
+  b.kC = kC; b.kcount = (uint32_t)(base + M);
   b.kqt2 = s->g_kqt2; b.gtab4 = d->gtab4;       // null gtab4: the 125-doubling keyed ladder
   b.gtabf = ctx->opt.gfull ? d->gtabf : nullptr;    // built by ensure_gtab4 above on first use
   b.k6 = kg ? kgng : k6 ? 4 : 0; b.gtab6 = d->gtab6;
   b.kqw = kg ? 2 : 0;
+  if (reuse) {                                  // everything is enqueued: the cache now holds these rows
+    s->g_count = base + M;
+    s->g_route = route;
+    s->g_seed = seed;
+    s->g_live = true;
+    ctx->grp_hit += U - M;
+    ctx->grp_built += M;
+  }
+  drop.armed = false;
   d->grouped_batches++;
-  d->grouped_keys += U;
+  d->grouped_keys += M;
   return GV_OK;
 }
 
@@ -1711,7 +1808,7 @@ int slice_group(gv_ctx* ctx, Dev* d, size_t lo, size_t n, const HostBatch& hb, K
   b.in_x = g->in_x; b.in_pfx = g->in_pfx; b.in_r = g->in_r; b.in_s = g->in_s; b.in_e = g->in_e;
   if ((rc = group_keys(ctx, d, g, b, n, g->st))) return rc;
   if (!b.kslot) return set_release(g, g->st);   // many distinct keys after all: per-chunk pipeline
-  CK(hipStreamWaitEvent(g->st, b.keys_ready, 0));
+  if (b.keys_ready) CK(hipStreamWaitEvent(g->st, b.keys_ready, 0));   // (null: every key's tables were at hand)
   CK(hipEventRecord(g->grp_ready, g->st));
   ka->kqt = b.kqt; ka->kzq = b.kzq; ka->kok = b.kok; ka->kqt2 = b.kqt2; ka->kzq2 = g->g_kzq2;
   ka->kC = b.kC; ka->kcount = b.kcount; ka->gtab4 = b.gtab4;
@@ -2086,7 +2183,7 @@ void free_set(Set& s) {
   if (s.keys_done) (void)hipEventDestroy(s.keys_done);
   if (s.grp_ready) (void)hipEventDestroy(s.grp_ready);
   if (s.side) { (void)hipStreamSynchronize(s.side); (void)hipStreamDestroy(s.side); }
-  for (uint32_t* p : {s.g_kqt, s.g_kzq, s.g_kok, s.g_kqt2, s.g_kzq2})
+  for (uint32_t* p : {s.g_kqt, s.g_kzq, s.g_kok, s.g_kqt2, s.g_kzq2, s.g_rows})
     if (p) (void)hipFree(p);
   if (s.h_count) (void)hipHostFree(s.h_count);
   if (s.lad) { (void)hipStreamSynchronize(s.lad); (void)hipStreamDestroy(s.lad); }
@@ -3481,6 +3578,10 @@ int gv_get_option(gv_ctx* ctx, const char* key, long long* val) {
               {"keys_index_hit", (long long)ctx->kidx_hit.load()},     // pub33 device batches routed keyed
               {"keys_index_miss", (long long)ctx->kidx_miss.load()},   // ... that fell through on a miss
               {"keys_index_launches", (long long)ctx->kidx_launches.load()},   // k_kidx_* launches so far
+              {"group_reuse_hit", (long long)ctx->grp_hit.load()},       // grouped keys whose tables were at hand
+              {"group_reuse_built", (long long)ctx->grp_built.load()},   // ... and built, by calls with group_reuse on
+              {"group_reuse_reset", (long long)ctx->grp_reset.load()},   // caches flushed (full, or another schedule's)
+              {"group_reuse_launches", (long long)ctx->grp_launches.load()},   // k_group_* launches so far
               {"keys_index_find_ns", (long long)ctx->kidx_find_ns.load()},     // the last routed lookup's kernel
                                                                                // ("time_kernels" on)
               {"kw_qw", GV_KW_QW},                   // the wide arena's window width (build)
@@ -3497,7 +3598,7 @@ int gv_get_option(gv_ctx* ctx, const char* key, long long* val) {
   // radix bits (0: no slot has wide tables) and the slots that have them
   const bool ed = !strcmp(key, "ed_kw_rb") || !strcmp(key, "ed_kw_keys");
   static const char* const kDev[] = {"kw_arena_qw", "kw_arena_ng", "keys_index_live", "keys_index_keys",
-                                     "keys_index_left_out", "keys_index_words"};
+                                     "keys_index_left_out", "keys_index_words", "group_reuse_rows"};
   if (!ed && std::none_of(std::begin(kDev), std::end(kDev), [&](const char* k) { return !strcmp(key, k); }))
     return GV_EINVAL;
   if (ctx->devs.empty()) return GV_EINVAL;
@@ -3506,7 +3607,9 @@ int gv_get_option(gv_ctx* ctx, const char* key, long long* val) {
   Dev* d = ctx->devs[0];
   std::lock_guard<std::mutex> lk(d->mu);
   const bool kw = d->kqtw && d->keysw, has = d->kidx_tab && !d->kidx_failed, ekw = d->ektabw && d->ekeysw;
-  *val = !strcmp(key, "kw_arena_qw")           ? (kw ? d->kw_qw : 0)
+  // (the row capacity of the first scratch set's grouping arena; 0: none yet)
+  *val = !strcmp(key, "group_reuse_rows")      ? (long long)d->set[0].gcap
+         : !strcmp(key, "kw_arena_qw")         ? (kw ? d->kw_qw : 0)
          : !strcmp(key, "kw_arena_ng")         ? (kw ? d->kw_ng : 0)
          : !strcmp(key, "keys_index_live")     ? (long long)kidx_live(ctx, d)
          : !strcmp(key, "keys_index_keys")     ? (long long)(has ? d->kidx_keys : 0)
@@ -3551,6 +3654,14 @@ int gv_set_option(gv_ctx* ctx, const char* key, long long val) {
       if (ctx->keys != 0) return GV_EINVAL;
       break;
   }
+  // a quiescing option may pick the grouped route's table layout, and a fault
+  // injected mid-call leaves a set's rows unknown: every set's key-table cache
+  // starts cold (group_keys)
+  const bool faults = !strcmp(key, "fault_inject");
+  if (faults && quiesce_all(ctx, false, &held)) return GV_EHIP;
+  if (r->fx == gvopt::FX_QUIESCE || faults)
+    for (Dev* d : ctx->devs)
+      for (Set* s : {&d->set[0], &d->set[1], &d->gset[0], &d->gset[1]}) s->g_live = false;
   gvopt::opt_store(ctx->opt, *r, val);
   if (r->fx == gvopt::FX_POOLS)
     for (Dev* d : ctx->devs) {

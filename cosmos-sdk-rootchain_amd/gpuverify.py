@@ -695,7 +695,8 @@ class Verifier:
         _check(self._L.gv_host_free(self._ctx, p), "gv_host_free")
 
     def group_stats(self, slot: int = 0):
-        """(batches that took the in-batch key grouping, distinct keys built) on device slot."""
+        """(batches that took the in-batch key grouping, keys whose tables were built) on device slot;
+        with "group_reuse" on, a key whose tables the scratch set still holds is not built again."""
         b, k = ctypes.c_uint64(), ctypes.c_uint64()
         _check(self._L.gv_group_stats(self._ctx, slot, ctypes.byref(b), ctypes.byref(k)), "gv_group_stats")
         return b.value, k.value

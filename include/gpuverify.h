@@ -389,6 +389,13 @@ int gv_ed_keys_wide_point(gv_ctx* ctx, size_t n, const uint32_t* slots, uint32_t
  * items / "group_div" (default 5) parses each distinct key once -- grouped
  * on the device, tables built into a per-batch arena, the items verified by
  * the keyed pipeline; same verdicts; default 1, env GV_GROUP_KEYS),
+ * "group_reuse" (0/1: that arena is kept as a cache -- each of a device's
+ * scratch sets remembers the keys whose tables it has built, all 33 bytes
+ * compared, and a later batch on the set builds only the keys it has not
+ * seen; rows are appended until the arena is full, then the cache is flushed
+ * and the batch builds all its keys; any option that drains the pipeline
+ * starts every cache cold; 0: every batch rebuilds every key, no k_group_*
+ * kernel runs; same verdicts; default 1, env GV_GROUP_REUSE),
  * "ed_group" (0/1: ed25519 throughput batches -- gv_verify_ed25519_msgs and
  * the device-resident variant -- of at least "ed_group_min" items (default
  * 196608; host chunks of 262,144 qualify) with at most items / 16 (and 16384) distinct keys build each key's
@@ -543,7 +550,13 @@ int gv_set_option(gv_ctx* ctx, const char* key, long long val);
  * that fell through on a miss, since gv_open), "keys_index_launches" (index
  * kernels launched since gv_open: 0 while the option has never been on) and
  * "keys_index_find_ns" (the last routed lookup's kernel, HIP events, with
- * "time_kernels" on).
+ * "time_kernels" on), and "group_reuse" with (read only) "group_reuse_hit" /
+ * "group_reuse_built" (distinct keys of grouped batches whose tables were at
+ * hand / were built, by calls with the option on, since gv_open),
+ * "group_reuse_reset" (caches flushed: full, or holding another schedule's
+ * tables), "group_reuse_launches" (k_group_* launches since gv_open: 0 while
+ * the option has never been on) and "group_reuse_rows" (the row capacity of
+ * the first device's first scratch set's grouping arena; 0: none yet).
  * GV_EINVAL for any other key.  Instrumentation (bench route
  * attribution). */
 int gv_get_option(gv_ctx* ctx, const char* key, long long* val);
@@ -605,7 +618,8 @@ int gv_host_alloc(gv_ctx* ctx, size_t bytes, void** out);
 int gv_host_free(gv_ctx* ctx, void* p);
 /* In-batch key grouping (options "group_keys", "ed_group"): on dev_slot, the
  * number of batches -- secp256k1 and ed25519 -- that took the grouped (keyed)
- * pipeline and the distinct keys whose tables they built. */
+ * pipeline and the keys whose tables they built (with "group_reuse" the
+ * keys the sets' caches did not hold; every distinct key without it). */
 int gv_group_stats(gv_ctx* ctx, int dev_slot, uint64_t* batches, uint64_t* keys);
 /* Batches per secp256k1 schedule on dev_slot since gv_open, out[GV_ROUTES]:
  * GV_ROUTE_PUB33 (per-item pipeline: k_prep + k_ecmult), GV_ROUTE_KEYED125
