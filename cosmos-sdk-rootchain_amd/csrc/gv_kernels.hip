@@ -1925,8 +1925,13 @@ constexpr int kn_row(int qw, int ng) {
 // front kernel's wave), parked in LDS (9 KB per block) to 126: 4 waves per
 // SIMD (kg4: C2 216 -> 222M/s alternated, profiles/r06/ab/ab3).  The arena's
 // ladders keep zq in registers (kw at 133 VGPRs: 440 vs 428M/s with LDS).
+// That was decided beside a front that rebuilt every key in every call.  Since
+// a set keeps its tables (group_reuse) and a promoted set runs these ladders
+// with no build beside them, registers win: kg9 pipelined on the C2 batch
+// 3.41 ms per step against 3.55 with LDS and 3.52-3.57 with the allocator
+// bound to 3 waves (GV_KN_WAVES=3; profiles/r07/group_promote/).  Default 0.
 #ifndef GV_KN_ZQ_LDS
-#define GV_KN_ZQ_LDS 1
+#define GV_KN_ZQ_LDS 0
 #endif
 // GV_KN_PREFETCH (A/B, round 6): the slot loop runs one slot ahead -- slot
 // s + 1's digit is read and its table entry's loads issued before slot s's

@@ -117,6 +117,15 @@ struct Options {
   bool group_reuse = true;      // ... and a set keeps the tables of the keys it has built: a later batch on the set
                                 // builds only the keys it has not seen (the set's arena as a cache, filled then
                                 // flushed; "group_reuse", GV_GROUP_REUSE=0: every call rebuilds)
+  int group_promote = 9;        // ... and a set whose keys recur moves its tables to the kg layout of this many groups
+                                // (6, 7, 9; 0 = never: k4's layout): after two warm calls and on a third, each
+                                // building fewer keys per item than half the break-even, the set rebuilds its keys
+                                // once in the kg layout and its calls run k_ecmult_kn<5, NG> -- 10 doublings
+                                // instead of 30 at 9 groups; it goes back when a call misses more keys than the
+                                // break-even ("group_promote", GV_GROUP_PROMOTE).  Inert when
+                                // "kg" or "k6" names a layout
+  size_t group_promote_min = 262144;   // ... on a batch of at least this many items (one full residency of the ladder:
+                                       // 256 CUs x 4 SIMDs x 4 waves x 64 lanes; "group_promote_min")
   bool keys_scratch = true;     // key tables: forward entries through coalesced scratch rows (GV_KEYS_SCRATCH=0: A/B)
   bool sort_keys = true;        // keyed k4 batches run their lanes in slot order (gv_sort.hip; GV_SORT_KEYS=0: A/B)
   size_t group_min = 16384;     // ... batches of at least this many items
@@ -284,6 +293,10 @@ constexpr Row kRows[] = {
 // opt_from_env read both.
 constexpr Row kRowsLater[] = {
     {"group_reuse", GVO(group_reuse), A_BOOL, 0, 1, X_ASIS, FX_QUIESCE, true, "GV_GROUP_REUSE", E_NOT0},
+    // 0 or one of the kg layouts above k4's four groups (gv_kernels.h GV_KG_NGS)
+    {"group_promote", GVO(group_promote), A_SET, 1 | 1 << 6 | 1 << 7 | 1 << 9, 0, X_ASIS, FX_QUIESCE, true,
+     "GV_GROUP_PROMOTE", E_SETTER},
+    {"group_promote_min", GVO(group_promote_min), A_RANGE, 0, kMaxItems, X_ASIS, FX_NONE, true},
 };
 #undef GVO
 

@@ -150,6 +150,17 @@ struct Set {
   bool g_live = false;
   int g_route = -1;
   uint64_t g_seed = 0;                            // the table's hash seed (ctx->opt.kidx_seed when it was filled)
+  // layout promotion (option "group_promote").  g_hist: the
+  // set's last two grouped calls on the k4 layout, newest in bit 0 -- set when
+  // the call was warm (a lookup ran, nothing flushed) and built fewer keys
+  // than items x T_up.  g_promoted: the set's key stream runs on the kg layout.
+  // Both describe the stream, not the tables: they outlive a dropped cache and
+  // are cleared by the options that choose the grouped schedule.
+  // g_promo_refused: the promoted arena was refused (no retry until a
+  // quiescing option).  g_wide: the arena was allocated for a promoted layout;
+  // k4's rows index a prefix of it, so a demoted set keeps it
+  unsigned g_hist = 0;
+  bool g_promoted = false, g_promo_refused = false, g_wide = false;
   uint32_t* h_count = nullptr;                    // pinned: the distinct-key count read back
   // pinned host staging
   uint8_t* h_in = nullptr;
@@ -308,6 +319,7 @@ struct Dev {
   hipEvent_t plain_done = nullptr;                // the last non-pipelined call on the context stream
   bool hi_used[2] = {false, false}, plain_used = false, bits_used = false;
   uint64_t grouped_batches = 0, grouped_keys = 0;  // in-batch key grouping taken (gv_group_stats)
+  int group_layout = 0;                           // groups per key of the last grouped call's tables ("group_layout")
   uint64_t routes[GV_ROUTES] = {};                // batches per schedule (gv_route_stats)
   int flip = 0;
   double last_slice_ms = 0;                       // host-buffer calls: this device's slice, wall time
@@ -759,6 +771,8 @@ struct gv_ctx {
   // the grouped route's key-table cache (option "group_reuse"): keys whose tables were reused / built by calls
   // with the option on, caches flushed, k_group_* launches ("group_reuse_hit", "_built", "_reset", "_launches")
   std::atomic<uint64_t> grp_hit{0}, grp_built{0}, grp_reset{0}, grp_launches{0};
+  // ... and its layout promotion (option "group_promote"): sets moved to the kg layout / back to k4's
+  std::atomic<uint64_t> grp_promoted{0}, grp_demoted{0};
   std::atomic<uint64_t> kidx_launches{0};            // k_kidx_* launches since gv_open ("keys_index_launches")
   std::atomic<uint64_t> kidx_find_ns{0};             // time_kernels: the last routed lookup's k_kidx_find
   // ed25519 key arena (gv_ed_keys_load), same on every device
@@ -906,13 +920,21 @@ size_t kidx_table_words(size_t cap);
 size_t group_arena_bytes(size_t cap, int ent, int ng) {
   return cap * ((size_t)ent * 4 * ng + 8 * 4 * ng + 4) + (cap * GV_KIDX_ROW + kidx_table_words(cap)) * 4;
 }
+// The arena at hand serves this layout: the one it was allocated for, or --
+// an arena allocated by a layout promotion (g_wide) -- k4's four groups, whose
+// rows (qi * 3 + grp - 1; Z rows (grp - 1) * 8 * kC) index a prefix of the
+// larger allocation: a demoted set frees and allocates nothing.
+bool group_arena_fits(const Set* s, size_t cap, int ent, int ng) {
+  return cap <= s->gcap && ent == s->g_ent && (ng == s->g_ng || (s->g_wide && ng == GV_LGRP && ng < s->g_ng));
+}
 int ensure_group_arena(gv_ctx* ctx, Dev* d, Set* s, size_t cap, int ent, int ng) {
-  if (cap <= s->gcap && ent == s->g_ent && ng == s->g_ng) return GV_OK;
+  if (group_arena_fits(s, cap, ent, ng)) return GV_OK;
   for (uint32_t** p : {&s->g_kqt, &s->g_kzq, &s->g_kok, &s->g_kqt2, &s->g_kzq2, &s->g_rows})
     if (*p) { (void)hipFree(*p); *p = nullptr; }
   s->g_idx = nullptr;
   s->g_live = false;                              // a new allocation holds no tables
   s->g_count = 0;
+  s->g_wide = false;                              // (group_keys marks a promotion's allocation)
   if (s->gcap) d->opt_bytes -= std::min(d->opt_bytes, group_arena_bytes(s->gcap, s->g_ent, s->g_ng));
   s->gcap = 0;
   s->g_ent = ent;
@@ -955,6 +977,29 @@ int ensure_group_arena(gv_ctx* ctx, Dev* d, Set* s, size_t cap, int ent, int ng)
 // its keys into rows [0, U) as a call without the option does, and enters
 // them.  g_count is committed once every launch is enqueued; an error on the
 // way leaves the cache dropped (the next call starts cold).
+//
+// group_promote: a set whose keys recur moves from k4's
+// layout to the option's kg layout (more groups: a dearer build per key, fewer
+// doublings per item) and back.  The two constants, serialized on the C2 batch
+// (profiles/r07/group_promote/consts_parent.jsonl): what a built key costs
+// more than in k4's layout, what an item saves on the ladder, in picoseconds.
+// Their ratio is the break-even in keys built per item: a promoted set demotes
+// above it (T_down), a k4 set promotes after two warm calls (and on a third)
+// that each built less than half of it (T_up).
+struct PromoteCost {
+  int ng;
+  uint64_t key_ps, item_ps;
+};
+constexpr PromoteCost kPromoteCost[] = {{6, 5456, 307}, {7, 7170, 497}, {9, 11436, 621}};
+const PromoteCost* promote_cost(int ng) {
+  for (const PromoteCost& c : kPromoteCost)
+    if (c.ng == ng) return &c;
+  return nullptr;
+}
+// keys built over items against the break-even: below half of it / above it
+bool promote_below_up(const PromoteCost& c, size_t built, size_t n) { return 2 * built * c.key_ps < n * c.item_ps; }
+bool promote_above_down(const PromoteCost& c, size_t built, size_t n) { return built * c.key_ps > n * c.item_ps; }
+
 int group_keys(gv_ctx* ctx, Dev* d, Set* s, gvk_batch& b, size_t n, hipStream_t st, uint32_t** used_end = nullptr) {
   const size_t C = b.C;
   size_t T = 512;
@@ -975,6 +1020,11 @@ int group_keys(gv_ctx* ctx, Dev* d, Set* s, gvk_batch& b, size_t n, hipStream_t 
   const bool k6_room = gvk_keys_scratch_words((uint32_t)capU, 4, GV_K6_NT, 0) <= room;
   const int kgng = ctx->opt.kg;                     // 0 or one of GV_KG_NGS
   const bool kg_room = kgng && gvk_keys_scratch_words((uint32_t)capU, kgng, GV_QTAB_N, 0) <= room;
+  // layout promotion: the caller chose no layout ("kg", "k6"), the cache is on
+  // and the promoted layout's build fits the scratch
+  const int png = ctx->opt.group_promote;
+  const PromoteCost* pc = png && !kgng && !ctx->opt.k6 && reuse ? promote_cost(png) : nullptr;
+  if (pc && gvk_keys_scratch_words((uint32_t)capU, png, GV_QTAB_N, 0) > room) pc = nullptr;
   if (!s->h_count && hipHostMalloc((void**)&s->h_count, 64, hipHostMallocDefault) != hipSuccess) {
     s->h_count = nullptr;
     return GV_ENOMEM;
@@ -1009,21 +1059,54 @@ int group_keys(gv_ctx* ctx, Dev* d, Set* s, gvk_batch& b, size_t n, hipStream_t 
   if (U == 0 || U * ctx->opt.group_div > n || U > capU) return keep();   // many distinct keys: the pub33 pipeline
   // the layout: kg (5-bit windows over kgng groups) > k6 (6-bit, 4 groups) > k4,
   // each needing gtab6 (kg, k6) and its arena within the HBM budget
-  if (((ctx->opt.k6 && k6_room) || kg_room) && (rc = ensure_gtab6(ctx, d, s, st, true))) return rc;
+  // ... or, the caller having chosen none, the set's own (group_promote): a
+  // promoted set stays on the kg layout unless this call's lookup missed more
+  // keys than the break-even (a cold call rebuilds in the kg layout: the flag
+  // describes the key stream); a k4 set promotes on a large enough warm call
+  // behind two warm calls, all three below half the break-even
+  const size_t missed = looked ? s->h_count[1] : U;
+  bool promo = false;                             // the kg layout by promotion
+  if (s->g_promoted)
+    promo = pc && !(looked && promote_above_down(*pc, missed, n));
+  else if (pc && !s->g_promo_refused && !d->gtab6_failed)
+    promo = n >= ctx->opt.group_promote_min && (s->g_hist & 3) == 3 && looked && promote_below_up(*pc, missed, n);
+  const int kgsel = promo ? png : kg_room ? kgng : 0;   // the kg layout this call tries (0: none)
+  if (((ctx->opt.k6 && k6_room) || kgsel) && (rc = ensure_gtab6(ctx, d, s, st, true))) return rc;
   // the arena for the set's whole capacity when the budget holds it: a later,
   // larger chunk on this set does not regrow it (hipFree waits for the device)
+  const size_t capA = round_up(std::max<size_t>(s->cap / ctx->opt.group_div, 256), 256);
   auto arena = [&](int ent, int ng) {
-    const size_t capA = round_up(std::max<size_t>(s->cap / ctx->opt.group_div, 256), 256);
-    if (capA > capU && !(capA <= s->gcap && ent == s->g_ent && ng == s->g_ng)) {
+    if (capA > capU && !group_arena_fits(s, capA, ent, ng)) {
       const int r = ensure_group_arena(ctx, d, s, capA, ent, ng);
       if (r != GV_ENOMEM) return r;
     }
     return ensure_group_arena(ctx, d, s, capU, ent, ng);
   };
-  bool kg = kg_room && d->gtab6;
-  if (kg && (rc = arena(GV_KEY_WORDS, kgng))) {
+  bool kg = kgsel && d->gtab6;
+  // a promotion's arena is asked of the budget before the k4 arena is given
+  // up: a refusal leaves the set, its tables and the route as they were
+  if (kg && promo && !group_arena_fits(s, capU, GV_KEY_WORDS, png)) {
+    const size_t held = s->gcap ? group_arena_bytes(s->gcap, s->g_ent, s->g_ng) : 0;
+    if (d->opt_bytes - std::min(d->opt_bytes, held) + group_arena_bytes(capU, GV_KEY_WORDS, png) > ctx->opt.hbm_budget)
+      kg = false;
+  }
+  if (kg && (rc = arena(GV_KEY_WORDS, kgsel))) {
     if (rc != GV_ENOMEM) return rc;
-    kg = false;                                 // no room for kgng groups
+    kg = false;                                 // no room for kgsel groups
+  }
+  if (promo) {
+    if (kg) s->g_wide = true;                   // (k4's rows fit the allocation: a demotion keeps it)
+    if (kg && !s->g_promoted) {
+      s->g_promoted = true;
+      ctx->grp_promoted++;
+    } else if (!kg && !s->g_promoted) {
+      s->g_promo_refused = true;                // no gtab6 or no memory: k4, and no retry until a quiescing option
+    }
+  }
+  if (s->g_promoted && !(promo && kg)) {        // back to k4: flushed below (another schedule's tables)
+    s->g_promoted = false;
+    s->g_hist = 0;
+    ctx->grp_demoted++;
   }
   bool k6 = !kg && ctx->opt.k6 && k6_room && d->gtab6;
   if (k6 && (rc = arena(GV_K6_KEY_WORDS, GV_LGRP))) {
@@ -1031,6 +1114,17 @@ int group_keys(gv_ctx* ctx, Dev* d, Set* s, gvk_batch& b, size_t n, hipStream_t 
     k6 = false;                                 // no room for the 32-entry tables: k4
   }
   if (!kg && !k6 && (rc = ensure_gtab4(ctx, d, s, st))) return rc;
+  // a k4 arena that has to be allocated anyway, for a batch that could promote
+  // its set later, is sized for the promoted layout when the budget holds it
+  // (k4's rows take a prefix): the promotion then frees and allocates nothing
+  // (hipFree drains the device, and 2.5 GB of arena per 1M-item set took up
+  // to ~0.1 s to map: profiles/r07/group_promote/session_b_shapes/)
+  if (!kg && !k6 && pc && !s->g_promoted && !s->g_promo_refused && !d->gtab6_failed &&
+      n >= ctx->opt.group_promote_min && !group_arena_fits(s, capU, GV_KEY_WORDS, GV_LGRP)) {
+    rc = arena(GV_KEY_WORDS, png);
+    if (!rc) s->g_wide = true;
+    else if (rc != GV_ENOMEM) return rc;
+  }
   if (!kg && !k6 && (rc = arena(GV_KEY_WORDS, GV_LGRP)))
     return rc == GV_ENOMEM ? GV_OK : rc;        // (a refused arena was freed first: the cache is dropped)
   // what is built, and where: the keys the lookup missed behind the rows in
@@ -1057,7 +1151,7 @@ int group_keys(gv_ctx* ctx, Dev* d, Set* s, gvk_batch& b, size_t n, hipStream_t 
       ctx->grp_launches++;
     }
   }
-  const int nt = k6 ? GV_K6_NT : GV_QTAB_N, ng = kg ? kgng : GV_LGRP;
+  const int nt = k6 ? GV_K6_NT : GV_QTAB_N, ng = kg ? kgsel : GV_LGRP;
   int with_qe = 0;
   if (M) {
     // the tables are built on the set's side stream while k_scalar_inv (which
@@ -1069,7 +1163,7 @@ int group_keys(gv_ctx* ctx, Dev* d, Set* s, gvk_batch& b, size_t n, hipStream_t 
     with_qe = ctx->opt.keys_scratch && gvk_keys_scratch_words((uint32_t)M, ng, nt, 1) <= room ? 1 : 0;
     if (kg)
       CK(gvk_keys_build_rows_kg((uint32_t)M, (uint32_t)capU, bx, bpfx, sc, with_qe, (uint32_t)base, s->g_kqt,
-                                s->g_kzq, kC, s->g_kok, s->g_kqt2, s->g_kzq2, kgng, s->side));
+                                s->g_kzq, kC, s->g_kok, s->g_kqt2, s->g_kzq2, kgsel, s->side));
     else if (k6)
       CK(gvk_keys_build_rows6((uint32_t)M, (uint32_t)capU, bx, bpfx, sc, with_qe, (uint32_t)base, s->g_kqt, s->g_kzq,
                               kC, s->g_kok, s->g_kqt2, s->g_kzq2, s->side));
@@ -1090,7 +1184,7 @@ int group_keys(gv_ctx* ctx, Dev* d, Set* s, gvk_batch& b, size_t n, hipStream_t 
   b.kC = kC; b.kcount = (uint32_t)(base + M);
   b.kqt2 = s->g_kqt2; b.gtab4 = d->gtab4;       // null gtab4: the 125-doubling keyed ladder
   b.gtabf = ctx->opt.gfull ? d->gtabf : nullptr;    // built by ensure_gtab4 above on first use
-  b.k6 = kg ? kgng : k6 ? 4 : 0; b.gtab6 = d->gtab6;
+  b.k6 = kg ? kgsel : k6 ? 4 : 0; b.gtab6 = d->gtab6;
   b.kqw = kg ? 2 : 0;
   if (reuse) {                                  // everything is enqueued: the cache now holds these rows
     s->g_count = base + M;
@@ -1100,6 +1194,9 @@ int group_keys(gv_ctx* ctx, Dev* d, Set* s, gvk_batch& b, size_t n, hipStream_t 
     ctx->grp_hit += U - M;
     ctx->grp_built += M;
   }
+  // the promotion rule's history: this call on the k4 layout, warm and below T_up
+  s->g_hist = pc && route == GV_ROUTE_K4 ? (s->g_hist << 1 | (append && promote_below_up(*pc, M, n) ? 1u : 0u)) & 3u : 0u;
+  d->group_layout = ng;
   drop.armed = false;
   d->grouped_batches++;
   d->grouped_keys += M;
@@ -3582,6 +3679,8 @@ int gv_get_option(gv_ctx* ctx, const char* key, long long* val) {
               {"group_reuse_built", (long long)ctx->grp_built.load()},   // ... and built, by calls with group_reuse on
               {"group_reuse_reset", (long long)ctx->grp_reset.load()},   // caches flushed (full, or another schedule's)
               {"group_reuse_launches", (long long)ctx->grp_launches.load()},   // k_group_* launches so far
+              {"group_promoted", (long long)ctx->grp_promoted.load()},   // sets moved to the "group_promote" layout
+              {"group_demoted", (long long)ctx->grp_demoted.load()},     // ... and back to k4's
               {"keys_index_find_ns", (long long)ctx->kidx_find_ns.load()},     // the last routed lookup's kernel
                                                                                // ("time_kernels" on)
               {"kw_qw", GV_KW_QW},                   // the wide arena's window width (build)
@@ -3598,7 +3697,8 @@ int gv_get_option(gv_ctx* ctx, const char* key, long long* val) {
   // radix bits (0: no slot has wide tables) and the slots that have them
   const bool ed = !strcmp(key, "ed_kw_rb") || !strcmp(key, "ed_kw_keys");
   static const char* const kDev[] = {"kw_arena_qw", "kw_arena_ng", "keys_index_live", "keys_index_keys",
-                                     "keys_index_left_out", "keys_index_words", "group_reuse_rows"};
+                                     "keys_index_left_out", "keys_index_words", "group_reuse_rows", "group_layout",
+                                     "hbm_optional_bytes"};
   if (!ed && std::none_of(std::begin(kDev), std::end(kDev), [&](const char* k) { return !strcmp(key, k); }))
     return GV_EINVAL;
   if (ctx->devs.empty()) return GV_EINVAL;
@@ -3609,6 +3709,10 @@ int gv_get_option(gv_ctx* ctx, const char* key, long long* val) {
   const bool kw = d->kqtw && d->keysw, has = d->kidx_tab && !d->kidx_failed, ekw = d->ektabw && d->ekeysw;
   // (the row capacity of the first scratch set's grouping arena; 0: none yet)
   *val = !strcmp(key, "group_reuse_rows")      ? (long long)d->set[0].gcap
+         // groups per key of the device's last grouped call (4: k4's and k6's layouts; 0: none yet); the
+         // bytes of optional tables the HBM budget counts on the device
+         : !strcmp(key, "group_layout")        ? (long long)d->group_layout
+         : !strcmp(key, "hbm_optional_bytes")  ? (long long)d->opt_bytes
          : !strcmp(key, "kw_arena_qw")         ? (kw ? d->kw_qw : 0)
          : !strcmp(key, "kw_arena_ng")         ? (kw ? d->kw_ng : 0)
          : !strcmp(key, "keys_index_live")     ? (long long)kidx_live(ctx, d)
@@ -3661,7 +3765,18 @@ int gv_set_option(gv_ctx* ctx, const char* key, long long val) {
   if (faults && quiesce_all(ctx, false, &held)) return GV_EHIP;
   if (r->fx == gvopt::FX_QUIESCE || faults)
     for (Dev* d : ctx->devs)
-      for (Set* s : {&d->set[0], &d->set[1], &d->gset[0], &d->gset[1]}) s->g_live = false;
+      for (Set* s : {&d->set[0], &d->set[1], &d->gset[0], &d->gset[1]}) {
+        s->g_live = false;
+        if (!faults) s->g_promo_refused = false;  // a refused promotion may be tried again
+        // the options that choose the grouped schedule also end a set's promotion and its
+        // history (any other leaves them: they describe the key stream, not the tables)
+        if (!faults && (r->f.i == &gvopt::Options::kg || r->f.b == &gvopt::Options::k6 ||
+                        r->f.b == &gvopt::Options::gfull || r->f.b == &gvopt::Options::group_reuse ||
+                        r->f.i == &gvopt::Options::group_promote)) {
+          s->g_promoted = false;
+          s->g_hist = 0;
+        }
+      }
   gvopt::opt_store(ctx->opt, *r, val);
   if (r->fx == gvopt::FX_POOLS)
     for (Dev* d : ctx->devs) {

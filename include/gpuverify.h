@@ -396,6 +396,25 @@ int gv_ed_keys_wide_point(gv_ctx* ctx, size_t n, const uint32_t* slots, uint32_t
  * and the batch builds all its keys; any option that drains the pipeline
  * starts every cache cold; 0: every batch rebuilds every key, no k_group_*
  * kernel runs; same verdicts; default 1, env GV_GROUP_REUSE),
+ * "group_promote" (0, 6, 7 or 9: a scratch set whose keys recur moves its
+ * cache from k4's four groups per key to the kg layout of this many -- the
+ * layouts of "kg", a dearer build per key and a ladder of 20 / 15 / 10
+ * doublings instead of 30, k_ecmult_kn<5, NG>.  A set promotes on a batch of
+ * at least "group_promote_min" items (default 262144; not quiescing) whose
+ * lookup, like those of the set's two calls before it, missed fewer keys per
+ * item than half the measured break-even: it flushes and rebuilds that
+ * batch's keys once in the kg layout.  It goes back to k4's layout, the same
+ * way, on a batch whose lookup misses more than the break-even.  The first
+ * promotion allocates the larger arena within "hbm_budget_mb" -- refused:
+ * the set stays on k4, no error, no retry until a quiescing option -- and
+ * later promotions and demotions neither free nor allocate.  The flag
+ * outlives whatever drops the cache (a promoted set rebuilds cold in the kg
+ * layout); "kg", "k6", "gfull", "group_reuse" and the option itself clear
+ * it.  Inert while "kg" or "k6" names a layout or "group_reuse" is 0; same
+ * verdicts; 0 = never; default 9, env GV_GROUP_PROMOTE; quiescing).  A set's
+ * first arena, allocated for a batch that could promote it, is sized for the
+ * promoted layout when the budget holds it, so that a promotion allocates
+ * nothing,
  * "ed_group" (0/1: ed25519 throughput batches -- gv_verify_ed25519_msgs and
  * the device-resident variant -- of at least "ed_group_min" items (default
  * 196608; host chunks of 262,144 qualify) with at most items / 16 (and 16384) distinct keys build each key's
@@ -556,7 +575,13 @@ int gv_set_option(gv_ctx* ctx, const char* key, long long val);
  * "group_reuse_reset" (caches flushed: full, or holding another schedule's
  * tables), "group_reuse_launches" (k_group_* launches since gv_open: 0 while
  * the option has never been on) and "group_reuse_rows" (the row capacity of
- * the first device's first scratch set's grouping arena; 0: none yet).
+ * the first device's first scratch set's grouping arena; 0: none yet),
+ * "group_promote" and "group_promote_min" with (read only) "group_layout"
+ * (groups per key of the tables the first device's last grouped call ran on:
+ * 4 for k4's and k6's layouts, the kg layout's NG otherwise; 0: none yet),
+ * "group_promoted" / "group_demoted" (sets moved to the "group_promote"
+ * layout / back to k4's, since gv_open) and "hbm_optional_bytes" (the bytes
+ * of optional tables "hbm_budget_mb" counts on the first device).
  * GV_EINVAL for any other key.  Instrumentation (bench route
  * attribution). */
 int gv_get_option(gv_ctx* ctx, const char* key, long long* val);
