@@ -467,6 +467,18 @@ hipError_t gvk_keys_build(const uint8_t* pub33, uint32_t n, uint32_t C, uint32_t
                           uint32_t* kok, uint32_t* kqt2, uint32_t* kzq2, hipStream_t st);
 hipError_t gvk_keys_point(uint32_t n, const uint32_t* slots, const uint32_t* kqt, const uint32_t* kzq, uint32_t kC,
                           const uint32_t* kok, uint32_t kcount, uint8_t* out_xy, uint8_t* out_ok, hipStream_t st);
+// Read table entries back (k_keys_entry, one lane per item; tests, tools):
+// entry js[i] (1..nt) of group groups[i] (< ng) of slot slots[i] of a key
+// arena in any layout -- nt entries of ew words (GV_QENT_WORDS or
+// GV_KW_ENT_WORDS) per group table, group 0 in kqt, groups 1.. in kqt2, the
+// shared Z in kzq (8 rows of stride kC) -- as affine x || y (64 bytes,
+// big-endian) with the slot's verdict; zeros and 0 for a slot >= kcount, a
+// rejected key, a group or an entry outside the layout.  Device pointers all;
+// reads the arena only.
+hipError_t gvk_keys_entry(uint32_t n, const uint32_t* slots, const uint32_t* groups, const uint32_t* js,
+                          const uint32_t* kqt, const uint32_t* kqt2, const uint32_t* kzq, uint32_t kC,
+                          const uint32_t* kok, uint32_t kcount, uint32_t nt, uint32_t ew, uint32_t ng, uint8_t* out_xy,
+                          uint8_t* out_ok, hipStream_t st);
 // The resident arena's pubkey index (gv_kidx.hip; gv_kidx.h: GV_KIDX_ROW words
 // per key row, a table of tslots words, a power of two, GV_KIDX_EMPTY or a
 // slot).  Keys and slots as the key-table builds take them: n keys for slots

@@ -1488,6 +1488,59 @@ __global__ __launch_bounds__(256) void k_keys_point(u32 n, const u32* slots, con
   out_ok[g] = kok[sl] ? 1 : 0;
 }
 
+// ------------------------------------------------------------ k_keys_entry
+// Key-table readback (gv_keys_entry, gv_group_entry), one lane per item: entry
+// js[g] (1..NT) of group groups[g] of slot slots[g] in a key arena of any
+// layout -- NT entries of EW words per group table (EW 20: raw 29-bit limbs,
+// load_qent29's order; EW 16: canonical words), NG groups per key, group 0 in
+// row slot of kqt, group k > 0 in row slot (NG - 1) + k - 1 of kqt2 (the
+// addresses k_ecmult_kn forms), the key's shared Z in kzq (8 rows of stride
+// kC) -- as the affine point x = X / Z^2, y = Y / Z^3, 64 bytes x || y
+// big-endian, with the slot's ParsePubKey verdict.  Zeros and 0 for a slot at
+// or past kcount, a rejected key, or a group / entry outside the layout (the
+// callers refuse those first).  Reads the arena only.
+__global__ __launch_bounds__(256) void k_keys_entry(u32 n, const u32* slots, const u32* groups, const u32* js,
+                                                     const u32* kqt, const u32* kqt2, const u32* kzq, u32 kC,
+                                                     const u32* kok, u32 kcount, u32 NT, u32 EW, u32 NG,
+                                                     uint8_t* out_xy, uint8_t* out_ok) {
+  const u32 g = blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= n) return;
+  const u32 sl = slots[g], grp = groups[g], j = js[g];
+  uint8_t* o = out_xy + (size_t)g * 64;
+  if (sl >= kcount || grp >= NG || j < 1u || j > NT || !kok[sl]) {
+    for (int i = 0; i < 64; ++i) o[i] = 0;
+    out_ok[g] = 0;
+    return;
+  }
+  const u32* tab = grp == 0u ? kqt : kqt2;
+  const size_t row = grp == 0u ? (size_t)sl : (size_t)sl * (NG - 1u) + (grp - 1u);
+  const u32* p = tab + (row * NT + (j - 1u)) * EW;
+  fe29 x, y, z, zi, z2, z3;
+  if (EW == 16u) {
+    u32 xw[8], yw[8];
+    for (int i = 0; i < 8; ++i) { xw[i] = p[i]; yw[i] = p[8 + i]; }
+    f29_from_words(x, xw);
+    f29_from_words(y, yw);
+  } else {
+    for (int i = 0; i < 9; ++i) { x.n[i] = p[i]; y.n[i] = p[9 + i]; }
+  }
+  load_f29(z, kzq, kC, sl);
+  f29_inv(zi, z);
+  f29_sqr(z2, zi);
+  f29_mul(z3, z2, zi);
+  f29_mul(x, x, z2);
+  f29_mul(y, y, z3);
+  u32 wx[8], wy[8];
+  f29_to_words(wx, x);
+  f29_to_words(wy, y);
+  for (int i = 0; i < 8; ++i)
+    for (int b = 0; b < 4; ++b) {
+      o[4 * (7 - i) + b] = (uint8_t)(wx[i] >> (24 - 8 * b));
+      o[32 + 4 * (7 - i) + b] = (uint8_t)(wy[i] >> (24 - 8 * b));
+    }
+  out_ok[g] = 1;
+}
+
 // ------------------------------------------------------------------ k_ecmult
 // acc <- acc + (x, y) where (x, y) is affine on the accumulator's curve
 // (zinv == nullptr: Q-table entry) or an affine point of the real curve to be
@@ -2528,6 +2581,16 @@ hipError_t gvk_keys_point(uint32_t n, const uint32_t* slots, const uint32_t* kqt
                           const uint32_t* kok, uint32_t kcount, uint8_t* out_xy, uint8_t* out_ok, hipStream_t st) {
   hipLaunchKernelGGL(gv::k_keys_point, dim3((n + 255) / 256), dim3(256), 0, st, n, slots, kqt, kzq, kC, kok, kcount,
                      out_xy, out_ok);
+  return hipGetLastError();
+}
+
+hipError_t gvk_keys_entry(uint32_t n, const uint32_t* slots, const uint32_t* groups, const uint32_t* js,
+                          const uint32_t* kqt, const uint32_t* kqt2, const uint32_t* kzq, uint32_t kC,
+                          const uint32_t* kok, uint32_t kcount, uint32_t nt, uint32_t ew, uint32_t ng, uint8_t* out_xy,
+                          uint8_t* out_ok, hipStream_t st) {
+  if (n == 0) return hipSuccess;
+  hipLaunchKernelGGL(gv::k_keys_entry, dim3((n + 255) / 256), dim3(256), 0, st, n, slots, groups, js, kqt, kqt2, kzq,
+                     kC, kok, kcount, nt, ew, ng, out_xy, out_ok);
   return hipGetLastError();
 }
 

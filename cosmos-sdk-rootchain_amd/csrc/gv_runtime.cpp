@@ -149,6 +149,7 @@ struct Set {
   size_t g_T = 0, g_count = 0;
   bool g_live = false;
   int g_route = -1;
+  int g_lng = 0;                                  // groups per key of the rows at hand (g_ng, or k4's 4 in a g_wide arena)
   uint64_t g_seed = 0;                            // the table's hash seed (ctx->opt.kidx_seed when it was filled)
   // layout promotion (option "group_promote").  g_hist: the
   // set's last two grouped calls on the k4 layout, newest in bit 0 -- set when
@@ -1189,6 +1190,7 @@ int group_keys(gv_ctx* ctx, Dev* d, Set* s, gvk_batch& b, size_t n, hipStream_t 
   if (reuse) {                                  // everything is enqueued: the cache now holds these rows
     s->g_count = base + M;
     s->g_route = route;
+    s->g_lng = ng;
     s->g_seed = seed;
     s->g_live = true;
     ctx->grp_hit += U - M;
@@ -3568,6 +3570,111 @@ int gv_keys_point(gv_ctx* ctx, size_t n, const uint32_t* slots, uint8_t* out_xy6
     rc = GV_EHIP;
   (void)hipFree(buf);
   return rc;
+}
+
+namespace {
+// One key arena as k_keys_entry reads it.
+struct EntryTabs {
+  const uint32_t *kqt, *kqt2, *kzq, *kok;
+  uint32_t kC, kcount, nt, ew, ng;
+};
+// Every group below the layout's NG, every entry in 1..NT.
+bool entry_args_ok(const EntryTabs& t, size_t n, const uint32_t* groups, const uint32_t* js) {
+  for (size_t i = 0; i < n; ++i)
+    if (groups[i] >= t.ng || js[i] < 1 || js[i] > t.nt) return false;
+  return true;
+}
+// The triples up, k_keys_entry, the points and verdicts down; scratch of the
+// call's own (nothing of the context is written).  An arena with no slot to
+// read answers zeros without a launch.
+int entry_read(const EntryTabs& t, hipStream_t st, size_t n, const uint32_t* slots, const uint32_t* groups,
+               const uint32_t* js, uint8_t* out_xy64, uint8_t* out_ok) {
+  if (t.kcount == 0 || !t.kqt || !t.kqt2 || !t.kzq || !t.kok) {
+    memset(out_xy64, 0, n * 64);
+    memset(out_ok, 0, n);
+    return hipStreamSynchronize(st) == hipSuccess ? GV_OK : GV_EHIP;
+  }
+  uint8_t* buf = nullptr;
+  const size_t sb = round_up(n * 4, 256), xb = round_up(n * 64, 256);
+  if (hipMalloc(&buf, 3 * sb + xb + n) != hipSuccess) return GV_ENOMEM;
+  int rc = GV_OK;
+  uint8_t *d_xy = buf + 3 * sb, *d_ok = d_xy + xb;
+  if (hipMemcpyAsync(buf, slots, n * 4, hipMemcpyHostToDevice, st) != hipSuccess ||
+      hipMemcpyAsync(buf + sb, groups, n * 4, hipMemcpyHostToDevice, st) != hipSuccess ||
+      hipMemcpyAsync(buf + 2 * sb, js, n * 4, hipMemcpyHostToDevice, st) != hipSuccess ||
+      gvk_keys_entry((uint32_t)n, (const uint32_t*)buf, (const uint32_t*)(buf + sb), (const uint32_t*)(buf + 2 * sb),
+                     t.kqt, t.kqt2, t.kzq, t.kC, t.kok, t.kcount, t.nt, t.ew, t.ng, d_xy, d_ok, st) != hipSuccess ||
+      hipMemcpyAsync(out_xy64, d_xy, n * 64, hipMemcpyDeviceToHost, st) != hipSuccess ||
+      hipMemcpyAsync(out_ok, d_ok, n, hipMemcpyDeviceToHost, st) != hipSuccess ||
+      hipStreamSynchronize(st) != hipSuccess)
+    rc = GV_EHIP;
+  (void)hipFree(buf);
+  return rc;
+}
+}  // namespace
+
+int gv_keys_entry(gv_ctx* ctx, int dev_slot, int tabs, size_t n, const uint32_t* slots, const uint32_t* groups,
+                  const uint32_t* js, uint8_t* out_xy64, uint8_t* out_ok) {
+  if (!ctx || dev_slot < 0 || dev_slot >= (int)ctx->devs.size() || tabs < 0 || tabs > 2) return GV_EINVAL;
+  if (n == 0) return GV_OK;
+  if (!slots || !groups || !js || !out_xy64 || !out_ok || n > kMaxItems) return GV_EINVAL;
+  Dev* d = ctx->devs[dev_slot];
+  std::lock_guard<std::mutex> lk(d->mu);
+  EntryTabs t;
+  const size_t keys = ctx->keys;
+  if (tabs == 0) {
+    t = {d->kqt, d->kqt2, d->kzq, d->kok, (uint32_t)d->kcap, (uint32_t)std::min(keys, d->kcap), GV_QTAB_N,
+         GV_QENT_WORDS, GV_LGRP};
+  } else if (tabs == 1) {
+    if (!d->kqt6) return GV_EINVAL;
+    t = {d->kqt6, d->kqt62, d->kzq6, d->kok, (uint32_t)d->kcap, (uint32_t)std::min({keys, d->keys6, d->kcap}),
+         GV_K6_NT, GV_QENT_WORDS, GV_KN_ARENA_NG};
+  } else {
+    if (!d->kqtw || !d->kw_ng || !d->kw_qw) return GV_EINVAL;
+    t = {d->kqtw, d->kqtw2, d->kzqw, d->kok, (uint32_t)d->kcapw, (uint32_t)std::min({keys, d->keysw, d->kcapw}),
+         (uint32_t)gvk_kw_nt(d->kw_qw), GV_KW_ENT_WORDS, (uint32_t)d->kw_ng};
+  }
+  if (!entry_args_ok(t, n, groups, js)) return GV_EINVAL;
+  CK(hipSetDevice(d->id));
+  return entry_read(t, d->set[0].st, n, slots, groups, js, out_xy64, out_ok);
+}
+
+int gv_group_entry(gv_ctx* ctx, int dev_slot, int set, size_t n, const uint32_t* rows, const uint32_t* groups,
+                   const uint32_t* js, uint8_t* out_key33, uint8_t* out_xy64, uint8_t* out_ok) {
+  if (!ctx || dev_slot < 0 || dev_slot >= (int)ctx->devs.size() || set < 0 || set > 3) return GV_EINVAL;
+  if (n == 0) return GV_OK;
+  if (!rows || !groups || !js || !out_key33 || !out_xy64 || !out_ok || n > kMaxItems) return GV_EINVAL;
+  Dev* d = ctx->devs[dev_slot];
+  std::lock_guard<std::mutex> lk(d->mu);
+  const Set* s = set < 2 ? &d->set[set] : &d->gset[set - 2];
+  if (!s->g_live || !s->g_kqt || !s->g_rows || s->g_ent <= 0 || s->g_lng < 2 || s->g_lng > s->g_ng) return GV_EINVAL;
+  const size_t count = std::min(s->g_count, s->gcap);
+  const EntryTabs t = {s->g_kqt, s->g_kqt2, s->g_kzq, s->g_kok, (uint32_t)s->gcap, (uint32_t)count,
+                       (uint32_t)(s->g_ent / GV_QENT_WORDS), GV_QENT_WORDS, (uint32_t)s->g_lng};
+  if (!entry_args_ok(t, n, groups, js)) return GV_EINVAL;
+  CK(hipSetDevice(d->id));
+  // after the set's last work (an asynchronous gv_dev_verify_* call) and the
+  // table build on its side stream
+  hipStream_t st = d->set[0].st;
+  if (s->last && s->last_st && s->last_st != st) CK(hipStreamWaitEvent(st, s->last, 0));
+  if (s->keys_done) CK(hipStreamWaitEvent(st, s->keys_done, 0));
+  std::vector<uint32_t> krows(count * GV_KIDX_ROW);
+  if (count) CK(hipMemcpyAsync(krows.data(), s->g_rows, count * GV_KIDX_ROW * 4, hipMemcpyDeviceToHost, st));
+  std::vector<uint8_t> xy(n * 64), ok(n);
+  const int rc = entry_read(t, st, n, rows, groups, js, xy.data(), ok.data());   // (synchronizes st)
+  if (rc) return rc;
+  memcpy(out_xy64, xy.data(), n * 64);
+  memcpy(out_ok, ok.data(), n);
+  for (size_t i = 0; i < n; ++i) {
+    uint8_t* p = out_key33 + i * 33;
+    memset(p, 0, 33);
+    if (rows[i] >= count) continue;
+    const uint32_t* r = &krows[(size_t)rows[i] * GV_KIDX_ROW];
+    p[0] = (uint8_t)r[0];
+    for (int w = 0; w < 8; ++w)
+      for (int b = 0; b < 4; ++b) p[1 + 4 * (7 - w) + b] = (uint8_t)(r[1 + w] >> (24 - 8 * b));
+  }
+  return GV_OK;
 }
 
 int gv_keys_find(gv_ctx* ctx, size_t n, const uint8_t* pub33, uint32_t* slot_out) {

@@ -48,7 +48,7 @@ EXPORTED_SYMBOLS = (
     "gv_ed_keys_load", "gv_ed_keys_reset", "gv_ed_keys_count", "gv_ed_keys_generation", "gv_verify_ed25519_msgs_keyed",
     "gv_ed_keys_replace", "gv_ed_keys_point", "gv_dev_verify_ed25519_msgs_keyed", "gv_ed_keys_wide_point",
     "gv_submit_digests", "gv_submit_digests_keyed", "gv_submit_msgs", "gv_submit_msgs_keyed", "gv_wait",
-    "gv_keys_find", "gv_dev_keys_find", "gv_debug_sl_op",
+    "gv_keys_find", "gv_dev_keys_find", "gv_debug_sl_op", "gv_keys_entry", "gv_group_entry",
 )
 
 # gv_debug_sl_op (csrc/gv_kernels.h): words per item, flags, status words, op codes
@@ -181,6 +181,12 @@ def load(path: str = LIB_PATH):
     L.gv_keys_point.restype = i32
     L.gv_keys_replace.argtypes = [vp, sz, vp, vp]
     L.gv_keys_replace.restype = i32
+    # (as the pubkey index below: a library from before the entry readback lacks them)
+    for name, args in (("gv_keys_entry", [vp, i32, i32, sz, vp, vp, vp, vp, vp]),
+                       ("gv_group_entry", [vp, i32, i32, sz, vp, vp, vp, vp, vp, vp])):
+        if hasattr(L, name):
+            getattr(L, name).argtypes = args
+            getattr(L, name).restype = i32
     # (a library from before the pubkey index, loaded through GV_LIB for an A/B
     # run, lacks these two: the wrappers then raise AttributeError when called)
     for name, args in (("gv_keys_find", [vp, sz, vp, vp]), ("gv_dev_keys_find", [vp, i32, sz, vp, vp, vp])):
@@ -391,6 +397,54 @@ class Verifier:
         if n:
             _check(self._L.gv_keys_point(self._ctx, n, _ptr(slots), _ptr(xy), _ptr(ok)), "gv_keys_point")
         return xy, ok
+
+    @staticmethod
+    def _entry_triples(what: str, slots, groups, js):
+        """The (slot, group, j) triples of an entry readback as three equal-length 1-d u32 arrays."""
+        out = []
+        for name, a in (("slots", slots), ("groups", groups), ("js", js)):
+            a = np.asarray(a)
+            if a.ndim != 1 or a.dtype.kind not in "ui" or (a.size and (a.min() < 0 or a.max() >= 2 ** 32)):
+                raise ValueError(f"{what}: {name} must be a 1-d array of u32")
+            out.append(a)
+        if not out[0].shape == out[1].shape == out[2].shape:
+            raise ValueError(f"{what}: {out[0].shape[0]} slots, {out[1].shape[0]} groups, {out[2].shape[0]} entries")
+        return [np.ascontiguousarray(a, dtype=np.uint32) for a in out]
+
+    def keys_entry(self, tabs: int, slots, groups, js, dev_slot: int = 0):
+        """Key-table readback (gv_keys_entry): for each triple (slots[i], groups[i], js[i]) the affine
+        point (n x 64 bytes x||y) entry js[i] of group groups[i] of the slot's table holds, and the
+        slot's ParsePubKey verdict.  tabs: 0 the k4 tables, 1 the kn tables, 2 the wide tables in the
+        arena's layout ("kw_arena_qw" / "kw_arena_ng"); dev_slot: whose arena."""
+        for name, a in (("tabs", tabs), ("dev_slot", dev_slot)):
+            if isinstance(a, bool) or not isinstance(a, (int, np.integer)):
+                raise ValueError(f"keys_entry: {name} must be an integer")
+        slots, groups, js = self._entry_triples("keys_entry", slots, groups, js)
+        n = slots.shape[0]
+        xy = np.zeros((n, 64), dtype=np.uint8)
+        ok = np.zeros(n, dtype=np.uint8)
+        if n:
+            _check(self._L.gv_keys_entry(self._ctx, int(dev_slot), int(tabs), n, _ptr(slots), _ptr(groups), _ptr(js),
+                                         _ptr(xy), _ptr(ok)), "gv_keys_entry")
+        return xy, ok
+
+    def group_entry(self, set_index: int, rows, groups, js, dev_slot: int = 0):
+        """Grouped-set readback (gv_group_entry): for each triple (rows[i], groups[i], js[i]) of the
+        key tables scratch set set_index keeps across calls (0 / 1: device-resident calls, 2 / 3:
+        host slices) the 33 key bytes the row was built from (n x 33), the entry's affine point
+        (n x 64) and the key's ParsePubKey verdict."""
+        for name, a in (("set_index", set_index), ("dev_slot", dev_slot)):
+            if isinstance(a, bool) or not isinstance(a, (int, np.integer)):
+                raise ValueError(f"group_entry: {name} must be an integer")
+        rows, groups, js = self._entry_triples("group_entry", rows, groups, js)
+        n = rows.shape[0]
+        key = np.zeros((n, 33), dtype=np.uint8)
+        xy = np.zeros((n, 64), dtype=np.uint8)
+        ok = np.zeros(n, dtype=np.uint8)
+        if n:
+            _check(self._L.gv_group_entry(self._ctx, int(dev_slot), int(set_index), n, _ptr(rows), _ptr(groups),
+                                          _ptr(js), _ptr(key), _ptr(xy), _ptr(ok)), "gv_group_entry")
+        return key, xy, ok
 
     def keys_replace(self, slots: np.ndarray, pub33: np.ndarray):
         """Rebuild loaded slots in place: slot slots[i] then holds key pub33[i] as if it had been

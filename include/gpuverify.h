@@ -180,6 +180,43 @@ uint64_t gv_keys_generation(const gv_ctx* ctx);
  * and out_ok[i] = its ParsePubKey verdict (a slot >= gv_keys_count(): zeros
  * and 0).  Reads the first device's arena. */
 int gv_keys_point(gv_ctx* ctx, size_t n, const uint32_t* slots, uint8_t* out_xy64, uint8_t* out_ok);
+/* Key-table readback (tests, tools): every entry of every table set of the
+ * resident arena of device dev_slot.  tabs picks the set: 0 the k4 / keyed
+ * latency tables (5-bit windows: 4 groups of 16 entries, every loaded slot),
+ * 1 the kn tables ("keys_k6": 6-bit windows, 11 groups of 32 entries), 2 the
+ * wide tables in the arena's layout ("kw_arena_qw" = QW 11 or 9 bits,
+ * "kw_arena_ng" groups of 2^(QW-1) entries).  Item i names slot slots[i],
+ * group groups[i] < NG and entry js[i] in 1..NT = 2^(QW-1); out_xy64 + 64*i
+ * = x || y (32 bytes each, big-endian) of the affine point the table holds
+ * there, which is js[i] * 2^(QW * w0(groups[i])) * Q for the slot's key Q
+ * -- group k starts at window w0(k) = k P - max(0, k - R), P = ceil(QWIN /
+ * NG), R = QWIN - (P - 1) NG, QWIN = 26 / 22 / 12 / 15 windows per 128-bit
+ * half for QW = 5 / 6 / 11 / 9 -- and out_ok[i] = the slot's ParsePubKey
+ * verdict.  A slot at or past the slots that have the table set (at most
+ * gv_keys_count()): zeros and 0; a rejected key: zeros and 0.
+ * GV_EINVAL, and the outputs untouched, for a NULL ctx (or pointer with n >
+ * 0), a bad dev_slot, a tabs the context holds no tables of (no kn or wide
+ * arena), any groups[i] >= NG or js[i] outside 1..NT; n == 0 is GV_OK.  Reads
+ * only: nothing is allocated in an arena, no counter or option moves; under
+ * gv_keys_point's locks. */
+int gv_keys_entry(gv_ctx* ctx, int dev_slot, int tabs, size_t n, const uint32_t* slots, const uint32_t* groups,
+                  const uint32_t* js, uint8_t* out_xy64, uint8_t* out_ok);
+/* Grouped-set readback (tests, tools): the key tables a scratch set of device
+ * dev_slot keeps across calls (option "group_reuse"): set 0 / 1 the sets of
+ * the device-resident calls, 2 / 3 those of the host slices.  Item i names
+ * cache row rows[i], group groups[i] and entry js[i] in the layout of the
+ * set's last grouped call ("group_layout" groups; 16 entries of 5-bit
+ * windows, or with "k6" 4 groups of 32 entries of 6-bit windows; w0 as for
+ * gv_keys_entry); out_key33 + 33*i = the 33 key bytes the row was built
+ * from, as sent, out_xy64 / out_ok as gv_keys_entry's.  A row at or past the
+ * rows in use: zeros and 0 in all three; a rejected key: its bytes, zeros
+ * and 0.  Waits for the set's last call, so it may follow an asynchronous
+ * gv_dev_verify_*.  GV_EINVAL, and the outputs untouched, for a NULL ctx (or
+ * pointer with n > 0), a bad dev_slot or set, a set that holds no live cache
+ * (never used, dropped, "group_reuse" 0), a group or entry outside the
+ * layout; n == 0 is GV_OK.  Reads only, as gv_keys_entry. */
+int gv_group_entry(gv_ctx* ctx, int dev_slot, int set, size_t n, const uint32_t* rows, const uint32_t* groups,
+                   const uint32_t* js, uint8_t* out_key33, uint8_t* out_xy64, uint8_t* out_ok);
 
 /* The arena's pubkey index (option "keys_index", below): which slot holds a
  * key.  With the option on, gv_keys_load and gv_keys_replace keep on every
