@@ -40,6 +40,7 @@
 #include "../../include/gpuverify.h"
 #include "gv_kernels.h"
 #include "gv_kidx.h"
+#include "gv_keytabs.h"
 #include "gv_options.h"
 #include "gv_stage.h"
 #include "gv_async.h"
@@ -108,6 +109,90 @@ using gvstage::par_copy_segs;
 using gvstage::run_sliced;
 
 
+// ------------------------------------------------------------ key table sets
+// Layouts, bytes, the growth rule, the promotion arithmetic: gv_keytabs.h
+using namespace gvkt;
+
+// One secp256k1 key table set on the device, in the layout lay: per slot the
+// group-0 table (qt) on the Z in zq (8 rows of stride cap), the tables of
+// groups 1.. (qt2: lay.ng - 1 rows per slot) and the chain's parked Zs (zq2:
+// (lay.ng - 1) x 8 rows of stride cap); ok: the verdict row of a set that owns
+// one (the resident kn and wide sets share k4's).  Plain data: copied by
+// assignment, freed by hand.  lay outlives free() (the wide arena's choice).
+struct KeyTabs {
+  uint32_t *qt = nullptr, *zq = nullptr, *ok = nullptr, *qt2 = nullptr, *zq2 = nullptr;
+  size_t cap = 0;
+  TabLayout lay;
+
+  void free() {
+    for (uint32_t** p : {&qt, &zq, &ok, &qt2, &zq2})
+      if (*p) { (void)hipFree(*p); *p = nullptr; }
+    cap = 0;
+  }
+  // An empty set becomes c slots of layout l; all or nothing.
+  bool alloc(const TabLayout& l, size_t c, bool with_ok) {
+    const size_t tb = l.table_words() * 4, g1 = (size_t)l.ng - 1;
+    lay = l;
+    if (hipMalloc(&qt, c * tb) != hipSuccess || hipMalloc(&zq, c * 8 * 4) != hipSuccess ||
+        (with_ok && hipMalloc(&ok, c * 4) != hipSuccess) || hipMalloc(&qt2, c * g1 * tb) != hipSuccess ||
+        hipMalloc(&zq2, c * g1 * 8 * 4) != hipSuccess) {
+      free();
+      (void)hipGetLastError();
+      return false;
+    }
+    cap = c;
+    return true;
+  }
+  // The first `used` slots of o (the same layout, any capacity) into this set
+  // on st: the Z rows move from stride o.cap to stride cap.
+  bool copy_from(const KeyTabs& o, size_t used, hipStream_t st) {
+    const size_t tb = lay.table_words() * 4, g1 = (size_t)lay.ng - 1;
+    bool good = hipMemcpyAsync(qt, o.qt, used * tb, hipMemcpyDeviceToDevice, st) == hipSuccess &&
+                hipMemcpyAsync(qt2, o.qt2, used * g1 * tb, hipMemcpyDeviceToDevice, st) == hipSuccess;
+    for (size_t r = 0; good && r < 8; ++r)
+      good = hipMemcpyAsync(zq + r * cap, o.zq + r * o.cap, used * 4, hipMemcpyDeviceToDevice, st) == hipSuccess;
+    for (size_t r = 0; good && r < g1 * 8; ++r)
+      good = hipMemcpyAsync(zq2 + r * cap, o.zq2 + r * o.cap, used * 4, hipMemcpyDeviceToDevice, st) == hipSuccess;
+    if (good && ok) good = hipMemcpyAsync(ok, o.ok, used * 4, hipMemcpyDeviceToDevice, st) == hipSuccess;
+    return good;
+  }
+};
+
+// A table set as a launch or a readback takes it: the resident arena's k4, kn
+// or wide tables (arena_tabs) or a set's grouped keys (group_keys), with the
+// selectors the kernels want (gvk_batch k6 / kqw / kwq, gvk_lat kn) and the
+// G tables of its ladder.  The launch stream waits on `ready` first.
+enum { kTabsK4 = 0, kTabsKn = 1, kTabsWide = 2 };   // gvk_lat's kn values
+struct KeyView {
+  const uint32_t *kqt = nullptr, *kzq = nullptr, *kok = nullptr, *kqt2 = nullptr, *kzq2 = nullptr;
+  uint32_t kC = 0, kcount = 0;
+  TabLayout lay;
+  int k6 = 0, kqw = 0, kwq = 0, kn = kTabsK4;
+  const uint32_t *gtab4 = nullptr, *gtab6 = nullptr;
+  hipEvent_t ready = nullptr;
+
+  KeyView() = default;
+  // count slots of t; ok: the verdict row of a set that owns none
+  KeyView(const KeyTabs& t, size_t count, const uint32_t* ok = nullptr)
+      : kqt(t.qt), kzq(t.zq), kok(t.ok ? t.ok : ok), kqt2(t.qt2), kzq2(t.zq2), kC((uint32_t)t.cap),
+        kcount((uint32_t)count), lay(t.lay) {}
+  void to_batch(gvk_batch& b, const uint32_t* kslot) const {
+    b.pub33 = nullptr;
+    b.kslot = kslot; b.kqt = kqt; b.kzq = kzq; b.kok = kok;
+    b.kC = kC; b.kcount = kcount;
+    b.kqt2 = kqt2; b.gtab4 = gtab4;               // null gtab4: the 125-doubling keyed ladder
+    b.k6 = k6; b.kqw = kqw; b.kwq = kwq; b.gtab6 = gtab6;
+    b.keys_ready = ready;
+  }
+  // (k_verify_lat16_kn / _kw read no parked Zs; the k4 kernels no gtab6)
+  void to_lat(gvk_lat& lb, const uint32_t* kslot) const {
+    lb.pub33 = nullptr;
+    lb.kslot = kslot; lb.kqt = kqt; lb.kzq = kzq; lb.kok = kok; lb.kC = kC; lb.kcount = kcount;
+    lb.kqt2 = kqt2; lb.kzq2 = kn ? nullptr : kzq2;
+    if (kn) { lb.gtab6 = gtab6; lb.kn = kn; }
+  }
+};
+
 // ------------------------------------------------------------ device state
 // Device scratch of one batch chunk of C lanes (C % 256 == 0): the staged
 // inputs (one contiguous region so a host chunk is ONE H2D copy), the SoA
@@ -134,22 +219,20 @@ struct Set {
   hipEvent_t fork = nullptr, keys_done = nullptr;
   hipEvent_t grp_ready = nullptr;                 // slice grouping on this set: the keys' tables are built
   // in-batch key grouping: the per-batch key arena (tables of the batch's
-  // distinct keys, key-arena layout) for up to gcap keys, and the count
-  uint32_t *g_kqt = nullptr, *g_kzq = nullptr, *g_kok = nullptr, *g_kqt2 = nullptr, *g_kzq2 = nullptr;
-  size_t gcap = 0;
-  int g_ent = 0, g_ng = 0;                        // the arena's layout: words per group table, groups per key
+  // distinct keys with their verdicts, for up to gk.cap keys in the layout gk.lay)
+  KeyTabs gk;
   // the arena as a cache of key tables (option "group_reuse"; DESIGN section
   // 4.1k): rows [0, g_count) hold the tables of the keys whose raw rows
   // (GV_KIDX_ROW words, gv_kidx.h) are in g_rows, g_idx the open-addressing
   // table over them (g_T words, one block with g_rows).  g_live: the rows, the
   // table and g_count describe what the arena holds; g_route: the schedule the
-  // tables were built for (GV_ROUTE_*) -- with g_ent, g_ng and the allocation
+  // tables were built for (GV_ROUTE_*) -- with gk's layout and the allocation
   // (ensure_group_arena clears g_live) the cache's validity tag
   uint32_t *g_rows = nullptr, *g_idx = nullptr;
   size_t g_T = 0, g_count = 0;
   bool g_live = false;
   int g_route = -1;
-  int g_lng = 0;                                  // groups per key of the rows at hand (g_ng, or k4's 4 in a g_wide arena)
+  int g_lng = 0;                                  // groups per key of the rows at hand (gk.lay.ng, or k4's 4 in a g_wide arena)
   uint64_t g_seed = 0;                            // the table's hash seed (ctx->opt.kidx_seed when it was filled)
   // layout promotion (option "group_promote").  g_hist: the
   // set's last two grouped calls on the k4 layout, newest in bit 0 -- set when
@@ -200,9 +283,9 @@ struct Dev {
                                                   // async lane alternates the two (a slice's grouping under the
                                                   // previous slice's chunks)
   hipEvent_t last_h2d = nullptr;                  // host slice: the previous chunk's H2D (h2d_serial)
-  // key arena (gv_keys_load): Q table rows, table Z (8 rows of stride kcap), verdicts
-  uint32_t *kqt = nullptr, *kzq = nullptr, *kok = nullptr;
-  uint32_t *kqt2 = nullptr, *kzq2 = nullptr;      // the keyed latency schedule's group tables (2^35 Q, ...)
+  // key arena (gv_keys_load): the k4 table set (Q's table and the group tables
+  // of 2^35 Q, 2^70 Q, 2^100 Q) and the verdicts of every slot
+  KeyTabs k4;
   uint32_t* glat = nullptr;                       // group tables of G / lambda G (k_gen_glat)
   uint32_t* gtab4 = nullptr;                      // k_ecmult_k4's tables of 2^35 G, 2^70 G, 2^100 G (+ lambda)
   uint32_t* gtab6 = nullptr;                      // k_ecmult_k6's full-scalar 24-bit-window tables of 2^(36 t) G (3.5 GiB)
@@ -210,31 +293,22 @@ struct Dev {
   uint32_t* gtabf = nullptr;                      // k_ecmult_k4<true>'s full-scalar G tables (GV_GF_WORDS, 6 GiB)
   bool gtabf_failed = false;                      // its allocation failed once: k4 keeps the GLV G tables
   bool gtab4_failed = false;                      // gtab4's allocation failed: keyed batches on the 125-doubling ladder
-  size_t kcap = 0;
-  // the resident kn arena (option "keys_k6"): per slot the GV_KN_ARENA_NG (11)
-  // 32-entry group tables of 2^(12 g) Q on one Z (kqt6: group 0, kqt62: groups
-  // 1.., kzq6: the Z, 8 rows of stride kcap; kzq62 holds the chain's parked
-  // Zs), read by k_ecmult_kn and k_verify_lat16_kn
-  uint32_t *kqt6 = nullptr, *kzq6 = nullptr, *kqt62 = nullptr, *kzq62 = nullptr;
+  // the resident kn set (option "keys_k6"; lay_kn: 11 32-entry group tables of
+  // 2^(12 g) Q), at k4's capacity, read by k_ecmult_kn and k_verify_lat16_kn
+  KeyTabs kn;
   size_t keys6 = 0;                               // leading slots whose k6 tables are built
-  // the resident arena's wide-window tables (option "keys_wide"): per slot
-  // kw_ng group tables of 2^(kw_qw - 1) entries on one Z -- kw_qw = GV_KW_QW
-  // (11: 1,024 entries; kw_ng = GV_KW_NG1 = 12: one window per group, or
-  // GV_KW_NG2 = 6: two) or GV_KWN_QW (9: 256 entries; GV_KWN_NG1 = 15 or
-  // GV_KWN_NG2 = 8; gv_kernels.h), the layout gv_keys_load picked (kWideLayouts)
-  // -- kqtw: group 0, kqtw2: groups 1.., kzqw: the Z, 8 rows of stride kcapw;
-  // kzqw2: the chain's parked Zs, in an arena of their own (capacity kcapw)
-  // grown by doubling while the HBM budget holds it; keysw leading slots
-  // built.  kw_full: the last layout's growth was refused (no more wide-window
-  // builds until gv_keys_reset)
-  uint32_t *kqtw = nullptr, *kzqw = nullptr, *kqtw2 = nullptr, *kzqw2 = nullptr;
-  size_t kcapw = 0, keysw = 0;
-  int kw_ng = 0, kw_qw = 0;
+  // the resident arena's wide-window tables (option "keys_wide"), in an arena
+  // of their own: the layout gv_keys_load picked (kWideLayouts, gv_keytabs.h;
+  // kw.lay.ng 0: none yet), grown by doubling while the HBM budget holds it;
+  // keysw leading slots built.  kw_full: the last layout's growth was refused
+  // (no more wide-window builds until gv_keys_reset)
+  KeyTabs kw;
+  size_t keysw = 0;
   bool kw_full = false;
   // the arena's pubkey index (option "keys_index"; gv_kidx.h): per slot the raw
   // key row (GV_KIDX_ROW words: the prefix and x as k_unpack forms them, the
-  // bytes as loaded -- a rejected key's too), capacity kidx_cap = kcap; the
-  // table of kidx_T words (a power of two >= 2 kcap, >= 512; a slot or
+  // bytes as loaded -- a rejected key's too), capacity kidx_cap = k4.cap; the
+  // table of kidx_T words (a power of two >= 2 k4.cap, >= 512; a slot or
   // GV_KIDX_EMPTY); kidx_keys leading slots have their row and went through
   // k_kidx_put.  kidx_on: the running arena took the option at slot 0.
   // kidx_failed: an allocation was refused or a launch failed (no index until
@@ -380,183 +454,91 @@ int set_release(Set* s, hipStream_t st) {
   return GV_OK;
 }
 
-// Bytes per slot of the resident key arena: the k4 tables (Q table, the three
-// group tables, their Zs, the verdict) and, with the k6 arena, its four
-// 32-entry group tables and Zs.
-size_t key_slot_bytes(bool k6) {
-  size_t b = ((size_t)GV_KEY_WORDS * (1 + GV_KEY2_TABLES) + 8 * (1 + GV_KEY2_TABLES) + 1) * 4;
-  if (k6) b += ((size_t)GV_K6_KEY_WORDS * GV_KN_ARENA_NG + 8 * GV_KN_ARENA_NG) * 4;
-  return b;
-}
-
-// Grow the key arena to hold `need` slots, keeping the first `used` (row
-// stride of the Z rows changes with the capacity).  Doubling, but not past
-// key_cap (the callers' reset point: GV_KEY_CAP or the "key_cap" option) --
-// past it the arena grows to exactly what is needed (a caller that never
-// resets pays one copy per load, not a quadratic series of doublings).
-// k6: the arena also holds the k6 group tables (allocated on the first k6
+// Grow the key arena to hold `need` slots, keeping the first `used` (the
+// growth rule: arena_grow_cap, to key_cap -- GV_KEY_CAP or the "key_cap"
+// option -- by doubling).
+// k6: the arena also holds the kn group tables (allocated on the first k6
 // load; *k6 is cleared when they do not fit the budget, the k4 tables stay).
+// A failed copy leaves the arena as it was.
 int ensure_keys(Dev* d, size_t need, size_t used, hipStream_t st, size_t key_cap, size_t budget, bool* k6) {
-  const bool want6 = k6 && *k6;
-  if (need <= d->kcap && (!want6 || d->kqt6)) return GV_OK;
-  size_t cap = d->kcap;
-  if (need > d->kcap) {
-    const size_t grow = d->kcap >= key_cap ? need : std::min<size_t>(2 * d->kcap, std::max<size_t>(need, key_cap));
-    cap = round_up(std::max<size_t>({need, grow, 4096}), 256);
-  }
-  const bool has6 = d->kqt6 != nullptr;
+  const bool want6 = k6 && *k6, has6 = d->kn.qt != nullptr;
+  if (need <= d->k4.cap && (!want6 || has6)) return GV_OK;
+  const size_t cap = need > d->k4.cap ? arena_grow_cap(d->k4.cap, need, key_cap, 4096) : d->k4.cap;
   bool alloc6 = want6 || has6;
   // budget: the new arena beside the old one during the copy, plus the other
   // optional tables
-  const size_t old_b = d->kcap * key_slot_bytes(has6);
-  const size_t base_b = d->opt_bytes - std::min(d->opt_bytes, old_b);
-  if (base_b + old_b + cap * key_slot_bytes(alloc6) > budget) {
-    if (!alloc6 || has6 || base_b + old_b + cap * key_slot_bytes(false) > budget) return GV_ENOMEM;
+  const size_t old_b = d->k4.cap * resident_slot_bytes(has6);
+  const size_t base_b = budget_replace(d->opt_bytes, old_b, 0);
+  if (base_b + old_b + cap * resident_slot_bytes(alloc6) > budget) {
+    if (!alloc6 || has6 || base_b + old_b + cap * resident_slot_bytes(false) > budget) return GV_ENOMEM;
     alloc6 = false;                             // no room for the k6 tables: k4 only
     *k6 = false;
-    if (need <= d->kcap) return GV_OK;
+    if (need <= d->k4.cap) return GV_OK;
   }
-  uint32_t *qt = nullptr, *zq = nullptr, *ok = nullptr, *qt2 = nullptr, *zq2 = nullptr;
-  uint32_t *qt6 = nullptr, *zq6 = nullptr, *qt62 = nullptr, *zq62 = nullptr;
-  auto fail = [&]() {
-    for (uint32_t* p : {qt, zq, ok, qt2, zq2, qt6, zq6, qt62, zq62}) if (p) (void)hipFree(p);
-    (void)hipGetLastError();
-    return GV_ENOMEM;
-  };
-  if (hipMalloc(&qt, cap * GV_KEY_WORDS * 4) != hipSuccess) return fail();
-  if (hipMalloc(&zq, cap * 8 * 4) != hipSuccess) return fail();
-  if (hipMalloc(&ok, cap * 4) != hipSuccess) return fail();
-  if (hipMalloc(&qt2, cap * GV_KEY2_TABLES * GV_KEY_WORDS * 4) != hipSuccess) return fail();
-  if (hipMalloc(&zq2, cap * GV_KEY2_TABLES * 8 * 4) != hipSuccess) return fail();
-  if (alloc6) {
-    if (hipMalloc(&qt6, cap * GV_K6_KEY_WORDS * 4) != hipSuccess) return fail();
-    if (hipMalloc(&zq6, cap * 8 * 4) != hipSuccess) return fail();
-    if (hipMalloc(&qt62, cap * (GV_KN_ARENA_NG - 1) * GV_K6_KEY_WORDS * 4) != hipSuccess) return fail();
-    if (hipMalloc(&zq62, cap * (GV_KN_ARENA_NG - 1) * 8 * 4) != hipSuccess) return fail();
-  }
+  KeyTabs k4, kn;
+  if (!k4.alloc(lay_k4(), cap, true)) return GV_ENOMEM;
+  if (alloc6 && !kn.alloc(lay_kn(), cap, false)) { k4.free(); return GV_ENOMEM; }
   // the k6 tables of the slots below `used` exist only if the old arena had them
-  const size_t used6 = d->kqt6 ? used : 0;
-  if (used) {
-    CK(hipMemcpyAsync(qt, d->kqt, used * GV_KEY_WORDS * 4, hipMemcpyDeviceToDevice, st));
-    CK(hipMemcpyAsync(qt2, d->kqt2, used * GV_KEY2_TABLES * GV_KEY_WORDS * 4, hipMemcpyDeviceToDevice, st));
-    for (int r = 0; r < 8; ++r)
-      CK(hipMemcpyAsync(zq + r * cap, d->kzq + r * d->kcap, used * 4, hipMemcpyDeviceToDevice, st));
-    for (int r = 0; r < GV_KEY2_TABLES * 8; ++r)
-      CK(hipMemcpyAsync(zq2 + r * cap, d->kzq2 + r * d->kcap, used * 4, hipMemcpyDeviceToDevice, st));
-    CK(hipMemcpyAsync(ok, d->kok, used * 4, hipMemcpyDeviceToDevice, st));
+  if (used && (!k4.copy_from(d->k4, used, st) || (has6 && !kn.copy_from(d->kn, used, st)) ||
+               hipStreamSynchronize(st) != hipSuccess)) {
+    k4.free();
+    kn.free();
+    return GV_EHIP;
   }
-  if (used6 && alloc6) {
-    CK(hipMemcpyAsync(qt6, d->kqt6, used6 * GV_K6_KEY_WORDS * 4, hipMemcpyDeviceToDevice, st));
-    CK(hipMemcpyAsync(qt62, d->kqt62, used6 * (GV_KN_ARENA_NG - 1) * GV_K6_KEY_WORDS * 4, hipMemcpyDeviceToDevice,
-                      st));
-    for (int r = 0; r < 8; ++r)
-      CK(hipMemcpyAsync(zq6 + r * cap, d->kzq6 + r * d->kcap, used6 * 4, hipMemcpyDeviceToDevice, st));
-    for (int r = 0; r < (GV_KN_ARENA_NG - 1) * 8; ++r)
-      CK(hipMemcpyAsync(zq62 + r * cap, d->kzq62 + r * d->kcap, used6 * 4, hipMemcpyDeviceToDevice, st));
-  }
-  if (used) CK(hipStreamSynchronize(st));
-  for (uint32_t* p : {d->kqt, d->kzq, d->kok, d->kqt2, d->kzq2, d->kqt6, d->kzq6, d->kqt62, d->kzq62})
-    if (p) (void)hipFree(p);
-  d->kqt = qt; d->kzq = zq; d->kok = ok; d->kqt2 = qt2; d->kzq2 = zq2;
-  d->kqt6 = qt6; d->kzq6 = zq6; d->kqt62 = qt62; d->kzq62 = zq62;
-  d->kcap = cap;
-  d->opt_bytes = base_b + cap * key_slot_bytes(alloc6);
+  d->k4.free();
+  d->kn.free();
+  d->k4 = k4;
+  d->kn = kn;
+  d->opt_bytes = base_b + cap * resident_slot_bytes(alloc6);
   return GV_OK;
 }
 
-// Bytes per slot of the qw-bit wide-window tables of ng groups.
-inline size_t key_wide_slot_bytes(int qw, int ng) {
-  return qw && ng ? (gvk_kw_key_words(qw) * (size_t)ng + 8 * (size_t)ng) * 4 : 0;
-}
-
-// The wide arena's layouts in order of falling memory per key: 768, 384, 240
-// and 128 KiB of tables at 11 / 9 bits.  gv_keys_load starts an arena at the
-// first one its options allow ("keys_wide" 2: any, 1: two windows per group;
-// "keys_wide_qw": one width only) and moves the whole arena to the next
-// allowed one when ensure_keys_wide refuses a growth.
-struct WideLayout {
-  int qw, ng, wpg;                                // window width, groups, windows per group
-};
-const WideLayout kWideLayouts[] = {{GV_KW_QW, GV_KW_NG1, 1}, {GV_KW_QW, GV_KW_NG2, 2},
-#if GV_KWN
-                                   {GV_KWN_QW, GV_KWN_NG1, 1}, {GV_KWN_QW, GV_KWN_NG2, 2},
-#endif
-};
-constexpr int kWideLayoutCount = (int)(sizeof kWideLayouts / sizeof kWideLayouts[0]);
-// The first layout at or after index `from` of width only_qw (0: any) with at
-// least min_wpg windows per group; kWideLayoutCount when there is none.
-inline int wide_layout_next(int from, int only_qw, int min_wpg) {
-  for (int i = from; i < kWideLayoutCount; ++i)
-    if ((!only_qw || kWideLayouts[i].qw == only_qw) && kWideLayouts[i].wpg >= min_wpg) return i;
-  return kWideLayoutCount;
-}
-
-// Grow the wide-window arena to `need` slots keeping the first `used` (doubling, not
-// past key_cap, then exact -- as ensure_keys).  Returns false when the budget
-// (the new arena beside the old one during the copy) does not hold it, when
-// it would take device memory the k4 / k6 arena needs to grow to key_cap
-// (plus 8 GiB of batch scratch: these tables are an optimisation and never
-// make a later gv_keys_load or batch fail), or when an allocation fails: the
-// arena is left as it was and batches keep the k6 tables.
-// The layout is d->kw_qw / d->kw_ng's; cap1 bounds the capacity of the
-// GV_KW_QW-bit one-window layout (a test hook, option "keys_wide1_cap"),
-// limit the new arena's bytes (option "keys_wide_mb"; 0: none).  ed_room:
-// device memory the ed25519 key arena still needs to reach its own cap
-// (reserved the same way).
-bool ensure_keys_wide(Dev* d, size_t need, size_t used, hipStream_t st, size_t key_cap, size_t budget,
-                      size_t ed_room, size_t limit, size_t cap1 = SIZE_MAX) {
-  if (need <= d->kcapw) return true;
-  const size_t grow = d->kcapw >= key_cap ? need : std::min<size_t>(2 * d->kcapw, std::max<size_t>(need, key_cap));
-  const size_t cap = round_up(std::max<size_t>({need, grow, 4096}), 256);
-  const size_t slot_b = key_wide_slot_bytes(d->kw_qw, d->kw_ng);
-  const size_t kwords = gvk_kw_key_words(d->kw_qw);
-  if (d->kw_qw == GV_KW_QW && d->kw_ng == GV_KW_NG1 && cap > cap1) return false;
+// Grow the wide-window arena (layout d->kw.lay) to `need` slots keeping the
+// first `used`, as ensure_keys.  Returns false when the budget (the new arena
+// beside the old one during the copy) does not hold it, when it would take
+// device memory the k4 / k6 arena needs to grow to key_cap (plus 8 GiB of
+// batch scratch: these tables are an optimisation and never make a later
+// gv_keys_load or batch fail), or when an allocation fails: the arena is left
+// as it was and batches keep the k6 tables.  Option "keys_wide1_cap" (a test
+// hook) bounds the capacity of the GV_KW_QW-bit one-window layout,
+// "keys_wide_mb" the new arena's bytes (0: no bound).  The ed25519 key
+// arena's growth to ed_key_cap is reserved too (72 KB per key).
+bool ensure_keys_wide(const gvopt::Options& opt, Dev* d, size_t need, size_t used, hipStream_t st) {
+  KeyTabs& kw = d->kw;
+  if (need <= kw.cap) return true;
+  const size_t key_cap = opt.key_cap, limit = opt.keys_wide_bytes;
+  const size_t cap = arena_grow_cap(kw.cap, need, key_cap, 4096);
+  const size_t slot_b = slot_bytes(kw.lay);
+  if (kw.lay == lay_wide(GV_KW_QW, GV_KW_NG1) && cap > opt.keys_wide1_cap) return false;
   if (limit && cap * slot_b > limit) return false;
-  if (d->opt_bytes + cap * slot_b > budget) return false;
+  if (d->opt_bytes + cap * slot_b > opt.hbm_budget) return false;
   size_t free_b = 0, total_b = 0;
   if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) return false;
-  const size_t reserve =
-      (key_cap > d->kcap ? key_cap - d->kcap : 0) * key_slot_bytes(true) + ed_room + (size_t(8) << 30);
+  const size_t reserve = (key_cap > d->k4.cap ? key_cap - d->k4.cap : 0) * resident_slot_bytes(true) +
+                         (opt.ed_key_cap > d->ekcap ? opt.ed_key_cap - d->ekcap : 0) *
+                             ((size_t)GV_EDK_WORDS + 8 + 1) * 4 +
+                         (size_t(8) << 30);
   if (free_b < cap * slot_b + reserve) return false;
-  const size_t ng1 = (size_t)d->kw_ng - 1;
-  uint32_t *qt = nullptr, *zq = nullptr, *qt2 = nullptr, *zq2 = nullptr;
-  if (hipMalloc(&qt, cap * kwords * 4) != hipSuccess || hipMalloc(&zq, cap * 8 * 4) != hipSuccess ||
-      hipMalloc(&qt2, cap * ng1 * kwords * 4) != hipSuccess ||
-      hipMalloc(&zq2, cap * ng1 * 8 * 4) != hipSuccess) {
-    for (uint32_t* p : {qt, zq, qt2, zq2}) if (p) (void)hipFree(p);
+  KeyTabs grown;
+  if (!grown.alloc(kw.lay, cap, false)) return false;
+  used = std::min(used, d->keysw);                // the slots whose wide-window tables exist
+  if (used && (!grown.copy_from(kw, used, st) || hipStreamSynchronize(st) != hipSuccess)) {
+    grown.free();
     (void)hipGetLastError();
     return false;
   }
-  used = std::min(used, d->keysw);                // the slots whose wide-window tables exist
-  if (used) {
-    bool ok = hipMemcpyAsync(qt, d->kqtw, used * kwords * 4, hipMemcpyDeviceToDevice, st) == hipSuccess &&
-              hipMemcpyAsync(qt2, d->kqtw2, used * ng1 * kwords * 4, hipMemcpyDeviceToDevice, st) ==
-                  hipSuccess;
-    for (int r = 0; ok && r < 8; ++r)
-      ok = hipMemcpyAsync(zq + r * cap, d->kzqw + r * d->kcapw, used * 4, hipMemcpyDeviceToDevice, st) == hipSuccess;
-    for (size_t r = 0; ok && r < ng1 * 8; ++r)
-      ok = hipMemcpyAsync(zq2 + r * cap, d->kzqw2 + r * d->kcapw, used * 4, hipMemcpyDeviceToDevice, st) ==
-           hipSuccess;
-    if (!ok || hipStreamSynchronize(st) != hipSuccess) {
-      for (uint32_t* p : {qt, zq, qt2, zq2}) (void)hipFree(p);
-      (void)hipGetLastError();
-      return false;
-    }
-  }
-  for (uint32_t* p : {d->kqtw, d->kzqw, d->kqtw2, d->kzqw2})
-    if (p) (void)hipFree(p);
-  d->opt_bytes = d->opt_bytes - std::min(d->opt_bytes, d->kcapw * slot_b) + cap * slot_b;
-  d->kqtw = qt; d->kzqw = zq; d->kqtw2 = qt2; d->kzqw2 = zq2;
-  d->kcapw = cap;
+  d->opt_bytes = budget_replace(d->opt_bytes, kw.cap * slot_b, cap * slot_b);
+  kw.free();
+  kw = grown;
   return true;
 }
 
-// Drop the wide-window arena (its memory back to the device).
-void free_keys_wide(Dev* d) {
-  for (uint32_t** p : {&d->kqtw, &d->kzqw, &d->kqtw2, &d->kzqw2})
-    if (*p) { (void)hipFree(*p); *p = nullptr; }
-  d->opt_bytes -= std::min(d->opt_bytes, d->kcapw * key_wide_slot_bytes(d->kw_qw, d->kw_ng));
-  d->kcapw = d->keysw = 0;
+// Drop the wide-window arena (its memory back to the device); the next one's layout is l.
+void free_keys_wide(Dev* d, const TabLayout& l) {
+  d->opt_bytes = budget_replace(d->opt_bytes, d->kw.cap * slot_bytes(d->kw.lay), 0);
+  d->kw.free();
+  d->kw.lay = l;
+  d->keysw = 0;
 }
 
 // ---- ed25519 scratch
@@ -848,7 +830,7 @@ void opt_free(Dev* d, uint32_t*& p, size_t bytes) {
   if (!p) return;
   (void)hipFree(p);
   p = nullptr;
-  d->opt_bytes -= std::min(d->opt_bytes, bytes);
+  d->opt_bytes = budget_replace(d->opt_bytes, bytes, 0);
 }
 constexpr size_t kGtab4Bytes = (size_t)GV_KEY2_TABLES * 2 * GV_GTAB_N * 16 * 4;
 
@@ -911,161 +893,87 @@ int ensure_gtab6(gv_ctx* ctx, Dev* d, Set* s, hipStream_t st, bool want, bool sy
   return GV_OK;
 }
 
-// The set's per-batch key arena for in-batch grouping (cap keys; k6: 32-entry
-// group tables), charged to the HBM budget like the other optional tables.
-// ent: words per group table (GV_KEY_WORDS: 16 entries; GV_K6_KEY_WORDS: 32),
-// ng: groups per key (4; the kg layouts GV_KG_NGS).
-// ... and, per key, its raw row and its share of the cache's table
-// (kidx_table_words below: a power of two >= 2 cap).
-size_t kidx_table_words(size_t cap);
-size_t group_arena_bytes(size_t cap, int ent, int ng) {
-  return cap * ((size_t)ent * 4 * ng + 8 * 4 * ng + 4) + (cap * GV_KIDX_ROW + kidx_table_words(cap)) * 4;
-}
+// The set's per-batch key arena for in-batch grouping (cap keys in layout l:
+// k4's, the grouped k6 one or a kg one), charged to the HBM budget like the
+// other optional tables -- and, per key, its raw row and its share of the
+// cache's table (group_bytes).
+size_t group_held(const Set* s) { return s->gk.cap ? group_bytes(s->gk.cap, s->gk.lay) : 0; }
 // The arena at hand serves this layout: the one it was allocated for, or --
 // an arena allocated by a layout promotion (g_wide) -- k4's four groups, whose
 // rows (qi * 3 + grp - 1; Z rows (grp - 1) * 8 * kC) index a prefix of the
 // larger allocation: a demoted set frees and allocates nothing.
-bool group_arena_fits(const Set* s, size_t cap, int ent, int ng) {
-  return cap <= s->gcap && ent == s->g_ent && (ng == s->g_ng || (s->g_wide && ng == GV_LGRP && ng < s->g_ng));
+bool group_arena_fits(const Set* s, size_t cap, const TabLayout& l) {
+  const TabLayout& h = s->gk.lay;
+  return cap <= s->gk.cap && l.table_words() == h.table_words() &&
+         (l.ng == h.ng || (s->g_wide && l.ng == GV_LGRP && l.ng < h.ng));
 }
-int ensure_group_arena(gv_ctx* ctx, Dev* d, Set* s, size_t cap, int ent, int ng) {
-  if (group_arena_fits(s, cap, ent, ng)) return GV_OK;
-  for (uint32_t** p : {&s->g_kqt, &s->g_kzq, &s->g_kok, &s->g_kqt2, &s->g_kzq2, &s->g_rows})
-    if (*p) { (void)hipFree(*p); *p = nullptr; }
+int ensure_group_arena(gv_ctx* ctx, Dev* d, Set* s, size_t cap, const TabLayout& l) {
+  if (group_arena_fits(s, cap, l)) return GV_OK;
+  d->opt_bytes = budget_replace(d->opt_bytes, group_held(s), 0);
+  s->gk.free();
+  if (s->g_rows) { (void)hipFree(s->g_rows); s->g_rows = nullptr; }
   s->g_idx = nullptr;
   s->g_live = false;                              // a new allocation holds no tables
   s->g_count = 0;
   s->g_wide = false;                              // (group_keys marks a promotion's allocation)
-  if (s->gcap) d->opt_bytes -= std::min(d->opt_bytes, group_arena_bytes(s->gcap, s->g_ent, s->g_ng));
-  s->gcap = 0;
-  s->g_ent = ent;
-  s->g_ng = ng;
-  const size_t eb = (size_t)ent * 4;
-  if (d->opt_bytes + group_arena_bytes(cap, ent, ng) > ctx->opt.hbm_budget) return GV_ENOMEM;
-  if (hipMalloc(&s->g_kqt, cap * eb) != hipSuccess || hipMalloc(&s->g_kzq, cap * 8 * 4) != hipSuccess ||
-      hipMalloc(&s->g_kok, cap * 4) != hipSuccess ||
-      hipMalloc(&s->g_kqt2, cap * (ng - 1) * eb) != hipSuccess ||
-      hipMalloc(&s->g_kzq2, cap * (ng - 1) * 8 * 4) != hipSuccess ||
-      hipMalloc(&s->g_rows, (cap * GV_KIDX_ROW + kidx_table_words(cap)) * 4) != hipSuccess) {
+  s->gk.lay = l;
+  const size_t T = kidx_table_words(cap);
+  if (d->opt_bytes + group_bytes(cap, l) > ctx->opt.hbm_budget) return GV_ENOMEM;
+  if (!s->gk.alloc(l, cap, true)) return GV_ENOMEM;
+  if (hipMalloc(&s->g_rows, (cap * GV_KIDX_ROW + T) * 4) != hipSuccess) {
     (void)hipGetLastError();
-    for (uint32_t** p : {&s->g_kqt, &s->g_kzq, &s->g_kok, &s->g_kqt2, &s->g_kzq2, &s->g_rows})
-      if (*p) { (void)hipFree(*p); *p = nullptr; }
+    s->gk.free();
+    s->g_rows = nullptr;
     return GV_ENOMEM;
   }
-  s->g_T = kidx_table_words(cap);
+  s->g_T = T;
   s->g_idx = s->g_rows + cap * GV_KIDX_ROW;
-  s->gcap = cap;
-  d->opt_bytes += group_arena_bytes(cap, ent, ng);
+  d->opt_bytes += group_bytes(cap, l);
   return GV_OK;
 }
 
-// In-batch key grouping for a pub33 throughput batch of n items (b prepared
-// for the pub33 pipeline, inputs on the device): the SoA rows are unpacked,
-// the items grouped by key (k_dedupe*), and when the batch has at most
-// n / group_div distinct keys their tables are built once into the set's
-// batch arena and b is switched to the keyed pipeline with the key's arena
-// row as slot.  Scratch: the set's per-lane Q-table region (unused by the
-// keyed pipeline; the pub33 pipeline rewrites it).  One read-back (the
-// distinct-key count and, with it, the count of keys the set's cache does not
-// hold) decides the route and what is built.
-//
-// group_reuse (DESIGN section 4.1k): the arena's rows [0, g_count) keep the
-// tables of the keys of earlier batches on this set.  k_group_find looks the
-// batch's distinct keys up before the read-back; the keys it missed are built
-// into rows [g_count, g_count + M) and entered (k_group_put), and the items'
-// slots are the rows (k_group_map).  When the rows do not fit, or the tables
-// at hand are another schedule's, the cache is flushed: this call builds all
-// its keys into rows [0, U) as a call without the option does, and enters
-// them.  g_count is committed once every launch is enqueued; an error on the
-// way leaves the cache dropped (the next call starts cold).
-//
-// group_promote: a set whose keys recur moves from k4's
-// layout to the option's kg layout (more groups: a dearer build per key, fewer
-// doublings per item) and back.  The two constants, serialized on the C2 batch
-// (profiles/r07/group_promote/consts_parent.jsonl): what a built key costs
-// more than in k4's layout, what an item saves on the ladder, in picoseconds.
-// Their ratio is the break-even in keys built per item: a promoted set demotes
-// above it (T_down), a k4 set promotes after two warm calls (and on a third)
-// that each built less than half of it (T_up).
-struct PromoteCost {
-  int ng;
-  uint64_t key_ps, item_ps;
+// group_keys' rows at the head of the set's per-lane Q-table region q (unused
+// by the keyed pipeline; the pub33 pipeline rewrites it) for a batch of n
+// items, C lanes, at most capU distinct keys: the dedupe's rows and table (T
+// words), the distinct keys' (x, prefix) -- with group_reuse each key's cache
+// row, the keys missed and their (x, prefix) gathered dense for the build --
+// then the key-table build's scratch rows (gvk_keys_scratch_words): room words.
+struct GroupScratch {
+  size_t T, room;
+  uint32_t *rep, *uid, *kslot, *count, *table, *kx, *kpfx, *krow, *miss, *mx, *mpfx, *sc;
 };
-constexpr PromoteCost kPromoteCost[] = {{6, 5456, 307}, {7, 7170, 497}, {9, 11436, 621}};
-const PromoteCost* promote_cost(int ng) {
-  for (const PromoteCost& c : kPromoteCost)
-    if (c.ng == ng) return &c;
-  return nullptr;
+GroupScratch carve_group(uint32_t* q, size_t C, size_t n, size_t capU, bool reuse) {
+  GroupScratch g;
+  g.T = kidx_table_words(n);
+  g.rep = q; g.uid = q + C; g.kslot = q + 2 * C; g.count = q + 3 * C; g.table = q + 3 * C + 256;
+  g.kx = g.table + g.T; g.kpfx = g.kx + 8 * capU;
+  g.krow = g.kpfx + capU; g.miss = g.krow + capU; g.mx = g.miss + capU; g.mpfx = g.mx + 8 * capU;
+  g.sc = reuse ? g.mpfx + capU : g.kpfx + capU;
+  const size_t used = (size_t)(g.sc - q), total = (size_t)GV_QTAB_WORDS * C;
+  g.room = used < total ? total - used : 0;
+  return g;
 }
-// keys built over items against the break-even: below half of it / above it
-bool promote_below_up(const PromoteCost& c, size_t built, size_t n) { return 2 * built * c.key_ps < n * c.item_ps; }
-bool promote_above_down(const PromoteCost& c, size_t built, size_t n) { return built * c.key_ps > n * c.item_ps; }
 
-int group_keys(gv_ctx* ctx, Dev* d, Set* s, gvk_batch& b, size_t n, hipStream_t st, uint32_t** used_end = nullptr) {
-  const size_t C = b.C;
-  size_t T = 512;
-  while (T < 2 * n) T <<= 1;
-  const size_t capU = round_up(std::max<size_t>(C / ctx->opt.group_div, 256), 256);
-  const bool reuse = ctx->opt.group_reuse;
-  const uint64_t seed = ctx->opt.kidx_seed;
-  uint32_t* q = s->qtab;
-  uint32_t *rep = q, *uid = q + C, *kslot = q + 2 * C, *count = q + 3 * C, *table = q + 3 * C + 256;
-  uint32_t* kx = table + T;
-  uint32_t* kpfx = kx + 8 * capU;
-  // group_reuse: each distinct key's cache row, the keys missed, their (x, prefix) gathered dense for the build
-  uint32_t *krow = kpfx + capU, *miss = krow + capU, *mx = miss + capU, *mpfx = mx + 8 * capU;
-  uint32_t* sc = reuse ? mpfx + capU : kpfx + capU;   // the key-table build's scratch rows (gvk_keys_scratch_words)
-  const size_t used = (size_t)(sc - q), total = (size_t)GV_QTAB_WORDS * C;
-  const size_t room = used < total ? total - used : 0;
-  if (gvk_keys_scratch_words((uint32_t)capU, GV_LGRP, GV_QTAB_N, 0) > room) return GV_OK;   // no room: pub33
-  const bool k6_room = gvk_keys_scratch_words((uint32_t)capU, 4, GV_K6_NT, 0) <= room;
-  const int kgng = ctx->opt.kg;                     // 0 or one of GV_KG_NGS
-  const bool kg_room = kgng && gvk_keys_scratch_words((uint32_t)capU, kgng, GV_QTAB_N, 0) <= room;
-  // layout promotion: the caller chose no layout ("kg", "k6"), the cache is on
-  // and the promoted layout's build fits the scratch
-  const int png = ctx->opt.group_promote;
-  const PromoteCost* pc = png && !kgng && !ctx->opt.k6 && reuse ? promote_cost(png) : nullptr;
-  if (pc && gvk_keys_scratch_words((uint32_t)capU, png, GV_QTAB_N, 0) > room) pc = nullptr;
-  if (!s->h_count && hipHostMalloc((void**)&s->h_count, 64, hipHostMallocDefault) != hipSuccess) {
-    s->h_count = nullptr;
-    return GV_ENOMEM;
-  }
+// The layout of a grouped call's tables: kg (5-bit windows over kgng groups) >
+// k6 (6-bit, 4 groups) > k4, each needing gtab6 (kg, k6) and its arena within
+// the HBM budget -- or, the caller having chosen none, the set's own
+// (group_promote; pc: its constants, null: off): a promoted set stays on the
+// kg layout unless this call's lookup (looked) missed more keys than the
+// break-even (a cold call rebuilds in the kg layout: the flag describes the
+// key stream); a k4 set promotes on a large enough warm call behind two warm
+// calls, all three below half the break-even.  The set's arena then holds
+// capU keys of c->lay for the schedule c->route -- or, route -1, no arena (it
+// was freed first: the cache is dropped): the batch takes the pub33 pipeline.
+struct GroupChoice {
+  TabLayout lay;
+  int route = -1;
+};
+int choose_group_layout(gv_ctx* ctx, Dev* d, Set* s, hipStream_t st, size_t n, size_t capU, size_t room,
+                        const PromoteCost* pc, bool looked, size_t missed, GroupChoice* c) {
   int rc = GV_OK;
-  // the key rows only: the signature / digest rows follow in gvk_verify, in
-  // item order or (keyed, key-ordered lanes) in slot order
-  CK(gvk_unpack(b.pub33, nullptr, nullptr, (uint32_t)n, (uint32_t)C, b.in_x, b.in_pfx, b.in_r, b.in_s, b.in_e, st));
-  b.unpacked = 2;
-  if (!reuse) s->g_live = false;                  // this call overwrites rows [0, U)
-  const bool looked = reuse && s->g_live && s->g_seed == seed;
-  // (a lookup in flight: the items' slots follow the decision, in one pass -- k_group_map)
-  CK(gvk_dedupe((uint32_t)n, (uint32_t)C, b.in_x, b.in_pfx, table, (uint32_t)T, rep, uid, count,
-                looked ? nullptr : kslot, (uint32_t)capU, (uint32_t)capU, kx, kpfx, st));
-  // a failure from here on drops the cache, unless the batch leaves for the
-  // pub33 pipeline with the arena untouched (keep) or all is enqueued (commit)
-  struct Drop {
-    Set* s;
-    bool armed;
-    ~Drop() { if (armed) s->g_live = false; }
-  } drop{s, false};
-  if (looked) {
-    drop.armed = true;                            // (count[1], the misses: cleared by gvk_dedupe)
-    CK(gvk_group_find(s->g_idx, (uint32_t)s->g_T, s->g_rows, (uint32_t)s->g_count, seed, kx, kpfx,
-                      (uint32_t)capU, count, (uint32_t)capU, krow, miss, count + 1, st));
-    ctx->grp_launches++;
-  }
-  CK(hipMemcpyAsync(s->h_count, count, looked ? 8 : 4, hipMemcpyDeviceToHost, st));
-  CK(hipStreamSynchronize(st));
-  const size_t U = *s->h_count;
-  auto keep = [&] { drop.armed = false; return GV_OK; };
-  if (U == 0 || U * ctx->opt.group_div > n || U > capU) return keep();   // many distinct keys: the pub33 pipeline
-  // the layout: kg (5-bit windows over kgng groups) > k6 (6-bit, 4 groups) > k4,
-  // each needing gtab6 (kg, k6) and its arena within the HBM budget
-  // ... or, the caller having chosen none, the set's own (group_promote): a
-  // promoted set stays on the kg layout unless this call's lookup missed more
-  // keys than the break-even (a cold call rebuilds in the kg layout: the flag
-  // describes the key stream); a k4 set promotes on a large enough warm call
-  // behind two warm calls, all three below half the break-even
-  const size_t missed = looked ? s->h_count[1] : U;
+  const bool k6_room = gvk_keys_scratch_words((uint32_t)capU, 4, GV_K6_NT, 0) <= room;
+  const int kgng = ctx->opt.kg, png = ctx->opt.group_promote;   // 0 or one of GV_KG_NGS
+  const bool kg_room = kgng && gvk_keys_scratch_words((uint32_t)capU, kgng, GV_QTAB_N, 0) <= room;
   bool promo = false;                             // the kg layout by promotion
   if (s->g_promoted)
     promo = pc && !(looked && promote_above_down(*pc, missed, n));
@@ -1076,22 +984,20 @@ int group_keys(gv_ctx* ctx, Dev* d, Set* s, gvk_batch& b, size_t n, hipStream_t 
   // the arena for the set's whole capacity when the budget holds it: a later,
   // larger chunk on this set does not regrow it (hipFree waits for the device)
   const size_t capA = round_up(std::max<size_t>(s->cap / ctx->opt.group_div, 256), 256);
-  auto arena = [&](int ent, int ng) {
-    if (capA > capU && !group_arena_fits(s, capA, ent, ng)) {
-      const int r = ensure_group_arena(ctx, d, s, capA, ent, ng);
+  auto arena = [&](const TabLayout& l) {
+    if (capA > capU && !group_arena_fits(s, capA, l)) {
+      const int r = ensure_group_arena(ctx, d, s, capA, l);
       if (r != GV_ENOMEM) return r;
     }
-    return ensure_group_arena(ctx, d, s, capU, ent, ng);
+    return ensure_group_arena(ctx, d, s, capU, l);
   };
   bool kg = kgsel && d->gtab6;
   // a promotion's arena is asked of the budget before the k4 arena is given
   // up: a refusal leaves the set, its tables and the route as they were
-  if (kg && promo && !group_arena_fits(s, capU, GV_KEY_WORDS, png)) {
-    const size_t held = s->gcap ? group_arena_bytes(s->gcap, s->g_ent, s->g_ng) : 0;
-    if (d->opt_bytes - std::min(d->opt_bytes, held) + group_arena_bytes(capU, GV_KEY_WORDS, png) > ctx->opt.hbm_budget)
-      kg = false;
-  }
-  if (kg && (rc = arena(GV_KEY_WORDS, kgsel))) {
+  if (kg && promo && !group_arena_fits(s, capU, lay_kg(png)) &&
+      budget_replace(d->opt_bytes, group_held(s), group_bytes(capU, lay_kg(png))) > ctx->opt.hbm_budget)
+    kg = false;
+  if (kg && (rc = arena(lay_kg(kgsel)))) {
     if (rc != GV_ENOMEM) return rc;
     kg = false;                                 // no room for kgsel groups
   }
@@ -1104,13 +1010,13 @@ int group_keys(gv_ctx* ctx, Dev* d, Set* s, gvk_batch& b, size_t n, hipStream_t 
       s->g_promo_refused = true;                // no gtab6 or no memory: k4, and no retry until a quiescing option
     }
   }
-  if (s->g_promoted && !(promo && kg)) {        // back to k4: flushed below (another schedule's tables)
+  if (s->g_promoted && !(promo && kg)) {        // back to k4: flushed by the caller (another schedule's tables)
     s->g_promoted = false;
     s->g_hist = 0;
     ctx->grp_demoted++;
   }
   bool k6 = !kg && ctx->opt.k6 && k6_room && d->gtab6;
-  if (k6 && (rc = arena(GV_K6_KEY_WORDS, GV_LGRP))) {
+  if (k6 && (rc = arena(lay_k6()))) {
     if (rc != GV_ENOMEM) return rc;
     k6 = false;                                 // no room for the 32-entry tables: k4
   }
@@ -1121,21 +1027,95 @@ int group_keys(gv_ctx* ctx, Dev* d, Set* s, gvk_batch& b, size_t n, hipStream_t 
   // (hipFree drains the device, and 2.5 GB of arena per 1M-item set took up
   // to ~0.1 s to map: profiles/r07/group_promote/session_b_shapes/)
   if (!kg && !k6 && pc && !s->g_promoted && !s->g_promo_refused && !d->gtab6_failed &&
-      n >= ctx->opt.group_promote_min && !group_arena_fits(s, capU, GV_KEY_WORDS, GV_LGRP)) {
-    rc = arena(GV_KEY_WORDS, png);
+      n >= ctx->opt.group_promote_min && !group_arena_fits(s, capU, lay_k4())) {
+    rc = arena(lay_kg(png));
     if (!rc) s->g_wide = true;
     else if (rc != GV_ENOMEM) return rc;
   }
-  if (!kg && !k6 && (rc = arena(GV_KEY_WORDS, GV_LGRP)))
-    return rc == GV_ENOMEM ? GV_OK : rc;        // (a refused arena was freed first: the cache is dropped)
+  if (!kg && !k6 && (rc = arena(lay_k4()))) return rc == GV_ENOMEM ? GV_OK : rc;
+  c->lay = kg ? lay_kg(kgsel) : k6 ? lay_k6() : lay_k4();
+  c->route = kg ? GV_ROUTE_KG : k6 ? GV_ROUTE_K6 : GV_ROUTE_K4;
+  return GV_OK;
+}
+
+// In-batch key grouping for a pub33 throughput batch of n items (b prepared
+// for the pub33 pipeline, inputs on the device): the SoA rows are unpacked,
+// the items grouped by key (k_dedupe*), and when the batch has at most
+// n / group_div distinct keys their tables are built once into the set's
+// batch arena and b is switched to the keyed pipeline with the key's arena
+// row as slot (*view: the tables as b got them).  Scratch: carve_group.  One
+// read-back (the distinct-key count and, with it, the count of keys the set's
+// cache does not hold) decides the route and what is built.
+//
+// group_reuse (DESIGN section 4.1k): the arena's rows [0, g_count) keep the
+// tables of the keys of earlier batches on this set.  k_group_find looks the
+// batch's distinct keys up before the read-back; the keys it missed are built
+// into rows [g_count, g_count + M) and entered (k_group_put), and the items'
+// slots are the rows (k_group_map).  When the rows do not fit, or the tables
+// at hand are another schedule's, the cache is flushed: this call builds all
+// its keys into rows [0, U) as a call without the option does, and enters
+// them.  g_count is committed once every launch is enqueued; an error on the
+// way leaves the cache dropped (the next call starts cold).
+//
+// group_promote: choose_group_layout, gv_keytabs.h.
+int group_keys(gv_ctx* ctx, Dev* d, Set* s, gvk_batch& b, size_t n, hipStream_t st, uint32_t** used_end = nullptr,
+               KeyView* view = nullptr) {
+  const size_t C = b.C;
+  const size_t capU = round_up(std::max<size_t>(C / ctx->opt.group_div, 256), 256);
+  const bool reuse = ctx->opt.group_reuse;
+  const uint64_t seed = ctx->opt.kidx_seed;
+  const GroupScratch g = carve_group(s->qtab, C, n, capU, reuse);
+  if (gvk_keys_scratch_words((uint32_t)capU, GV_LGRP, GV_QTAB_N, 0) > g.room) return GV_OK;   // no room: pub33
+  // layout promotion: the caller chose no layout ("kg", "k6"), the cache is on
+  // and the promoted layout's build fits the scratch
+  const int png = ctx->opt.group_promote;
+  const PromoteCost* pc = png && !ctx->opt.kg && !ctx->opt.k6 && reuse ? promote_cost(png) : nullptr;
+  if (pc && gvk_keys_scratch_words((uint32_t)capU, png, GV_QTAB_N, 0) > g.room) pc = nullptr;
+  if (!s->h_count && hipHostMalloc((void**)&s->h_count, 64, hipHostMallocDefault) != hipSuccess) {
+    s->h_count = nullptr;
+    return GV_ENOMEM;
+  }
+  int rc = GV_OK;
+  // the key rows only: the signature / digest rows follow in gvk_verify, in
+  // item order or (keyed, key-ordered lanes) in slot order
+  CK(gvk_unpack(b.pub33, nullptr, nullptr, (uint32_t)n, (uint32_t)C, b.in_x, b.in_pfx, b.in_r, b.in_s, b.in_e, st));
+  b.unpacked = 2;
+  if (!reuse) s->g_live = false;                  // this call overwrites rows [0, U)
+  const bool looked = reuse && s->g_live && s->g_seed == seed;
+  // (a lookup in flight: the items' slots follow the decision, in one pass -- k_group_map)
+  CK(gvk_dedupe((uint32_t)n, (uint32_t)C, b.in_x, b.in_pfx, g.table, (uint32_t)g.T, g.rep, g.uid, g.count,
+                looked ? nullptr : g.kslot, (uint32_t)capU, (uint32_t)capU, g.kx, g.kpfx, st));
+  // a failure from here on drops the cache, unless the batch leaves for the
+  // pub33 pipeline with the arena untouched (keep) or all is enqueued (commit)
+  struct Drop {
+    Set* s;
+    bool armed;
+    ~Drop() { if (armed) s->g_live = false; }
+  } drop{s, false};
+  if (looked) {
+    drop.armed = true;                            // (count[1], the misses: cleared by gvk_dedupe)
+    CK(gvk_group_find(s->g_idx, (uint32_t)s->g_T, s->g_rows, (uint32_t)s->g_count, seed, g.kx, g.kpfx,
+                      (uint32_t)capU, g.count, (uint32_t)capU, g.krow, g.miss, g.count + 1, st));
+    ctx->grp_launches++;
+  }
+  CK(hipMemcpyAsync(s->h_count, g.count, looked ? 8 : 4, hipMemcpyDeviceToHost, st));
+  CK(hipStreamSynchronize(st));
+  const size_t U = *s->h_count;
+  auto keep = [&] { drop.armed = false; return GV_OK; };
+  if (U == 0 || U * ctx->opt.group_div > n || U > capU) return keep();   // many distinct keys: the pub33 pipeline
+  GroupChoice ch;
+  if ((rc = choose_group_layout(ctx, d, s, st, n, capU, g.room, pc, looked, looked ? s->h_count[1] : U, &ch))) return rc;
+  const int route = ch.route;
+  if (route < 0) return GV_OK;
+  const bool kg = route == GV_ROUTE_KG, k6 = route == GV_ROUTE_K6;
+  const KeyTabs& gk = s->gk;
   // what is built, and where: the keys the lookup missed behind the rows in
   // use, or -- a cold, flushed or switched-off cache -- every key from row 0
-  const int route = kg ? GV_ROUTE_KG : k6 ? GV_ROUTE_K6 : GV_ROUTE_K4;
-  const uint32_t kC = (uint32_t)(reuse ? s->gcap : capU);
+  const uint32_t kC = (uint32_t)(reuse ? gk.cap : capU);
   bool append = looked && s->g_live && s->g_route == route;   // (g_live: the arena was not reallocated above)
-  if (append && s->g_count + s->h_count[1] > s->gcap) append = false;
+  if (append && s->g_count + s->h_count[1] > gk.cap) append = false;
   const size_t M = append ? s->h_count[1] : U, base = append ? s->g_count : 0;
-  const uint32_t *bx = append ? mx : kx, *bpfx = append ? mpfx : kpfx;
+  const uint32_t *bx = append ? g.mx : g.kx, *bpfx = append ? g.mpfx : g.kpfx;
   if (reuse) {
     drop.armed = true;
     if (!append) {
@@ -1143,17 +1123,20 @@ int group_keys(gv_ctx* ctx, Dev* d, Set* s, gvk_batch& b, size_t n, hipStream_t 
       s->g_live = false;
       CK(hipMemsetAsync(s->g_idx, 0xFF, s->g_T * 4, st));
     }
-    CK(gvk_group_put(s->g_idx, (uint32_t)s->g_T, s->g_rows, seed, kx, kpfx, (uint32_t)capU,
-                     append ? miss : nullptr, (uint32_t)M, (uint32_t)base, append ? mx : nullptr,
-                     append ? mpfx : nullptr, st));
+    CK(gvk_group_put(s->g_idx, (uint32_t)s->g_T, s->g_rows, seed, g.kx, g.kpfx, (uint32_t)capU,
+                     append ? g.miss : nullptr, (uint32_t)M, (uint32_t)base, append ? g.mx : nullptr,
+                     append ? g.mpfx : nullptr, st));
     if (M) ctx->grp_launches += 2;
     if (looked) {
-      CK(gvk_group_map((uint32_t)n, rep, uid, append ? krow : nullptr, kslot, st));
+      CK(gvk_group_map((uint32_t)n, g.rep, g.uid, append ? g.krow : nullptr, g.kslot, st));
       ctx->grp_launches++;
     }
   }
-  const int nt = k6 ? GV_K6_NT : GV_QTAB_N, ng = kg ? kgsel : GV_LGRP;
+  const int nt = (int)ch.lay.nt, ng = (int)ch.lay.ng;
   int with_qe = 0;
+  KeyView v(gk, base + M);
+  v.kC = kC;
+  v.lay = ch.lay;
   if (M) {
     // the tables are built on the set's side stream while k_scalar_inv (which
     // does not read keys) runs on st: both are one wave per SIMD or so
@@ -1161,32 +1144,29 @@ int group_keys(gv_ctx* ctx, Dev* d, Set* s, gvk_batch& b, size_t n, hipStream_t 
     CK(hipStreamWaitEvent(s->side, s->fork, 0));
     // the forward pass's entries in coalesced scratch rows after the ratio and
     // E rows, when they fit (else through the tables themselves)
-    with_qe = ctx->opt.keys_scratch && gvk_keys_scratch_words((uint32_t)M, ng, nt, 1) <= room ? 1 : 0;
+    with_qe = ctx->opt.keys_scratch && gvk_keys_scratch_words((uint32_t)M, ng, nt, 1) <= g.room ? 1 : 0;
     if (kg)
-      CK(gvk_keys_build_rows_kg((uint32_t)M, (uint32_t)capU, bx, bpfx, sc, with_qe, (uint32_t)base, s->g_kqt,
-                                s->g_kzq, kC, s->g_kok, s->g_kqt2, s->g_kzq2, kgsel, s->side));
-    else if (k6)
-      CK(gvk_keys_build_rows6((uint32_t)M, (uint32_t)capU, bx, bpfx, sc, with_qe, (uint32_t)base, s->g_kqt, s->g_kzq,
-                              kC, s->g_kok, s->g_kqt2, s->g_kzq2, s->side));
+      CK(gvk_keys_build_rows_kg((uint32_t)M, (uint32_t)capU, bx, bpfx, g.sc, with_qe, (uint32_t)base, gk.qt, gk.zq, kC,
+                                gk.ok, gk.qt2, gk.zq2, ng, s->side));
     else
-      CK(gvk_keys_build_rows((uint32_t)M, (uint32_t)capU, bx, bpfx, sc, with_qe, (uint32_t)base, s->g_kqt, s->g_kzq,
-                             kC, s->g_kok, s->g_kqt2, s->g_kzq2, s->side));
+      CK((k6 ? gvk_keys_build_rows6 : gvk_keys_build_rows)((uint32_t)M, (uint32_t)capU, bx, bpfx, g.sc, with_qe,
+                                                          (uint32_t)base, gk.qt, gk.zq, kC, gk.ok, gk.qt2, gk.zq2, s->side));
     CK(hipEventRecord(s->keys_done, s->side));
-    b.keys_ready = s->keys_done;
+    v.ready = s->keys_done;
   } else {
     // nothing to build: the rows were built on the side stream by earlier
     // calls on this set, whose ladders waited for them -- and so does this one,
     // should such a call have failed before its ladder was enqueued
     CK(hipStreamWaitEvent(st, s->keys_done, 0));
   }
-  if (used_end) *used_end = sc + (M ? gvk_keys_scratch_words((uint32_t)M, ng, nt, with_qe) : 0);
-  b.pub33 = nullptr;
-  b.kslot = kslot; b.kqt = s->g_kqt; b.kzq = s->g_kzq; b.kok = s->g_kok;
-  b.kC = kC; b.kcount = (uint32_t)(base + M);
-  b.kqt2 = s->g_kqt2; b.gtab4 = d->gtab4;       // null gtab4: the 125-doubling keyed ladder
+  if (used_end) *used_end = g.sc + (M ? gvk_keys_scratch_words((uint32_t)M, ng, nt, with_qe) : 0);
+  v.gtab4 = d->gtab4;
+  v.gtab6 = d->gtab6;
+  v.k6 = kg ? ng : k6 ? 4 : 0;
+  v.kqw = kg ? 2 : 0;
+  v.to_batch(b, g.kslot);
   b.gtabf = ctx->opt.gfull ? d->gtabf : nullptr;    // built by ensure_gtab4 above on first use
-  b.k6 = kg ? kgsel : k6 ? 4 : 0; b.gtab6 = d->gtab6;
-  b.kqw = kg ? 2 : 0;
+  if (view) *view = v;
   if (reuse) {                                  // everything is enqueued: the cache now holds these rows
     s->g_count = base + M;
     s->g_route = route;
@@ -1220,35 +1200,14 @@ void plan_sort(gv_ctx* ctx, Set* s, gvk_batch& b, uint32_t* base) {
   b.srt = so;
 }
 
-// A key arena other than the device's gv_keys_load arena: a host slice's
-// grouped keys (slice_group).  The launch stream waits on `ready` first.
-struct KeyArena {
-  const uint32_t *kqt, *kzq, *kok, *kqt2, *kzq2;
-  uint32_t kC, kcount;
-  const uint32_t* gtab4;
-  const uint32_t* gtab6;
-  int k6;                                       // k6 / kg group tables: the throughput pipeline only
-  int kqw;                                      // 2: the kg layout (gvk_batch kqw)
-  hipEvent_t ready;
-};
-
-// ---- the resident arena's pubkey index (option "keys_index"; gv_kidx.h)
-// Table words for an arena of `cap` slots: a power of two, at least twice the
-// capacity and 512.
-size_t kidx_table_words(size_t cap) {
-  size_t T = 512;
-  while (T < 2 * cap) T <<= 1;
-  return T;
-}
+// ---- the resident arena's pubkey index (option "keys_index"; gv_kidx.h;
+// kidx_table_words: gv_keytabs.h)
 size_t kidx_bytes(size_t cap, size_t T) { return (cap * GV_KIDX_ROW + T) * 4; }
 constexpr size_t kKidxCntBytes = 256;
 
 void kidx_free(Dev* d) {
-  if (d->kidx_rows) {                             // one block: the rows, then the table
-    (void)hipFree(d->kidx_rows);
-    d->opt_bytes -= std::min(d->opt_bytes, kidx_bytes(d->kidx_cap, d->kidx_T));
-  }
-  d->kidx_rows = d->kidx_tab = nullptr;
+  opt_free(d, d->kidx_rows, kidx_bytes(d->kidx_cap, d->kidx_T));   // one block: the rows, then the table
+  d->kidx_tab = nullptr;
   d->kidx_cap = d->kidx_T = 0;
 }
 // No index on this device until gv_keys_reset: every call takes the routes it
@@ -1277,7 +1236,7 @@ int kidx_refill(gv_ctx* ctx, Dev* d, size_t count, hipStream_t st) {
   return GV_OK;
 }
 
-// Rows and table for the arena's capacity (d->kcap), charged to the HBM budget
+// Rows and table for the arena's capacity (d->k4.cap), charged to the HBM budget
 // like the other optional tables.  On growth the rows of the first `used`
 // slots are copied and the table refilled from them.
 int kidx_ensure(gv_ctx* ctx, Dev* d, size_t used, hipStream_t st) {
@@ -1289,8 +1248,8 @@ int kidx_ensure(gv_ctx* ctx, Dev* d, size_t used, hipStream_t st) {
     d->kidx_h = nullptr;
     return GV_ENOMEM;
   }
-  if (d->kidx_rows && d->kidx_cap >= d->kcap) return GV_OK;
-  const size_t cap = d->kcap, T = kidx_table_words(cap);
+  if (d->kidx_rows && d->kidx_cap >= d->k4.cap) return GV_OK;
+  const size_t cap = d->k4.cap, T = kidx_table_words(cap);
   if (T > (size_t(1) << 31)) return GV_ENOMEM;
   uint32_t* rows = opt_alloc(ctx, d, kidx_bytes(cap, T));      // one block: the rows, then the table
   if (!rows) return GV_ENOMEM;
@@ -1301,10 +1260,7 @@ int kidx_ensure(gv_ctx* ctx, Dev* d, size_t used, hipStream_t st) {
     opt_free(d, rows, kidx_bytes(cap, T));
     return GV_EHIP;
   }
-  if (d->kidx_rows) {
-    (void)hipFree(d->kidx_rows);
-    d->opt_bytes -= std::min(d->opt_bytes, kidx_bytes(d->kidx_cap, d->kidx_T));
-  }
+  kidx_free(d);
   d->kidx_rows = rows; d->kidx_tab = tab; d->kidx_cap = cap; d->kidx_T = T;
   return kidx_refill(ctx, d, used, st);
 }
@@ -1347,21 +1303,19 @@ size_t grow_items(const gv_ctx* ctx, size_t C) {
 
 // The tables of the resident arena (gv_keys_load) that serve a keyed batch:
 // the wide-window ones when every slot in use has them (their own arena: Z
-// rows of stride kcapw) and the caller's schedule reads their layout
-// (wide_ok), else the kn ones when every slot has those, else k4's.  The
-// kinds are gvk_lat's kn values.
-enum { kTabsK4 = 0, kTabsKn = 1, kTabsWide = 2 };
-struct ArenaTabs {
-  int kind;
-  const uint32_t *kqt, *kzq, *kqt2;
-  uint32_t kC;
-};
-ArenaTabs arena_tabs(const gv_ctx* ctx, const Dev* d, bool wide_ok) {
-  if (wide_ok && ctx->opt.keys_wide && d->kqtw && d->kw_ng && d->gtab6 && d->keysw >= ctx->keys)
-    return {kTabsWide, d->kqtw, d->kzqw, d->kqtw2, (uint32_t)d->kcapw};
-  if (ctx->opt.keys_k6 && d->kqt6 && d->gtab6 && d->keys6 >= ctx->keys)
-    return {kTabsKn, d->kqt6, d->kzq6, d->kqt62, (uint32_t)d->kcap};
-  return {kTabsK4, d->kqt, d->kzq, d->kqt2, (uint32_t)d->kcap};
+// rows of stride kw.cap) and the caller's schedule reads their layout
+// (wide_ok), else the kn ones when every slot has those (kn_ok), else k4's.
+KeyView arena_tabs(const gv_ctx* ctx, const Dev* d, bool wide_ok, bool kn_ok = true) {
+  KeyView v(d->k4, ctx->keys);
+  if (wide_ok && ctx->opt.keys_wide && d->kw.qt && d->kw.lay.ng && d->gtab6 && d->keysw >= ctx->keys) {
+    v = KeyView(d->kw, ctx->keys, d->k4.ok);
+    v.kn = kTabsWide; v.k6 = (int)v.lay.ng; v.kqw = 1; v.kwq = v.lay.qw(); v.gtab6 = d->gtab6;
+  } else if (kn_ok && ctx->opt.keys_k6 && d->kn.qt && d->gtab6 && d->keys6 >= ctx->keys) {
+    v = KeyView(d->kn, ctx->keys, d->k4.ok);
+    v.kn = kTabsKn; v.k6 = GV_KN_ARENA_NG; v.gtab6 = d->gtab6;
+  }
+  v.gtab4 = d->gtab4;
+  return v;
 }
 
 // What launch() verifies: n items by key bytes (pub33) or by slot (kslot) of
@@ -1373,7 +1327,7 @@ struct Items {
   const uint8_t *sig64 = nullptr, *dig32 = nullptr, *blob = nullptr;
   const uint64_t* off = nullptr;
   const uint32_t* len = nullptr;
-  const KeyArena* ka = nullptr;                   // a host slice's grouped keys, which kslot then indexes
+  const KeyView* ka = nullptr;                    // a host slice's grouped keys, which kslot then indexes
   bool no_group = false;                          // the per-item pub33 pipeline whatever the keys repeat
   bool index = false;                             // pub33 throughput batches may route through the pubkey index
 };
@@ -1393,7 +1347,7 @@ struct LaunchOut {
 int launch(gv_ctx* ctx, Dev* d, Set* s, const Items& it, const LaunchOut& out, hipStream_t st) {
   const size_t n = it.n;
   const uint32_t* kslot = it.kslot;             // (or the index's slots, below)
-  const KeyArena* ka = it.ka;
+  const KeyView* ka = it.ka;
   if (n == 0 || n > kMaxItems) return GV_EINVAL;
   const size_t C = round_up(n, 256);
   int rc = ensure_cap(s, grow_items(ctx, C));
@@ -1415,7 +1369,6 @@ int launch(gv_ctx* ctx, Dev* d, Set* s, const Items& it, const LaunchOut& out, h
   b.digits = s->digits; b.zq = s->zq; b.flags = s->flags; b.qtab = s->qtab;
   b.bits = out.bits;
   b.inv_m = ctx->opt.inv_small ? 0u : (uint32_t)GV_INV_M;
-  const uint32_t* kzq2 = d->kzq2;
   // index (gv_dev_verify_digests / _msgs, option "keys_index"): a throughput
   // batch whose keys are all resident runs as the keyed call with those slots
   // would -- the slots looked up into the head of the set's Q-table region
@@ -1427,23 +1380,12 @@ int launch(gv_ctx* ctx, Dev* d, Set* s, const Items& it, const LaunchOut& out, h
     if (via_index) kslot = s->qtab;
     (via_index ? ctx->kidx_hit : ctx->kidx_miss)++;
   }
-  if (kslot && ka) {                            // a host slice's grouped keys
-    b.pub33 = nullptr;
-    b.kslot = kslot; b.kqt = ka->kqt; b.kzq = ka->kzq; b.kok = ka->kok;
-    b.kC = ka->kC; b.kcount = ka->kcount;
-    b.kqt2 = ka->kqt2; b.gtab4 = ka->gtab4;
-    b.k6 = ka->k6; b.kqw = ka->kqw; b.gtab6 = ka->gtab6;
-    kzq2 = ka->kzq2;
-    // the slots are on the device already (slice_group read the key count
-    // back after k_dedupe_map); only k_prep on reads the tables, so the
-    // chunk's unpack / sort / s^-1 overlap the slice's table build
-    b.keys_ready = ka->ready;
-  } else if (kslot) {
-    b.pub33 = nullptr;
-    b.kslot = kslot; b.kqt = d->kqt; b.kzq = d->kzq; b.kok = d->kok;
-    b.kC = (uint32_t)d->kcap; b.kcount = (uint32_t)ctx->keys;
-    b.kqt2 = d->kqt2; b.gtab4 = d->gtab4;       // null: the 125-doubling keyed ladder
-  }
+  // a host slice's grouped keys (the slots are on the device already:
+  // slice_group read the key count back after k_dedupe_map; only k_prep on
+  // reads the tables, so the chunk's unpack / sort / s^-1 overlap the slice's
+  // table build: ka->ready), or the resident arena's k4 tables
+  const KeyView kv = !kslot ? KeyView() : ka ? *ka : arena_tabs(ctx, d, false, false);
+  if (kslot) kv.to_batch(b, kslot);
   hipEvent_t* rs = nullptr;
   if (ctx->opt.time_kernels) {
     rs = d->ring[d->ring_next];
@@ -1460,14 +1402,7 @@ int launch(gv_ctx* ctx, Dev* d, Set* s, const Items& it, const LaunchOut& out, h
   const bool pipelined = out.st_ecm != nullptr && !small;
   // the resident arena's wide or kn tables: throughput batches on
   // k_ecmult_kn / k_ecmult_k6 (the small-batch kernels choose below)
-  if (kslot && !ka && !small) {
-    const ArenaTabs t = arena_tabs(ctx, d, true);
-    if (t.kind != kTabsK4) {
-      b.kqt = t.kqt; b.kzq = t.kzq; b.kqt2 = t.kqt2; b.kC = t.kC; b.gtab6 = d->gtab6;
-      b.k6 = t.kind == kTabsWide ? d->kw_ng : GV_KN_ARENA_NG;
-    }
-    if (t.kind == kTabsWide) { b.kqw = 1; b.kwq = d->kw_qw; }
-  }
+  if (kslot && !ka && !small) arena_tabs(ctx, d, true).to_batch(b, kslot);
   if (pipelined) {
     b.st_ecm = out.st_ecm;
     b.ecm_ready = s->ecm_ready;
@@ -1485,27 +1420,18 @@ int launch(gv_ctx* ctx, Dev* d, Set* s, const Items& it, const LaunchOut& out, h
     lb.gtab = d->gtab; lb.e_soa = s->in_e; lb.bits = out.bits;
     lb.ev[0] = b.ev[0];
     if (!kslot && n <= ctx->opt.lat_rows_max) lb.gtab6 = d->gtab6;   // k_verify_lat_sl4 (null: not built)
-    if (kslot) {
-      lb.pub33 = nullptr;
-      lb.kslot = kslot; lb.kqt = b.kqt; lb.kzq = b.kzq; lb.kok = b.kok; lb.kC = b.kC; lb.kcount = b.kcount;
-    }
     const bool sliced = ctx->opt.lat_sliced && n <= (kslot ? ctx->opt.lat_sl_max_keyed : ctx->opt.lat_sl_max);
     if (out.out8 && !sliced) return GV_EINVAL;  // byte verdicts: the sliced kernels only
     lb.out8 = out.out8;
     d->routes[kslot ? GV_ROUTE_LAT_KEYED : GV_ROUTE_LAT]++;
     if (kslot) {                                // keyed: 16 lanes per signature (group tables)
-      lb.kqt2 = b.kqt2; lb.kzq2 = kzq2; lb.glat = d->glat;
       // every slot has its GV_KW_QW-bit one-window wide tables:
-      // k_verify_lat16_kw (no doublings; their own arena: Z rows of stride
-      // kcapw); an arena of another layout, or lat_kw off, takes the kn
-      // tables: k_verify_lat16_kn (6 doublings, G from the 24-bit tables)
-      if (sliced && !ka) {
-        const ArenaTabs t = arena_tabs(ctx, d, ctx->opt.lat_kw && d->kw_qw == GV_KW_QW && d->kw_ng == GV_KW_NG1);
-        if (t.kind != kTabsK4) {
-          lb.kqt = t.kqt; lb.kzq = t.kzq; lb.kqt2 = t.kqt2; lb.kzq2 = nullptr; lb.kC = t.kC;
-          lb.gtab6 = d->gtab6; lb.kn = t.kind;
-        }
-      }
+      // k_verify_lat16_kw (no doublings); an arena of another layout, or
+      // lat_kw off, takes the kn tables: k_verify_lat16_kn (6 doublings, G
+      // from the 24-bit tables); else, or not sliced, k4's
+      const bool kw1 = ctx->opt.lat_kw && d->kw.lay == lay_wide(GV_KW_QW, GV_KW_NG1);
+      (sliced && !ka ? arena_tabs(ctx, d, kw1) : kv).to_lat(lb, kslot);
+      lb.glat = d->glat;
       if (sliced) CK(gvk_verify_lat16_sl(&lb, st));
       else CK(gvk_verify_lat16(&lb, st));
     } else if (sliced) {
@@ -1618,7 +1544,7 @@ struct HostBatch {
   uint64_t* out_bits;
   bool pinned = false;          // digest inputs in pinned host memory (gv_host_alloc): no staging copy
   const uint32_t* d_slots = nullptr;   // slice grouping: per-item key ids on the device (offset lo)
-  const KeyArena* ka = nullptr;        // ... and the arena they index
+  const KeyView* ka = nullptr;         // ... and the arena they index
   size_t d_slots_lo = 0;
   bool plain = false;                  // the per-item pub33 pipeline, no in-batch grouping (a grouped
                                        // slice's first chunk, run while the slice's key tables build)
@@ -1880,7 +1806,7 @@ bool worth_grouping(const uint8_t* pub33, size_t n, int div) {
 // the slice has few enough distinct keys the chunks then run keyed: only
 // signatures and digests (or messages) travel per chunk, the slots stay on
 // the device.  *ka is filled and *d_slots set when the route is taken.
-int slice_group(gv_ctx* ctx, Dev* d, size_t lo, size_t n, const HostBatch& hb, KeyArena* ka,
+int slice_group(gv_ctx* ctx, Dev* d, size_t lo, size_t n, const HostBatch& hb, KeyView* ka,
                 const uint32_t** d_slots, Set* g) {
   *d_slots = nullptr;
   if (!worth_grouping(hb.pub33 + lo * 33, n, ctx->opt.group_div)) return GV_OK;
@@ -1905,14 +1831,11 @@ int slice_group(gv_ctx* ctx, Dev* d, size_t lo, size_t n, const HostBatch& hb, K
   b.n = (uint32_t)n; b.C = (uint32_t)C;
   b.pub33 = g->d_in;
   b.in_x = g->in_x; b.in_pfx = g->in_pfx; b.in_r = g->in_r; b.in_s = g->in_s; b.in_e = g->in_e;
-  if ((rc = group_keys(ctx, d, g, b, n, g->st))) return rc;
+  if ((rc = group_keys(ctx, d, g, b, n, g->st, nullptr, ka))) return rc;
   if (!b.kslot) return set_release(g, g->st);   // many distinct keys after all: per-chunk pipeline
   if (b.keys_ready) CK(hipStreamWaitEvent(g->st, b.keys_ready, 0));   // (null: every key's tables were at hand)
   CK(hipEventRecord(g->grp_ready, g->st));
-  ka->kqt = b.kqt; ka->kzq = b.kzq; ka->kok = b.kok; ka->kqt2 = b.kqt2; ka->kzq2 = g->g_kzq2;
-  ka->kC = b.kC; ka->kcount = b.kcount; ka->gtab4 = b.gtab4;
-  ka->gtab6 = b.gtab6; ka->k6 = b.k6; ka->kqw = b.kqw;
-  ka->ready = g->grp_ready;
+  ka->ready = g->grp_ready;                     // (the chunks wait for this, not for the build's own event)
   *d_slots = b.kslot;
   return GV_OK;   // the set stays acquired until run_slice releases it after the last chunk
 }
@@ -1992,7 +1915,7 @@ int run_slice(gv_ctx* ctx, Dev* d, size_t lo, size_t hi, const HostBatch& hb) {
     k = 1;
   }
   HostBatch hg = hb;
-  KeyArena ka;
+  KeyView ka;
   bool grouped = false;
   if (try_group) {
     const uint32_t* dsl = nullptr;
@@ -2133,7 +2056,7 @@ namespace {
 struct ActiveSlice {
   AsyncSlice sl;
   HostBatch hr;                                   // what the chunks run (a grouped slice: device slots)
-  KeyArena ka;
+  KeyView ka;
   Set* g = nullptr;                               // its grouping set (released after its last chunk)
   int inflight = 0;
   bool submitted = false;
@@ -2282,8 +2205,8 @@ void free_set(Set& s) {
   if (s.keys_done) (void)hipEventDestroy(s.keys_done);
   if (s.grp_ready) (void)hipEventDestroy(s.grp_ready);
   if (s.side) { (void)hipStreamSynchronize(s.side); (void)hipStreamDestroy(s.side); }
-  for (uint32_t* p : {s.g_kqt, s.g_kzq, s.g_kok, s.g_kqt2, s.g_kzq2, s.g_rows})
-    if (p) (void)hipFree(p);
+  s.gk.free();
+  if (s.g_rows) (void)hipFree(s.g_rows);
   if (s.h_count) (void)hipHostFree(s.h_count);
   if (s.lad) { (void)hipStreamSynchronize(s.lad); (void)hipStreamDestroy(s.lad); }
   if (s.lad_done) (void)hipEventDestroy(s.lad_done);
@@ -2314,10 +2237,10 @@ static int presize_devices(gv_ctx* ctx) {
       if (hipMemsetAsync(s.scratch, 0, s.d_in ? (size_t)((uint8_t*)(s.bits + C / 64) - s.scratch) : 0, s.st) !=
           hipSuccess)
         return GV_EHIP;
-      rc = ensure_group_arena(ctx, d, &s, capU, GV_KEY_WORDS, GV_LGRP);
+      rc = ensure_group_arena(ctx, d, &s, capU, lay_k4());
       if (rc == GV_OK) {
-        for (uint32_t* p : {s.g_kqt, s.g_kqt2})
-          if (hipMemsetAsync(p, 0, (size_t)capU * GV_KEY_WORDS * 4 * (p == s.g_kqt ? 1 : GV_LGRP - 1), s.st) !=
+        for (uint32_t* p : {s.gk.qt, s.gk.qt2})
+          if (hipMemsetAsync(p, 0, (size_t)capU * GV_KEY_WORDS * 4 * (p == s.gk.qt ? 1 : GV_LGRP - 1), s.st) !=
               hipSuccess)
             return GV_EHIP;
       } else if (rc != GV_ENOMEM) {
@@ -2447,9 +2370,7 @@ void gv_close(gv_ctx* ctx) {
     if (d->gtab4) (void)hipFree(d->gtab4);
     if (d->gtab6) (void)hipFree(d->gtab6);
     if (d->gtabf) (void)hipFree(d->gtabf);
-    for (uint32_t* p : {d->kqt, d->kzq, d->kok, d->kqt2, d->kzq2, d->kqt6, d->kzq6, d->kqt62, d->kzq62, d->kqtw,
-                        d->kzqw, d->kqtw2, d->kzqw2})
-      if (p) (void)hipFree(p);
+    for (KeyTabs* t : {&d->k4, &d->kn, &d->kw}) t->free();
     if (d->edtab) (void)hipFree(d->edtab);
     if (d->edtab16) (void)hipFree(d->edtab16);
     if (d->ed.d_in) (void)hipFree(d->ed.d_in);
@@ -2661,101 +2582,92 @@ hipError_t stage_slots(Set* s, size_t C, const uint32_t* slots, size_t cn, hipSt
   return hipMemcpyAsync(p, slots, cn * 4, hipMemcpyHostToDevice, st);
 }
 
-// The k4 and / or the resident k6 tables of the n keys pub33 (host) into slots
-// base.. (slots: as build_wide's), one pub33 upload per chunk for both builds.
-// The k4 build takes max_batch keys at a time; the k6 tables' scratch rows per
-// key are ~12x its (GV_KN_ARENA_NG groups of 32 entries): smaller chunks.
-int build_k4k6(gv_ctx* ctx, Dev* d, Set* s, hipStream_t st, const uint8_t* pub33, size_t n, size_t base,
-               const uint32_t* slots, bool k4, bool k6) {
-  const size_t step = k6 ? std::min<size_t>(ctx->opt.max_batch, 32768) : ctx->opt.max_batch;
+// The n keys pub33 (host) through set s in chunks of `step`: the set grown to
+// the chunk's lanes C (256-aligned), or those whose Q-table region holds the
+// words(cn) words of a key-table build's scratch if more, the chunk's bytes
+// uploaded -- slots (host, n entries; null: none): the chunk's part of the list
+// behind them (stage_slots) -- body(c0, cn, C, d_slots) enqueued, and a sync
+// (the caller's pub33 chunk is read by then).  The caller holds d->mu.
+int key_chunks(Set* s, hipStream_t st, const uint8_t* pub33, size_t n, const uint32_t* slots, size_t step,
+               const std::function<size_t(size_t)>& words,
+               const std::function<hipError_t(size_t, uint32_t, uint32_t, const uint32_t*)>& body) {
   int rc;
   for (size_t c0 = 0; c0 < n; c0 += step) {
-    const size_t cn = std::min(step, n - c0);
-    const size_t C = round_up(cn, 256);
-    // scratch: the key-table build's rows (ratios, E, and when they fit the
-    // forward-pass entries) from the start of the set's Q-table region
-    const size_t w4 = k4 ? gvk_keys_scratch_words((uint32_t)cn, GV_LGRP, GV_QTAB_N, 0) : 0;
-    const size_t w6 = k6 ? gvk_keys_scratch_words((uint32_t)cn, GV_KN_ARENA_NG, GV_K6_NT, 1) : 0;
-    const size_t Cs = std::max(C, round_up(std::max(w4, w6) / GV_QTAB_WORDS + 1, 256));
-    if ((rc = ensure_cap(s, Cs))) return rc;
+    const size_t cn = std::min(step, n - c0), C = round_up(cn, 256);
+    if ((rc = ensure_cap(s, words ? std::max(C, round_up(words(cn) / GV_QTAB_WORDS + 1, 256)) : C))) return rc;
     if ((rc = set_acquire(s, st))) return rc;
     CK(hipMemcpyAsync(s->d_in, pub33 + c0 * 33, cn * 33, hipMemcpyHostToDevice, st));
     const uint32_t* d_slots = nullptr;
     if (slots) CK(stage_slots(s, C, slots + c0, cn, st, &d_slots));
-    const uint32_t b0 = slots ? 0u : (uint32_t)(base + c0);
-    if (k4) {
-      const size_t room = (size_t)GV_QTAB_WORDS * s->cap;
-      const int qe4 = ctx->opt.keys_scratch && gvk_keys_scratch_words((uint32_t)cn, GV_LGRP, GV_QTAB_N, 1) <= room;
-      CK(gvk_keys_build(s->d_in, (uint32_t)cn, (uint32_t)C, s->in_x, s->in_pfx, s->in_r, s->in_s, s->in_e, s->qtab,
-                        qe4, b0, d_slots, d->kqt, d->kzq, (uint32_t)d->kcap, d->kok, d->kqt2, d->kzq2, st));
-    }
-    if (k6)
-      CK(gvk_keys_build6(s->d_in, (uint32_t)cn, (uint32_t)C, s->in_x, s->in_pfx, s->in_r, s->in_s, s->in_e, s->qtab,
-                         ctx->opt.keys_scratch ? 1 : 0, b0, d_slots, d->kqt6, d->kzq6, (uint32_t)d->kcap, d->kok,
-                         d->kqt62, d->kzq62, st));
-    if ((rc = set_release(s, st))) return rc;
-    CK(hipStreamSynchronize(st));              // the caller's pub33 chunk is read by then
-  }
-  return GV_OK;
-}
-
-// The wide-window tables (layout d->kw_qw / d->kw_ng) of the n keys pub33 (host) into
-// slots base.. of the wide arena, in chunks whose build scratch stays within
-// what the k6 build's chunks take.  slots (host, n entries; null: append):
-// key i goes to slot slots[i] instead (gv_keys_replace; each chunk's list
-// rides behind its pub33 in the staged-input region).  The caller holds d->mu.
-int build_wide(gv_ctx* ctx, Dev* d, Set* s, hipStream_t st, const uint8_t* pub33, size_t n, size_t base,
-               const uint32_t* slots = nullptr) {
-  const size_t stepw = std::min<size_t>(ctx->opt.max_batch, std::max<size_t>(256, 32768 / (size_t)d->kw_ng / 256 * 256));
-  int rc;
-  for (size_t c0 = 0; c0 < n; c0 += stepw) {
-    const size_t cn = std::min(stepw, n - c0);
-    const size_t C = round_up(cn, 256);
-    const int qew = ctx->opt.keys_scratch ? 1 : 0;
-    const size_t ww = gvk_keys_scratch_words((uint32_t)cn, d->kw_ng, gvk_kw_nt(d->kw_qw), qew);
-    const size_t Cs = std::max(C, round_up(ww / GV_QTAB_WORDS + 1, 256));
-    if ((rc = ensure_cap(s, Cs))) return rc;
-    if ((rc = set_acquire(s, st))) return rc;
-    CK(hipMemcpyAsync(s->d_in, pub33 + c0 * 33, cn * 33, hipMemcpyHostToDevice, st));
-    const uint32_t* d_slots = nullptr;
-    if (slots) CK(stage_slots(s, C, slots + c0, cn, st, &d_slots));
-    CK(gvk_keys_build_wide(s->d_in, (uint32_t)cn, (uint32_t)C, s->in_x, s->in_pfx, s->in_r, s->in_s, s->in_e, s->qtab,
-                           qew, (uint32_t)(base + c0), d_slots, d->kqtw, d->kzqw, (uint32_t)d->kcapw, d->kok, d->kqtw2,
-                           d->kzqw2, d->kw_qw, d->kw_ng, st));
+    CK(body(c0, (uint32_t)cn, (uint32_t)C, d_slots));
     if ((rc = set_release(s, st))) return rc;
     CK(hipStreamSynchronize(st));
   }
   return GV_OK;
 }
 
+// The k4 and / or the resident k6 tables of the n keys pub33 (host) into slots
+// base.., or -- slots given (gv_keys_replace) -- key i into slot slots[i]; one
+// pub33 upload per chunk for both builds.  The k4 build takes max_batch keys
+// at a time; the k6 tables' scratch rows per key are ~12x its (GV_KN_ARENA_NG
+// groups of 32 entries): smaller chunks.
+int build_k4k6(gv_ctx* ctx, Dev* d, Set* s, hipStream_t st, const uint8_t* pub33, size_t n, size_t base,
+               const uint32_t* slots, bool k4, bool k6) {
+  const size_t step = k6 ? std::min<size_t>(ctx->opt.max_batch, 32768) : ctx->opt.max_batch;
+  auto words = [&](size_t cn) {                   // (ratios, E, and when they fit the forward-pass entries)
+    return std::max<size_t>(k4 ? gvk_keys_scratch_words((uint32_t)cn, GV_LGRP, GV_QTAB_N, 0) : 0,
+                            k6 ? gvk_keys_scratch_words((uint32_t)cn, GV_KN_ARENA_NG, GV_K6_NT, 1) : 0);
+  };
+  return key_chunks(s, st, pub33, n, slots, step, words, [&](size_t c0, uint32_t cn, uint32_t C, const uint32_t* d_slots) {
+    const uint32_t b0 = slots ? 0u : (uint32_t)(base + c0);
+    hipError_t e = hipSuccess;
+    if (k4) {
+      const size_t room = (size_t)GV_QTAB_WORDS * s->cap;
+      const int qe4 = ctx->opt.keys_scratch && gvk_keys_scratch_words(cn, GV_LGRP, GV_QTAB_N, 1) <= room;
+      e = gvk_keys_build(s->d_in, cn, C, s->in_x, s->in_pfx, s->in_r, s->in_s, s->in_e, s->qtab, qe4, b0, d_slots,
+                         d->k4.qt, d->k4.zq, (uint32_t)d->k4.cap, d->k4.ok, d->k4.qt2, d->k4.zq2, st);
+    }
+    if (k6 && e == hipSuccess)
+      e = gvk_keys_build6(s->d_in, cn, C, s->in_x, s->in_pfx, s->in_r, s->in_s, s->in_e, s->qtab,
+                          ctx->opt.keys_scratch ? 1 : 0, b0, d_slots, d->kn.qt, d->kn.zq, (uint32_t)d->kn.cap, d->k4.ok,
+                          d->kn.qt2, d->kn.zq2, st);
+    return e;
+  });
+}
+
+// The wide-window tables (layout d->kw.lay) of the n keys pub33 (host) into
+// slots base.. of the wide arena (slots: as build_k4k6's), in chunks whose
+// build scratch stays within what the k6 build's chunks take.
+int build_wide(gv_ctx* ctx, Dev* d, Set* s, hipStream_t st, const uint8_t* pub33, size_t n, size_t base,
+               const uint32_t* slots = nullptr) {
+  const KeyTabs& kw = d->kw;
+  const int qw = kw.lay.qw(), nt = (int)kw.lay.nt, ng = (int)kw.lay.ng, qew = ctx->opt.keys_scratch ? 1 : 0;
+  const size_t stepw = std::min<size_t>(ctx->opt.max_batch, std::max<size_t>(256, 32768 / (size_t)ng / 256 * 256));
+  auto words = [&](size_t cn) { return (size_t)gvk_keys_scratch_words((uint32_t)cn, ng, nt, qew); };
+  return key_chunks(s, st, pub33, n, slots, stepw, words, [&](size_t c0, uint32_t cn, uint32_t C, const uint32_t* d_slots) {
+    return gvk_keys_build_wide(s->d_in, cn, C, s->in_x, s->in_pfx, s->in_r, s->in_s, s->in_e, s->qtab, qew,
+                               (uint32_t)(base + c0), d_slots, kw.qt, kw.zq, (uint32_t)kw.cap, d->k4.ok, kw.qt2, kw.zq2,
+                               qw, ng, st);
+  });
+}
+
 // The index rows of the n keys pub33 (host) for slots base.. (slots: as
-// build_wide's), in the build chunks' staging; put: the chunk's slots also
+// build_k4k6's), in the build chunks' staging; put: the chunk's slots also
 // enter the table (an append; a replacement refills it afterwards).  The rows
 // come from the bytes as given: read_back_pub33 below cannot stand in, it
 // turns a rejected key's prefix into 00.
 int kidx_write(gv_ctx* ctx, Dev* d, Set* s, hipStream_t st, const uint8_t* pub33, size_t n, size_t base,
                const uint32_t* slots, bool put) {
-  int rc;
-  for (size_t c0 = 0; c0 < n; c0 += ctx->opt.max_batch) {
-    const size_t cn = std::min(ctx->opt.max_batch, n - c0);
-    const size_t C = round_up(cn, 256);
-    if ((rc = ensure_cap(s, C))) return rc;
-    if ((rc = set_acquire(s, st))) return rc;
-    CK(hipMemcpyAsync(s->d_in, pub33 + c0 * 33, cn * 33, hipMemcpyHostToDevice, st));
-    const uint32_t* d_slots = nullptr;
-    if (slots) CK(stage_slots(s, C, slots + c0, cn, st, &d_slots));
+  return key_chunks(s, st, pub33, n, slots, ctx->opt.max_batch, nullptr,
+                    [&](size_t c0, uint32_t cn, uint32_t, const uint32_t* d_slots) {
     const uint32_t b0 = slots ? 0u : (uint32_t)(base + c0);
-    CK(gvk_kidx_rows(s->d_in, (uint32_t)cn, b0, d_slots, d->kidx_rows, st));
-    ctx->kidx_launches++;
-    if (put) {
-      CK(gvk_kidx_put(d->kidx_tab, (uint32_t)d->kidx_T, d->kidx_rows, (uint32_t)cn, b0, d_slots, ctx->opt.kidx_seed,
-                      d->kidx_cnt, st));
+    hipError_t e = gvk_kidx_rows(s->d_in, cn, b0, d_slots, d->kidx_rows, st);
+    if (e == hipSuccess) ctx->kidx_launches++;
+    if (e == hipSuccess && put && (e = gvk_kidx_put(d->kidx_tab, (uint32_t)d->kidx_T, d->kidx_rows, cn, b0, d_slots,
+                                                    ctx->opt.kidx_seed, d->kidx_cnt, st)) == hipSuccess)
       ctx->kidx_launches++;
-    }
-    if ((rc = set_release(s, st))) return rc;
-    CK(hipStreamSynchronize(st));              // the caller's pub33 chunk is read by then
-  }
-  return GV_OK;
+    return e;
+  });
 }
 // The keys the table's last fill and the appends since left out.
 int kidx_read_left_out(Dev* d, hipStream_t st) {
@@ -2768,32 +2680,39 @@ int kidx_read_left_out(Dev* d, hipStream_t st) {
 // their tables.
 int kidx_load(gv_ctx* ctx, Dev* d, Set* s, hipStream_t st, const uint8_t* pub33, size_t n, size_t base) {
   int rc;
-  const bool had = d->kidx_rows && d->kidx_cap >= d->kcap;
+  const bool had = d->kidx_rows && d->kidx_cap >= d->k4.cap;
   if ((rc = kidx_ensure(ctx, d, base, st))) return rc;
   if (base == 0 && had && (rc = kidx_refill(ctx, d, 0, st))) return rc;   // an arena restarted: the table is cleared
   if ((rc = kidx_write(ctx, d, s, st, pub33, n, base, nullptr, true))) return rc;
   return kidx_read_left_out(d, st);
 }
 
-// The compressed keys of slots 0..n-1 read back from the k4 tables (affine
-// 1*Q of each slot); a slot whose key ParsePubKey rejected gets a prefix
-// byte it rejects again (0x00), so a rebuild keeps its verdict.
-int read_back_pub33(gv_ctx* ctx, Dev* d, hipStream_t st, size_t n, std::vector<uint8_t>& pub) {
-  std::vector<uint32_t> slots(n);
-  for (size_t i = 0; i < n; ++i) slots[i] = (uint32_t)i;
-  std::vector<uint8_t> xy(n * 64), ok(n);
+// Affine 1*Q (64 bytes) and the verdict of the n slots `slots` (host) of the
+// k4 tables, kcount slots in use; scratch of the call's own.
+int keys_point_read(Dev* d, hipStream_t st, size_t n, const uint32_t* slots, size_t kcount, uint8_t* xy, uint8_t* ok) {
   uint8_t* buf = nullptr;
   const size_t sb = round_up(n * 4, 256), xb = round_up(n * 64, 256);
   if (hipMalloc(&buf, sb + xb + n) != hipSuccess) return GV_ENOMEM;
   int rc = GV_OK;
-  if (hipMemcpyAsync(buf, slots.data(), n * 4, hipMemcpyHostToDevice, st) != hipSuccess ||
-      gvk_keys_point((uint32_t)n, (const uint32_t*)buf, d->kqt, d->kzq, (uint32_t)d->kcap, d->kok, (uint32_t)n,
-                     buf + sb, buf + sb + xb, st) != hipSuccess ||
-      hipMemcpyAsync(xy.data(), buf + sb, n * 64, hipMemcpyDeviceToHost, st) != hipSuccess ||
-      hipMemcpyAsync(ok.data(), buf + sb + xb, n, hipMemcpyDeviceToHost, st) != hipSuccess ||
+  if (hipMemcpyAsync(buf, slots, n * 4, hipMemcpyHostToDevice, st) != hipSuccess ||
+      gvk_keys_point((uint32_t)n, (const uint32_t*)buf, d->k4.qt, d->k4.zq, (uint32_t)d->k4.cap, d->k4.ok,
+                     (uint32_t)kcount, buf + sb, buf + sb + xb, st) != hipSuccess ||
+      hipMemcpyAsync(xy, buf + sb, n * 64, hipMemcpyDeviceToHost, st) != hipSuccess ||
+      hipMemcpyAsync(ok, buf + sb + xb, n, hipMemcpyDeviceToHost, st) != hipSuccess ||
       hipStreamSynchronize(st) != hipSuccess)
     rc = GV_EHIP;
   (void)hipFree(buf);
+  return rc;
+}
+
+// The compressed keys of slots 0..n-1 read back from the k4 tables (affine
+// 1*Q of each slot); a slot whose key ParsePubKey rejected gets a prefix
+// byte it rejects again (0x00), so a rebuild keeps its verdict.
+int read_back_pub33(Dev* d, hipStream_t st, size_t n, std::vector<uint8_t>& pub) {
+  std::vector<uint32_t> slots(n);
+  for (size_t i = 0; i < n; ++i) slots[i] = (uint32_t)i;
+  std::vector<uint8_t> xy(n * 64), ok(n);
+  const int rc = keys_point_read(d, st, n, slots.data(), n, xy.data(), ok.data());
   if (rc) return rc;
   pub.assign(n * 33, 0);
   for (size_t i = 0; i < n; ++i) {
@@ -2863,32 +2782,23 @@ int gv_keys_load(gv_ctx* ctx, size_t n, const uint8_t* pub33, uint32_t* slot_out
     if (ctx->opt.keys_wide && d->gtab6 && d->keysw == base && !d->kw_full) {
       const int only_qw = ctx->opt.keys_wide_qw;
       int li = wide_layout_next(0, only_qw, ctx->opt.keys_wide == 2 ? 1 : 2);
-      if (base != 0 && d->kw_ng) {                // a running arena keeps its layout
+      if (base != 0 && d->kw.lay.ng) {            // a running arena keeps its layout
         li = kWideLayoutCount;
         for (int i = 0; i < kWideLayoutCount; ++i)
-          if (kWideLayouts[i].qw == d->kw_qw && kWideLayouts[i].ng == d->kw_ng) li = i;
-      } else if (li < kWideLayoutCount && (d->kw_ng != kWideLayouts[li].ng || d->kw_qw != kWideLayouts[li].qw)) {
-        free_keys_wide(d);
-        d->kw_qw = kWideLayouts[li].qw;
-        d->kw_ng = kWideLayouts[li].ng;
+          if (lay_wide(kWideLayouts[i]) == d->kw.lay) li = i;
+      } else if (li < kWideLayoutCount && d->kw.lay != lay_wide(kWideLayouts[li])) {
+        free_keys_wide(d, lay_wide(kWideLayouts[li]));
       }
-      // the ed25519 arena's growth to ed_key_cap is reserved too (72 KB per key)
-      const size_t ed_room = (ctx->opt.ed_key_cap > d->ekcap ? ctx->opt.ed_key_cap - d->ekcap : 0) *
-                             ((size_t)GV_EDK_WORDS + 8 + 1) * 4;
-      bool ok = li < kWideLayoutCount &&
-                ensure_keys_wide(d, base + n, base, st, ctx->opt.key_cap, ctx->opt.hbm_budget, ed_room,
-                                 ctx->opt.keys_wide_bytes, ctx->opt.keys_wide1_cap);
+      bool ok = li < kWideLayoutCount && ensure_keys_wide(ctx->opt, d, base + n, base, st);
       // (a failed read-back only stops the wide tables: the k6 ones serve)
       std::vector<uint8_t> old_pub;
       bool moved = false;
       while (!ok && (li = wide_layout_next(li + 1, only_qw, 1)) < kWideLayoutCount) {
-        const bool back = moved || !base || read_back_pub33(ctx, d, st, base, old_pub) == GV_OK;
+        const bool back = moved || !base || read_back_pub33(d, st, base, old_pub) == GV_OK;
         moved = true;
-        free_keys_wide(d);
-        d->kw_qw = kWideLayouts[li].qw;
-        d->kw_ng = kWideLayouts[li].ng;
+        free_keys_wide(d, lay_wide(kWideLayouts[li]));
         if (!back) break;
-        ok = ensure_keys_wide(d, base + n, 0, st, ctx->opt.key_cap, ctx->opt.hbm_budget, ed_room, ctx->opt.keys_wide_bytes);
+        ok = ensure_keys_wide(ctx->opt, d, base + n, 0, st);   // (never the one-window 11-bit layout: keys_wide1_cap is moot)
       }
       // a failed rebuild only stops the wide tables (the k6 / k4 ones serve
       // every slot): never a gv_keys_load error
@@ -2926,31 +2836,34 @@ int gv_keys_replace(gv_ctx* ctx, size_t n, const uint32_t* slots, const uint8_t*
   if (!check_slots(count, n, slots)) return GV_EINVAL;
   std::vector<uint32_t> fs;                    // the slots (and their keys) below a table set's built prefix
   std::vector<uint8_t> fp;
+  auto below = [&](size_t lim) {
+    fs.clear();
+    fp.clear();
+    for (size_t i = 0; i < n; ++i)
+      if (slots[i] < lim) {
+        fs.push_back(slots[i]);
+        fp.insert(fp.end(), pub33 + i * 33, pub33 + (i + 1) * 33);
+      }
+  };
   for (Dev* d : ctx->devs) {                    // every device holds every key
     std::lock_guard<std::mutex> lk(d->mu);
     CK(hipSetDevice(d->id));
     Set* s = &d->set[0];
     hipStream_t st = s->st;
     for (hipStream_t t : d->hi_st) CK(hipStreamSynchronize(t));   // no pipelined ladder reads a row being rewritten
-    if (count > d->kcap || d->keys6 > d->kcap || d->keysw > d->kcapw) return GV_EINVAL;   // (never: the arenas hold their slots)
+    if (count > d->k4.cap || d->keys6 > d->k4.cap || d->keysw > d->kw.cap) return GV_EINVAL;   // (never: the arenas hold their slots)
     int rc;
     // which: 0 the k4 tables (every slot), 1 the k6 tables (slots below keys6),
     // 2 the wide tables in the arena's layout (slots below keysw); one pass of
     // gv_keys_load's chunks per table set
     for (int which = 0; which < 3; ++which) {
-      const size_t lim = which == 0 ? count : which == 1 ? (d->kqt6 ? d->keys6 : 0) : (d->kqtw ? d->keysw : 0);
+      const size_t lim = which == 0 ? count : which == 1 ? (d->kn.qt ? d->keys6 : 0) : (d->kw.qt ? d->keysw : 0);
       if (lim == 0) continue;
       const uint32_t* sl = slots;
       const uint8_t* pb = pub33;
       size_t m = n;
       if (lim < count) {
-        fs.clear();
-        fp.clear();
-        for (size_t i = 0; i < n; ++i)
-          if (slots[i] < lim) {
-            fs.push_back(slots[i]);
-            fp.insert(fp.end(), pub33 + i * 33, pub33 + (i + 1) * 33);
-          }
+        below(lim);
         sl = fs.data();
         pb = fp.data();
         m = fs.size();
@@ -2963,13 +2876,7 @@ int gv_keys_replace(gv_ctx* ctx, size_t n, const uint32_t* slots, const uint8_t*
     // the named slots' rows, then the table refilled from every row -- the
     // old bytes leave it, and the order of replacements does not matter
     if (d->kidx_rows && d->kidx_keys && !d->kidx_failed) {
-      fs.clear();
-      fp.clear();
-      for (size_t i = 0; i < n; ++i)
-        if (slots[i] < d->kidx_keys) {
-          fs.push_back(slots[i]);
-          fp.insert(fp.end(), pub33 + i * 33, pub33 + (i + 1) * 33);
-        }
+      below(d->kidx_keys);
       if ((!fs.empty() && kidx_write(ctx, d, s, st, fp.data(), fs.size(), 0, fs.data(), false) != GV_OK) ||
           kidx_refill(ctx, d, d->kidx_keys, st) != GV_OK || kidx_read_left_out(d, st) != GV_OK)
         kidx_stop(d);
@@ -3004,9 +2911,7 @@ namespace {
 // per key each -- stays within cap + the old arena.
 int ensure_ed_keys(Dev* d, size_t need, size_t used, hipStream_t st, size_t cap_limit) {
   if (need <= d->ekcap) return GV_OK;
-  const size_t grow = d->ekcap >= cap_limit ? need
-                                            : std::min<size_t>(2 * d->ekcap, std::max<size_t>(need, cap_limit));
-  const size_t cap = round_up(std::max<size_t>({need, grow, 256}), 256);
+  const size_t cap = arena_grow_cap(d->ekcap, need, cap_limit, 256);
   uint32_t *t = nullptr, *p = nullptr, *o = nullptr;
   auto fail = [&]() {
     for (uint32_t* q : {t, p, o}) if (q) (void)hipFree(q);
@@ -3055,7 +2960,7 @@ inline size_t ed_wide_windows(int rb) { return rb == 8 ? 32 : 43; }
 // Drop the wide ed25519 arena (its memory back to the device).
 void free_ed_keys_wide(Dev* d) {
   if (d->ektabw) { (void)hipFree(d->ektabw); d->ektabw = nullptr; }
-  d->opt_bytes -= std::min(d->opt_bytes, d->ekcapw * ed_wide_slot_bytes(d->ekw_rb));
+  d->opt_bytes = budget_replace(d->opt_bytes, d->ekcapw * ed_wide_slot_bytes(d->ekw_rb), 0);
   d->ekcapw = d->ekeysw = 0;
 }
 
@@ -3068,17 +2973,14 @@ void free_ed_keys_wide(Dev* d) {
 // ed_key_cap, 8 GiB of batch scratch), or when an allocation fails.
 bool ensure_ed_keys_wide(gv_ctx* ctx, Dev* d, size_t need, size_t used, hipStream_t st) {
   if (need <= d->ekcapw) return true;
-  const size_t cap_limit = ctx->opt.ed_key_cap;
-  const size_t grow = d->ekcapw >= cap_limit ? need
-                                             : std::min<size_t>(2 * d->ekcapw, std::max<size_t>(need, cap_limit));
-  const size_t cap = round_up(std::max<size_t>({need, grow, 256}), 256);
+  const size_t cap = arena_grow_cap(d->ekcapw, need, ctx->opt.ed_key_cap, 256);
   const size_t slot_b = ed_wide_slot_bytes(d->ekw_rb);
   if (!slot_b) return false;
   if (ctx->opt.ed_keys_wide_bytes && cap * slot_b > ctx->opt.ed_keys_wide_bytes) return false;
   if (d->opt_bytes + cap * slot_b > ctx->opt.hbm_budget) return false;
   size_t free_b = 0, total_b = 0;
   if (hipMemGetInfo(&free_b, &total_b) != hipSuccess) return false;
-  const size_t reserve = (ctx->opt.key_cap > d->kcap ? ctx->opt.key_cap - d->kcap : 0) * key_slot_bytes(true) +
+  const size_t reserve = (ctx->opt.key_cap > d->k4.cap ? ctx->opt.key_cap - d->k4.cap : 0) * resident_slot_bytes(true) +
                          (ctx->opt.ed_key_cap > d->ekcap ? ctx->opt.ed_key_cap - d->ekcap : 0) *
                              ((size_t)GV_EDK_WORDS + 8 + 1) * 4 +
                          (size_t(8) << 30);
@@ -3096,7 +2998,7 @@ bool ensure_ed_keys_wide(gv_ctx* ctx, Dev* d, size_t need, size_t used, hipStrea
     return false;
   }
   if (d->ektabw) (void)hipFree(d->ektabw);
-  d->opt_bytes = d->opt_bytes - std::min(d->opt_bytes, d->ekcapw * slot_b) + cap * slot_b;
+  d->opt_bytes = budget_replace(d->opt_bytes, d->ekcapw * slot_b, cap * slot_b);
   d->ektabw = t;
   d->ekcapw = cap;
   return true;
@@ -3557,37 +3459,20 @@ int gv_keys_point(gv_ctx* ctx, size_t n, const uint32_t* slots, uint8_t* out_xy6
   CK(hipSetDevice(d->id));
   hipStream_t st = d->set[0].st;
   int rc = ensure_keys(d, 1, ctx->keys, st, ctx->opt.key_cap, ctx->opt.hbm_budget, nullptr);
-  if (rc) return rc;
-  uint8_t* buf = nullptr;
-  const size_t sb = round_up(n * 4, 256), xb = round_up(n * 64, 256);
-  if (hipMalloc(&buf, sb + xb + n) != hipSuccess) return GV_ENOMEM;
-  if (hipMemcpyAsync(buf, slots, n * 4, hipMemcpyHostToDevice, st) != hipSuccess ||
-      gvk_keys_point((uint32_t)n, (const uint32_t*)buf, d->kqt, d->kzq, (uint32_t)d->kcap, d->kok,
-                     (uint32_t)ctx->keys, buf + sb, buf + sb + xb, st) != hipSuccess ||
-      hipMemcpyAsync(out_xy64, buf + sb, n * 64, hipMemcpyDeviceToHost, st) != hipSuccess ||
-      hipMemcpyAsync(out_ok, buf + sb + xb, n, hipMemcpyDeviceToHost, st) != hipSuccess ||
-      hipStreamSynchronize(st) != hipSuccess)
-    rc = GV_EHIP;
-  (void)hipFree(buf);
-  return rc;
+  return rc ? rc : keys_point_read(d, st, n, slots, ctx->keys, out_xy64, out_ok);
 }
 
 namespace {
-// One key arena as k_keys_entry reads it.
-struct EntryTabs {
-  const uint32_t *kqt, *kqt2, *kzq, *kok;
-  uint32_t kC, kcount, nt, ew, ng;
-};
 // Every group below the layout's NG, every entry in 1..NT.
-bool entry_args_ok(const EntryTabs& t, size_t n, const uint32_t* groups, const uint32_t* js) {
+bool entry_args_ok(const KeyView& t, size_t n, const uint32_t* groups, const uint32_t* js) {
   for (size_t i = 0; i < n; ++i)
-    if (groups[i] >= t.ng || js[i] < 1 || js[i] > t.nt) return false;
+    if (groups[i] >= t.lay.ng || js[i] < 1 || js[i] > t.lay.nt) return false;
   return true;
 }
 // The triples up, k_keys_entry, the points and verdicts down; scratch of the
 // call's own (nothing of the context is written).  An arena with no slot to
 // read answers zeros without a launch.
-int entry_read(const EntryTabs& t, hipStream_t st, size_t n, const uint32_t* slots, const uint32_t* groups,
+int entry_read(const KeyView& t, hipStream_t st, size_t n, const uint32_t* slots, const uint32_t* groups,
                const uint32_t* js, uint8_t* out_xy64, uint8_t* out_ok) {
   if (t.kcount == 0 || !t.kqt || !t.kqt2 || !t.kzq || !t.kok) {
     memset(out_xy64, 0, n * 64);
@@ -3603,7 +3488,8 @@ int entry_read(const EntryTabs& t, hipStream_t st, size_t n, const uint32_t* slo
       hipMemcpyAsync(buf + sb, groups, n * 4, hipMemcpyHostToDevice, st) != hipSuccess ||
       hipMemcpyAsync(buf + 2 * sb, js, n * 4, hipMemcpyHostToDevice, st) != hipSuccess ||
       gvk_keys_entry((uint32_t)n, (const uint32_t*)buf, (const uint32_t*)(buf + sb), (const uint32_t*)(buf + 2 * sb),
-                     t.kqt, t.kqt2, t.kzq, t.kC, t.kok, t.kcount, t.nt, t.ew, t.ng, d_xy, d_ok, st) != hipSuccess ||
+                     t.kqt, t.kqt2, t.kzq, t.kC, t.kok, t.kcount, t.lay.nt, t.lay.ew, t.lay.ng, d_xy, d_ok,
+                     st) != hipSuccess ||
       hipMemcpyAsync(out_xy64, d_xy, n * 64, hipMemcpyDeviceToHost, st) != hipSuccess ||
       hipMemcpyAsync(out_ok, d_ok, n, hipMemcpyDeviceToHost, st) != hipSuccess ||
       hipStreamSynchronize(st) != hipSuccess)
@@ -3620,20 +3506,11 @@ int gv_keys_entry(gv_ctx* ctx, int dev_slot, int tabs, size_t n, const uint32_t*
   if (!slots || !groups || !js || !out_xy64 || !out_ok || n > kMaxItems) return GV_EINVAL;
   Dev* d = ctx->devs[dev_slot];
   std::lock_guard<std::mutex> lk(d->mu);
-  EntryTabs t;
-  const size_t keys = ctx->keys;
-  if (tabs == 0) {
-    t = {d->kqt, d->kqt2, d->kzq, d->kok, (uint32_t)d->kcap, (uint32_t)std::min(keys, d->kcap), GV_QTAB_N,
-         GV_QENT_WORDS, GV_LGRP};
-  } else if (tabs == 1) {
-    if (!d->kqt6) return GV_EINVAL;
-    t = {d->kqt6, d->kqt62, d->kzq6, d->kok, (uint32_t)d->kcap, (uint32_t)std::min({keys, d->keys6, d->kcap}),
-         GV_K6_NT, GV_QENT_WORDS, GV_KN_ARENA_NG};
-  } else {
-    if (!d->kqtw || !d->kw_ng || !d->kw_qw) return GV_EINVAL;
-    t = {d->kqtw, d->kqtw2, d->kzqw, d->kok, (uint32_t)d->kcapw, (uint32_t)std::min({keys, d->keysw, d->kcapw}),
-         (uint32_t)gvk_kw_nt(d->kw_qw), GV_KW_ENT_WORDS, (uint32_t)d->kw_ng};
-  }
+  // the slots that have the set's tables: all (k4), below keys6 (kn), below keysw (wide)
+  const KeyTabs& tb = tabs == 0 ? d->k4 : tabs == 1 ? d->kn : d->kw;
+  if (tabs && (!tb.qt || !tb.lay.ng)) return GV_EINVAL;
+  KeyView t(tb, std::min({ctx->keys, tabs == 0 ? ctx->keys : tabs == 1 ? d->keys6 : d->keysw, tb.cap}), d->k4.ok);
+  if (tabs == 0) t.lay = lay_k4();              // (an arena never loaded answers zeros, not an error)
   if (!entry_args_ok(t, n, groups, js)) return GV_EINVAL;
   CK(hipSetDevice(d->id));
   return entry_read(t, d->set[0].st, n, slots, groups, js, out_xy64, out_ok);
@@ -3647,10 +3524,11 @@ int gv_group_entry(gv_ctx* ctx, int dev_slot, int set, size_t n, const uint32_t*
   Dev* d = ctx->devs[dev_slot];
   std::lock_guard<std::mutex> lk(d->mu);
   const Set* s = set < 2 ? &d->set[set] : &d->gset[set - 2];
-  if (!s->g_live || !s->g_kqt || !s->g_rows || s->g_ent <= 0 || s->g_lng < 2 || s->g_lng > s->g_ng) return GV_EINVAL;
-  const size_t count = std::min(s->g_count, s->gcap);
-  const EntryTabs t = {s->g_kqt, s->g_kqt2, s->g_kzq, s->g_kok, (uint32_t)s->gcap, (uint32_t)count,
-                       (uint32_t)(s->g_ent / GV_QENT_WORDS), GV_QENT_WORDS, (uint32_t)s->g_lng};
+  if (!s->g_live || !s->gk.qt || !s->g_rows || !s->gk.lay.nt || s->g_lng < 2 || s->g_lng > (int)s->gk.lay.ng)
+    return GV_EINVAL;
+  const size_t count = std::min(s->g_count, s->gk.cap);
+  KeyView t(s->gk, count);
+  t.lay.ng = (uint32_t)s->g_lng;                  // (k4's four groups in a promotion's arena)
   if (!entry_args_ok(t, n, groups, js)) return GV_EINVAL;
   CK(hipSetDevice(d->id));
   // after the set's last work (an asynchronous gv_dev_verify_* call) and the
@@ -3813,15 +3691,15 @@ int gv_get_option(gv_ctx* ctx, const char* key, long long* val) {
   if (ed) kl = std::unique_lock<std::mutex>(ctx->ed_keys_mu);
   Dev* d = ctx->devs[0];
   std::lock_guard<std::mutex> lk(d->mu);
-  const bool kw = d->kqtw && d->keysw, has = d->kidx_tab && !d->kidx_failed, ekw = d->ektabw && d->ekeysw;
+  const bool kw = d->kw.qt && d->keysw, has = d->kidx_tab && !d->kidx_failed, ekw = d->ektabw && d->ekeysw;
   // (the row capacity of the first scratch set's grouping arena; 0: none yet)
-  *val = !strcmp(key, "group_reuse_rows")      ? (long long)d->set[0].gcap
+  *val = !strcmp(key, "group_reuse_rows")      ? (long long)d->set[0].gk.cap
          // groups per key of the device's last grouped call (4: k4's and k6's layouts; 0: none yet); the
          // bytes of optional tables the HBM budget counts on the device
          : !strcmp(key, "group_layout")        ? (long long)d->group_layout
          : !strcmp(key, "hbm_optional_bytes")  ? (long long)d->opt_bytes
-         : !strcmp(key, "kw_arena_qw")         ? (kw ? d->kw_qw : 0)
-         : !strcmp(key, "kw_arena_ng")         ? (kw ? d->kw_ng : 0)
+         : !strcmp(key, "kw_arena_qw")         ? (kw ? d->kw.lay.qw() : 0)
+         : !strcmp(key, "kw_arena_ng")         ? (kw ? (int)d->kw.lay.ng : 0)
          : !strcmp(key, "keys_index_live")     ? (long long)kidx_live(ctx, d)
          : !strcmp(key, "keys_index_keys")     ? (long long)(has ? d->kidx_keys : 0)
          : !strcmp(key, "keys_index_left_out") ? (long long)(has ? d->kidx_left_out : 0)
