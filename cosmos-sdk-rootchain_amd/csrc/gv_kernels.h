@@ -495,6 +495,29 @@ hipError_t gvk_kidx_put(uint32_t* table, uint32_t tslots, const uint32_t* rows, 
                         const uint32_t* slots, uint64_t seed, uint32_t* left_out, hipStream_t st);
 hipError_t gvk_kidx_find(const uint32_t* table, uint32_t tslots, const uint32_t* rows, uint32_t count, uint64_t seed,
                          const uint8_t* pub33, uint32_t n, uint32_t* slot_out, uint32_t* miss, hipStream_t st);
+// A routed batch with a few keys that are not resident (option
+// "keys_index_split"): the dense sub-batch of those items, `cap` rows (device).
+// count: one word, the rows taken; idx[j]: the item of row j; pub33 / sig64 /
+// dig32 (or off / len: the message path, the caller's blob shared) its inputs
+// as the pub33 routes read them; bits: the sub-batch's accept bitmap.
+typedef struct gvk_split {
+  uint32_t cap;
+  uint32_t *count, *idx;
+  uint8_t *pub33, *sig64, *dig32;
+  uint64_t* off;
+  uint32_t* len;
+  uint64_t* bits;
+} gvk_split;
+// gvk_kidx_split: the items g < n with slot[g] == GV_KIDX_EMPTY (gvk_kidx_find's
+// output) take rows 0.. in an unspecified order; a row at or past cap is not
+// written (the caller launches only when the misses fit).  dig32 null: off /
+// len are copied.  sig64 and dig32 4-byte aligned.
+// gvk_bits_merge: bits[idx[j]] |= s->bits[j] for the rows j < m (m <= cap,
+// idx[j] < n), by atomic OR.
+hipError_t gvk_kidx_split(const gvk_split* s, const uint32_t* slot, uint32_t n, const uint8_t* pub33,
+                          const uint8_t* sig64, const uint8_t* dig32, const uint64_t* off, const uint32_t* len,
+                          hipStream_t st);
+hipError_t gvk_bits_merge(const gvk_split* s, uint32_t m, uint32_t n, uint64_t* bits, hipStream_t st);
 // The grouped route's per-set key-table cache (option "group_reuse"; DESIGN
 // section 4.1k): the same rows / table over a set's per-batch arena.
 // gvk_group_find: one lane per distinct key u < min(*ucount, capU) of the

@@ -114,4 +114,36 @@ inline const PromoteCost* promote_cost(int ng) {
 inline bool promote_below_up(const PromoteCost& c, size_t built, size_t n) { return 2 * built * c.key_ps < n * c.item_ps; }
 inline bool promote_above_down(const PromoteCost& c, size_t built, size_t n) { return built * c.key_ps > n * c.item_ps; }
 
+// keys_index_split: a pub33 device batch the index looked
+// up, `miss` of its items not resident.  It splits -- the resident items on the
+// arena, the others as a dense sub-batch on the pub33 routes -- when the index
+// is live, there is a miss, the option (`bound`: the most misses per call still
+// split; 0 = never) covers them and the sub-batch's buffers are at hand.  Else
+// no miss runs keyed and any miss falls through whole, as without the option.
+inline bool kidx_split_ok(size_t bound, size_t miss, bool live, bool buffers) {
+  return live && buffers && miss != 0 && miss <= bound;
+}
+// Rows of the sub-batch's buffers for `miss` items: the misses rounded up to
+// 256, a growth at least doubling what is held (never sized by the option).
+inline size_t kidx_split_rows(size_t have, size_t miss) {
+  const size_t need = (miss + 255) / 256 * 256;
+  return need <= have ? have : std::max(need, 2 * have);
+}
+// Their bytes, each part 256-byte aligned: the row counter, idx, pub33, sig64,
+// dig32 (or u64 off + u32 len in its place), the accept bitmap.
+struct SplitLayout {
+  size_t idx, pub, sig, third, len, bits, total;
+};
+inline SplitLayout kidx_split_layout(size_t rows) {   // rows % 256 == 0
+  SplitLayout L;
+  L.idx = 256;
+  L.pub = L.idx + rows * 4;
+  L.sig = L.pub + (rows * 33 + 255) / 256 * 256;
+  L.third = L.sig + rows * 64;
+  L.len = L.third + rows * 8;
+  L.bits = L.third + rows * 32;
+  L.total = L.bits + (rows / 64 * 8 + 255) / 256 * 256;
+  return L;
+}
+
 }  // namespace gvkt

@@ -1,8 +1,9 @@
 // gv_kidx.hip -- kernels of the resident key arena's pubkey index (option
 // "keys_index"; gv_kidx.h holds the hash, the probe sequence, insert and
-// lookup), and of the grouped route's per-set key-table cache over the same
-// routines (option "group_reuse").  All are one lane per key or item,
-// memory-bound and tiny beside a table build or a ladder.
+// lookup), of a routed batch's split into resident and non-resident items
+// (option "keys_index_split"), and of the grouped route's per-set key-table
+// cache over the same routines (option "group_reuse").  All are one lane per
+// key or item, memory-bound and tiny beside a table build or a ladder.
 #include <hip/hip_runtime.h>
 #include "gv_kernels.h"
 #include "gv_kidx.h"
@@ -55,6 +56,71 @@ __global__ __launch_bounds__(256) void k_kidx_find(const u32* table, u32 tmask, 
     slot_out[g] = slot;
   }
   wave_count(g < n && slot == GV_KIDX_EMPTY, miss);
+}
+
+// ---- a routed batch with a few keys that are not resident (option
+// "keys_index_split").
+//
+// k_kidx_split: one lane per item of the batch.  An item whose looked-up slot
+// is GV_KIDX_EMPTY takes the next row j of the dense sub-batch (one atomicAdd
+// per wave on *count, as k_group_find; the order of rows across waves is
+// unspecified): idx[j] = the item, its 33 key bytes (the caller's AoS,
+// unaligned), its 64 signature bytes and its digest (dig32) or its message's
+// offset and length (dig32 null; the blob is shared) into row j of the
+// sub-batch's arrays.  A row at or past cap is never written (the host
+// launches only when the misses fit).  sig64 / dig32 are 4-byte aligned (the
+// device calls check); a 16-byte aligned sig64 is copied as 16-byte vectors.
+__global__ __launch_bounds__(256) void k_kidx_split(const u32* slot, u32 n, const uint8_t* pub33, const uint8_t* sig64,
+                                                     const uint8_t* dig32, const uint64_t* off, const u32* len,
+                                                     u32 cap, u32* count, u32* idx, uint8_t* mpub, uint8_t* msig,
+                                                     uint8_t* mdig, uint64_t* moff, u32* mlen) {
+  const u32 g = blockIdx.x * blockDim.x + threadIdx.x;
+  const bool missed = g < n && slot[g] == GV_KIDX_EMPTY;
+  const uint64_t m = __ballot(missed);
+  if (m == 0) return;                                    // wave-uniform
+  const u32 lane = threadIdx.x & 63u, leader = (u32)__builtin_ctzll(m);
+  u32 b0 = 0;
+  if (lane == leader) b0 = atomicAdd(count, (u32)__builtin_popcountll(m));
+  b0 = (u32)__shfl((int)b0, (int)leader);
+  if (!missed) return;
+  const u32 j = b0 + (u32)__builtin_popcountll(m & ((1ull << lane) - 1ull));
+  if (j >= cap) return;
+  idx[j] = g;
+  const uint8_t* p = pub33 + (size_t)g * 33u;
+  uint8_t* q = mpub + (size_t)j * 33u;
+#pragma unroll
+  for (int i = 0; i < 33; ++i) q[i] = p[i];
+  if (((uintptr_t)sig64 & 15u) == 0) {                   // kernel-uniform
+    const uint4* s = (const uint4*)(sig64 + (size_t)g * 64u);
+    uint4* t = (uint4*)(msig + (size_t)j * 64u);
+    const uint4 a = s[0], b = s[1], c = s[2], d = s[3];
+    t[0] = a; t[1] = b; t[2] = c; t[3] = d;
+  } else {
+    const u32* s = (const u32*)(sig64 + (size_t)g * 64u);
+    u32* t = (u32*)(msig + (size_t)j * 64u);
+#pragma unroll
+    for (int i = 0; i < 16; ++i) t[i] = s[i];
+  }
+  if (dig32) {
+    const u32* s = (const u32*)(dig32 + (size_t)g * 32u);
+    u32* t = (u32*)(mdig + (size_t)j * 32u);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) t[i] = s[i];
+  } else {
+    moff[j] = off[g];
+    mlen[j] = len[g];
+  }
+}
+
+// k_bits_merge: one lane per sub-batch row j < m.  An accepted row (bit j of
+// sub) sets bit idx[j] of the batch's bitmap -- an atomic OR: two rows may
+// share a word.
+__global__ __launch_bounds__(256) void k_bits_merge(const uint64_t* sub, const u32* idx, u32 m, u32 n,
+                                                     unsigned long long* bits) {
+  const u32 j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= m || !((sub[j >> 6] >> (j & 63u)) & 1ull)) return;
+  const u32 i = idx[j];
+  if (i < n) atomicOr(bits + (i >> 6), 1ull << (i & 63u));
 }
 
 // ---- the grouped route's per-set key-table cache (option "group_reuse";
@@ -152,6 +218,26 @@ hipError_t gvk_kidx_find(const uint32_t* table, uint32_t tslots, const uint32_t*
   if (tslots == 0 || (tslots & (tslots - 1))) return hipErrorInvalidValue;
   hipLaunchKernelGGL(gv::k_kidx_find, dim3((n + 255) / 256), dim3(256), 0, st, table, tslots - 1, rows, count, seed,
                      pub33, n, slot_out, miss);
+  return hipGetLastError();
+}
+
+hipError_t gvk_kidx_split(const gvk_split* s, const uint32_t* slot, uint32_t n, const uint8_t* pub33,
+                          const uint8_t* sig64, const uint8_t* dig32, const uint64_t* off, const uint32_t* len,
+                          hipStream_t st) {
+  if (n == 0) return hipSuccess;
+  if (!s->cap || (!dig32 && (!off || !len))) return hipErrorInvalidValue;
+  const hipError_t e = hipMemsetAsync(s->count, 0, 4, st);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(gv::k_kidx_split, dim3((n + 255) / 256), dim3(256), 0, st, slot, n, pub33, sig64, dig32, off, len,
+                     s->cap, s->count, s->idx, s->pub33, s->sig64, s->dig32, s->off, s->len);
+  return hipGetLastError();
+}
+
+hipError_t gvk_bits_merge(const gvk_split* s, uint32_t m, uint32_t n, uint64_t* bits, hipStream_t st) {
+  if (m == 0) return hipSuccess;
+  if (m > s->cap) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(gv::k_bits_merge, dim3((m + 255) / 256), dim3(256), 0, st, (const uint64_t*)s->bits,
+                     (const uint32_t*)s->idx, m, n, (unsigned long long*)bits);
   return hipGetLastError();
 }
 

@@ -136,6 +136,10 @@ struct Options {
                                 // resident onto the keyed pipeline ("keys_index", GV_KEYS_INDEX): taken by an arena
                                 // started from slot 0; 0 stops its use at once
   uint64_t kidx_seed = 0;       // the index hash's seed, drawn at gv_open ("keys_index_seed": a test hook)
+  size_t keys_index_split = 0;  // ... and a routed batch with at most this many items whose keys are NOT resident still
+                                // runs keyed: those items are compacted into a sub-batch for the pub33 routes, under
+                                // the main ladder, and their accept bits merged in ("keys_index_split"; 0 = any miss
+                                // sends the whole batch to the pub33 routes)
   bool ed_group = true;          // ed25519 throughput batches: in-batch key grouping + k_ed_keyed (GV_ED_GROUP=0: A/B)
   size_t ed_group_min = 196608;  // ... from this many items (the key build's chain is ~1 ms of one-lane chains whatever
                                  // the key count up to ~65k keys; the keyed kernel saves ~6.4 ns per item; host
@@ -297,6 +301,8 @@ constexpr Row kRowsLater[] = {
     {"group_promote", GVO(group_promote), A_SET, 1 | 1 << 6 | 1 << 7 | 1 << 9, 0, X_ASIS, FX_QUIESCE, true,
      "GV_GROUP_PROMOTE", E_SETTER},
     {"group_promote_min", GVO(group_promote_min), A_RANGE, 0, kMaxItems, X_ASIS, FX_NONE, true},
+    // the most non-resident items of a routed batch that are still split off (0: none; no variable)
+    {"keys_index_split", GVO(keys_index_split), A_RANGE, 0, kMaxItems, X_ASIS, FX_NONE, true},
 };
 #undef GVO
 

@@ -246,6 +246,19 @@ struct Set {
   unsigned g_hist = 0;
   bool g_promoted = false, g_promo_refused = false, g_wide = false;
   uint32_t* h_count = nullptr;                    // pinned: the distinct-key count read back
+  // a routed pub33 device batch with a few keys that are not resident (option
+  // "keys_index_split"): the dense sub-batch of those
+  // items -- miss_buf, one block of kidx_split_layout(miss.cap).total bytes
+  // charged to the HBM budget, carved into `miss` -- and the scratch set the pub33 routes
+  // verify it on (miss_set: its scratch and `last` only).  They belong to the
+  // set whose call split: the merge runs before that call's set_release, so
+  // the set's next call (two pipelined calls alternate the sets) finds them free.
+  // miss_done: the sub-batch's end on the front stream, which the ladder
+  // stream's merge waits for
+  uint32_t* miss_buf = nullptr;
+  gvk_split miss = {};
+  Set* miss_set = nullptr;
+  hipEvent_t miss_done = nullptr;
   // pinned host staging
   uint8_t* h_in = nullptr;
   size_t h_in_cap = 0;
@@ -751,6 +764,9 @@ struct gv_ctx {
   std::atomic<uint64_t> keys_replaced{0};   // slots gv_keys_replace rewrote since gv_open ("keys_replaced")
   std::mutex keys_mu;
   std::atomic<uint64_t> kidx_hit{0}, kidx_miss{0};   // pub33 device batches routed keyed / that fell through
+  // ... routed with their non-resident items split off ("keys_index_split_calls"; they count in kidx_hit
+  // too), and those items ("keys_index_split_items")
+  std::atomic<uint64_t> kidx_split_calls{0}, kidx_split_items{0};
   // the grouped route's key-table cache (option "group_reuse"): keys whose tables were reused / built by calls
   // with the option on, caches flushed, k_group_* launches ("group_reuse_hit", "_built", "_reset", "_launches")
   std::atomic<uint64_t> grp_hit{0}, grp_built{0}, grp_reset{0}, grp_launches{0};
@@ -1267,8 +1283,9 @@ int kidx_ensure(gv_ctx* ctx, Dev* d, size_t used, hipStream_t st) {
 
 // The slots of a pub33 device batch (n items, device AoS) into `out` (n
 // words): k_kidx_find on st, then one 4-byte read-back of the miss count and
-// a sync -- what group_keys pays for its key count.  *all: every key was found.
-int kidx_lookup(gv_ctx* ctx, Dev* d, size_t n, const uint8_t* pub, uint32_t* out, hipStream_t st, bool* all) {
+// a sync -- what group_keys pays for its key count.  *nmiss: the items whose
+// key was not found (their word of `out` is GV_KIDX_EMPTY).
+int kidx_lookup(gv_ctx* ctx, Dev* d, size_t n, const uint8_t* pub, uint32_t* out, hipStream_t st, size_t* nmiss) {
   uint32_t* miss = d->kidx_cnt + 16;
   CK(hipMemsetAsync(miss, 0, 4, st));
   const bool timed = ctx->opt.time_kernels;
@@ -1283,13 +1300,55 @@ int kidx_lookup(gv_ctx* ctx, Dev* d, size_t n, const uint8_t* pub, uint32_t* out
   if (timed) CK(hipEventRecord(d->kidx_ev[1], st));
   CK(hipMemcpyAsync(d->kidx_h, miss, 4, hipMemcpyDeviceToHost, st));
   CK(hipStreamSynchronize(st));
-  *all = *d->kidx_h == 0;
+  *nmiss = *d->kidx_h;
   if (timed) {
     float ms = 0;
     CK(hipEventElapsedTime(&ms, d->kidx_ev[0], d->kidx_ev[1]));
     ctx->kidx_find_ns = (uint64_t)(ms * 1e6f);
   }
   return GV_OK;
+}
+
+// The sub-batch buffers and the scratch set of a call on set s that splits
+// `miss` non-resident items off (option "keys_index_split"): false when the
+// HBM budget or hipMalloc refuses them -- the call then falls through whole.
+// The buffers grow by kidx_split_rows; the scratch set as launch() will ask.
+size_t grow_items(const gv_ctx* ctx, size_t C);
+bool miss_ensure(gv_ctx* ctx, Dev* d, Set* s, size_t miss) {
+  if (!s->miss_done && hipEventCreateWithFlags(&s->miss_done, hipEventDisableTiming) != hipSuccess) {
+    (void)hipGetLastError();
+    s->miss_done = nullptr;
+    return false;
+  }
+  if (!s->miss_set) {
+    Set* m = new Set;
+    if (hipEventCreateWithFlags(&m->last, hipEventDisableTiming) != hipSuccess) {
+      (void)hipGetLastError();
+      delete m;
+      return false;
+    }
+    s->miss_set = m;
+  }
+  const size_t rows = kidx_split_rows(s->miss.cap, miss);
+  if (rows != s->miss.cap) {
+    opt_free(d, s->miss_buf, kidx_split_layout(s->miss.cap).total);
+    s->miss = gvk_split{};
+    const SplitLayout L = kidx_split_layout(rows);
+    if (rows > kMaxItems || !(s->miss_buf = opt_alloc(ctx, d, L.total))) return false;
+    uint8_t* p = (uint8_t*)s->miss_buf;
+    gvk_split& m = s->miss;
+    m.cap = (uint32_t)rows;
+    m.count = (uint32_t*)p;
+    m.idx = (uint32_t*)(p + L.idx);
+    m.pub33 = p + L.pub; m.sig64 = p + L.sig; m.dig32 = p + L.third;
+    m.off = (uint64_t*)(p + L.third); m.len = (uint32_t*)(p + L.len);
+    m.bits = (uint64_t*)(p + L.bits);
+  }
+  if (ensure_cap(s->miss_set, grow_items(ctx, round_up(miss, 256))) != GV_OK) {
+    (void)hipGetLastError();
+    return false;
+  }
+  return true;
 }
 
 // A chunk past the ramp's first size grows its set straight to a whole
@@ -1330,6 +1389,7 @@ struct Items {
   const KeyView* ka = nullptr;                    // a host slice's grouped keys, which kslot then indexes
   bool no_group = false;                          // the per-item pub33 pipeline whatever the keys repeat
   bool index = false;                             // pub33 throughput batches may route through the pubkey index
+  bool quiet = false;                             // no stage events (a split call's sub-batch: the ring describes the main batch)
 };
 // Where the verdicts go: the accept bitmap (device) or, on the sliced
 // small-batch kernels, one byte per item (out8).  st_ecm (pipelined
@@ -1372,13 +1432,28 @@ int launch(gv_ctx* ctx, Dev* d, Set* s, const Items& it, const LaunchOut& out, h
   // index (gv_dev_verify_digests / _msgs, option "keys_index"): a throughput
   // batch whose keys are all resident runs as the keyed call with those slots
   // would -- the slots looked up into the head of the set's Q-table region
-  // (free on the keyed pipeline; plan_sort starts past them).  Any miss: the
-  // batch goes on as without the index.
+  // (free on the keyed pipeline; plan_sort starts past them).  A few misses
+  // (option "keys_index_split", kidx_split_ok): the batch still runs keyed,
+  // its miss lanes (slot GV_KIDX_EMPTY: out of range, answered 0) compacted
+  // into a sub-batch that is verified below and merged in.  Any other miss:
+  // the batch goes on as without the index.
   bool via_index = false;
+  size_t split = 0;                             // the items split off
   if (it.index && it.pub33 && !kslot && n > ctx->opt.lat_max && ctx->keys && kidx_live(ctx, d)) {
-    if ((rc = kidx_lookup(ctx, d, n, it.pub33, s->qtab, st, &via_index))) return rc;
+    size_t nmiss = 0;
+    if ((rc = kidx_lookup(ctx, d, n, it.pub33, s->qtab, st, &nmiss))) return rc;
+    const size_t bound = ctx->opt.keys_index_split;
+    const bool wanted = kidx_split_ok(bound, nmiss, true, true);   // (the buffers are asked for only then)
+    if (kidx_split_ok(bound, nmiss, true, wanted && miss_ensure(ctx, d, s, nmiss))) split = nmiss;
+    via_index = nmiss == 0 || split;
     if (via_index) kslot = s->qtab;
     (via_index ? ctx->kidx_hit : ctx->kidx_miss)++;
+    if (split) {
+      CK(gvk_kidx_split(&s->miss, s->qtab, (uint32_t)n, it.pub33, it.sig64, it.dig32, it.off, it.len, st));
+      ctx->kidx_launches++;
+      ctx->kidx_split_calls++;
+      ctx->kidx_split_items += split;
+    }
   }
   // a host slice's grouped keys (the slots are on the device already:
   // slice_group read the key count back after k_dedupe_map; only k_prep on
@@ -1387,7 +1462,7 @@ int launch(gv_ctx* ctx, Dev* d, Set* s, const Items& it, const LaunchOut& out, h
   const KeyView kv = !kslot ? KeyView() : ka ? *ka : arena_tabs(ctx, d, false, false);
   if (kslot) kv.to_batch(b, kslot);
   hipEvent_t* rs = nullptr;
-  if (ctx->opt.time_kernels) {
+  if (ctx->opt.time_kernels && !it.quiet) {
     rs = d->ring[d->ring_next];
     for (int i = 0; i < 6; ++i)
       if (!rs[i]) CK(hipEventCreate(&rs[i]));
@@ -1407,7 +1482,7 @@ int launch(gv_ctx* ctx, Dev* d, Set* s, const Items& it, const LaunchOut& out, h
     b.st_ecm = out.st_ecm;
     b.ecm_ready = s->ecm_ready;
     b.bits_wait = d->bits_wait;
-    b.bits_done = d->bits_rec;
+    b.bits_done = split ? nullptr : d->bits_rec;   // (a split call: recorded behind the merge, below)
   }
   if (small) {
     // small batch: one fused kernel, several lanes per signature (gv_lat.hip)
@@ -1467,6 +1542,33 @@ int launch(gv_ctx* ctx, Dev* d, Set* s, const Items& it, const LaunchOut& out, h
               : b.gtabf                       ? GV_ROUTE_ITEMF
                                               : GV_ROUTE_PUB33]++;
     CK(gvk_verify(&b, st));
+    if (split) {
+      // the front stream is free again (the ladder runs on st_ecm): the
+      // sub-batch goes under the main ladder as the next call's front kernels
+      // would -- by its 33 key bytes, never grouped (no host sync), the call's
+      // thresholds picking its kernel -- and the ladder stream ORs its accept
+      // bits in behind its own bitmap write, before the event later calls'
+      // bitmap writes wait for and before the set is released
+      const gvk_split& m = s->miss;
+      Items sub;
+      sub.n = split;
+      sub.pub33 = m.pub33; sub.sig64 = m.sig64;
+      if (it.dig32) sub.dig32 = m.dig32;
+      else { sub.blob = it.blob; sub.off = m.off; sub.len = m.len; }
+      sub.no_group = true;
+      sub.quiet = true;
+      LaunchOut so;
+      so.bits = m.bits;
+      if ((rc = launch(ctx, d, s->miss_set, sub, so, st))) return rc;
+      hipStream_t se = pipelined ? out.st_ecm : st;
+      if (se != st) {
+        CK(hipEventRecord(s->miss_done, st));
+        CK(hipStreamWaitEvent(se, s->miss_done, 0));
+      }
+      CK(gvk_bits_merge(&m, (uint32_t)split, (uint32_t)n, out.bits, se));
+      ctx->kidx_launches++;
+      if (pipelined && d->bits_rec) CK(hipEventRecord(d->bits_rec, se));
+    }
   }
   if (rs) {
     d->last = d->ring_next;
@@ -2208,6 +2310,9 @@ void free_set(Set& s) {
   s.gk.free();
   if (s.g_rows) (void)hipFree(s.g_rows);
   if (s.h_count) (void)hipHostFree(s.h_count);
+  if (s.miss_buf) (void)hipFree(s.miss_buf);
+  if (s.miss_done) (void)hipEventDestroy(s.miss_done);
+  if (s.miss_set) { free_set(*s.miss_set); delete s.miss_set; }
   if (s.lad) { (void)hipStreamSynchronize(s.lad); (void)hipStreamDestroy(s.lad); }
   if (s.lad_done) (void)hipEventDestroy(s.lad_done);
   if (s.st) (void)hipStreamDestroy(s.st);
@@ -3660,6 +3765,9 @@ int gv_get_option(gv_ctx* ctx, const char* key, long long* val) {
               {"keys_index_hit", (long long)ctx->kidx_hit.load()},     // pub33 device batches routed keyed
               {"keys_index_miss", (long long)ctx->kidx_miss.load()},   // ... that fell through on a miss
               {"keys_index_launches", (long long)ctx->kidx_launches.load()},   // k_kidx_* launches so far
+              // routed batches whose non-resident items were split off ("keys_index_split"), and those items
+              {"keys_index_split_calls", (long long)ctx->kidx_split_calls.load()},
+              {"keys_index_split_items", (long long)ctx->kidx_split_items.load()},
               {"group_reuse_hit", (long long)ctx->grp_hit.load()},       // grouped keys whose tables were at hand
               {"group_reuse_built", (long long)ctx->grp_built.load()},   // ... and built, by calls with group_reuse on
               {"group_reuse_reset", (long long)ctx->grp_reset.load()},   // caches flushed (full, or another schedule's)

@@ -253,6 +253,14 @@ type GPU struct {
 	// the arena's tables.  Applies to an arena started from slot 0 (default
 	// false, env GV_KEYS_INDEX=1).
 	KeysIndex bool
+	// KeysIndexSplit: a device-resident pub33 batch the index routes may hold
+	// up to this many items whose keys are NOT resident and still run on the
+	// arena's tables -- those items are verified by their key bytes beside it
+	// and merged in (gv_set_option "keys_index_split"); with more, and with 0,
+	// one such item sends the whole batch to the pub33 routes.  Same verdicts
+	// either way (default 0; no environment variable: the server forwards its
+	// keys-index-split with SetOption after "keys_index" and records it here).
+	KeysIndexSplit int
 	// Logger, when set, reports every call that fell back to the CPU.
 	Logger Logger
 

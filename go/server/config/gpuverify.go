@@ -54,6 +54,11 @@ type GPUVerifyConfig struct {
 	// key arena (gv_set_option keys_index; gv_keys_find): device-resident
 	// pub33 batches whose keys are all resident run on the arena's tables.
 	KeysIndex bool `mapstructure:"keys-index"`
+	// KeysIndexSplit: such a batch may hold up to this many items whose keys
+	// are not resident and still run on the arena's tables, those items
+	// verified by key bytes beside it (gv_set_option keys_index_split; 0 =
+	// any such item sends the whole batch to the pub33 routes).
+	KeysIndexSplit int `mapstructure:"keys-index-split"`
 	// CacheEntries: the verdict cache (0 = no cache).
 	CacheEntries int `mapstructure:"cache-entries"`
 	// CheckTxWindowTxs / CheckTxWindow: the concurrent-CheckTx accumulation
@@ -72,7 +77,7 @@ type GPUVerifyConfig struct {
 func DefaultGPUVerifyConfig() GPUVerifyConfig {
 	return GPUVerifyConfig{
 		Enable: false, Devices: "", MaxBatch: 1 << 20, CPUBelow: 4, Keyed: true, KeyLoadMin: 4096,
-		KeyCap: 1 << 22, EdKeyCap: 1 << 16, KeyResident: 0, EdKeyResident: 0, KeysWideQW: 0, EdKeysWide: 0, KeysIndex: false, CacheEntries: 1 << 20,
+		KeyCap: 1 << 22, EdKeyCap: 1 << 16, KeyResident: 0, EdKeyResident: 0, KeysWideQW: 0, EdKeysWide: 0, KeysIndex: false, KeysIndexSplit: 0, CacheEntries: 1 << 20,
 		CheckTxWindowTxs: 64, CheckTxWindow: 200 * time.Microsecond, PreVerifyBlocks: true,
 	}
 }
@@ -111,6 +116,8 @@ func (c GPUVerifyConfig) Validate() error {
 		return fmt.Errorf("gpu-verify.keys-wide-qw must be 0, 9 or 11, got %d", c.KeysWideQW)
 	case c.EdKeysWide != 0 && c.EdKeysWide != 6 && c.EdKeysWide != 8:
 		return fmt.Errorf("gpu-verify.ed-keys-wide must be 0, 6 or 8, got %d", c.EdKeysWide)
+	case c.KeysIndexSplit < 0:
+		return fmt.Errorf("gpu-verify.keys-index-split must be >= 0, got %d", c.KeysIndexSplit)
 	case c.CheckTxWindowTxs < 1 || c.CheckTxWindow < 0:
 		return fmt.Errorf("gpu-verify: bad CheckTx window (%d txs, %v)", c.CheckTxWindowTxs, c.CheckTxWindow)
 	}
@@ -168,6 +175,12 @@ ed-keys-wide = {{ .GPUVerify.EdKeysWide }}
 # resident tables when all their keys are resident.  Taken when the arena next
 # starts from slot 0.
 keys-index = {{ .GPUVerify.KeysIndex }}
+
+# With keys-index: a batch with at most this many signatures whose keys are not
+# resident still runs on the resident tables; those signatures are verified by
+# their key bytes beside it (0 = one such signature sends the whole batch to
+# the per-key route).  Same verdicts either way.
+keys-index-split = {{ .GPUVerify.KeysIndexSplit }}
 
 # Verdict cache entries (0 disables it).
 cache-entries = {{ .GPUVerify.CacheEntries }}

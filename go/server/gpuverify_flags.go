@@ -27,6 +27,7 @@ const (
 	FlagGPUVerifyEdRes    = "gpu-verify.ed-key-resident"
 	FlagGPUVerifyEdWide   = "gpu-verify.ed-keys-wide"
 	FlagGPUVerifyKeysIdx  = "gpu-verify.keys-index"
+	FlagGPUVerifyKeysSplt = "gpu-verify.keys-index-split"
 )
 
 // AddGPUVerifyFlags registers the flags that override app.toml.
@@ -42,9 +43,10 @@ func AddGPUVerifyFlags(cmd *cobra.Command) {
 	cmd.Flags().Int(FlagGPUVerifyEdRes, d.EdKeyResident, "Keep the ed25519 key arena at this many keys (0 = off)")
 	cmd.Flags().Int(FlagGPUVerifyEdWide, d.EdKeysWide, "Wide ed25519 key tables: 0 (off), 6 or 8 radix bits")
 	cmd.Flags().Bool(FlagGPUVerifyKeysIdx, d.KeysIndex, "Device-side pubkey index of the account-key arena")
+	cmd.Flags().Int(FlagGPUVerifyKeysSplt, d.KeysIndexSplit, "Non-resident signatures per batch still verified beside the arena (0 = off)")
 	for _, f := range []string{FlagGPUVerify, FlagGPUVerifyDevices, FlagGPUVerifyMaxBatch, FlagGPUVerifyCPUBelow,
 		FlagGPUVerifyKeyed, FlagGPUVerifyWindow, FlagGPUVerifyResident, FlagGPUVerifyEdRes, FlagGPUVerifyEdWide,
-		FlagGPUVerifyKeysIdx} {
+		FlagGPUVerifyKeysIdx, FlagGPUVerifyKeysSplt} {
 		_ = viper.BindPFlag(f, cmd.Flags().Lookup(f))
 	}
 }
@@ -89,6 +91,13 @@ func NewGPUVerifier(cfg config.GPUVerifyConfig, logger log.Logger) (gv.Verifier,
 			logger.Error("gpu-verify: keys-index not applied", "err", err)
 		} else {
 			g.KeysIndex = true
+		}
+	}
+	if cfg.KeysIndexSplit > 0 {
+		if err := g.SetOption("keys_index_split", int64(cfg.KeysIndexSplit)); err != nil {
+			logger.Error("gpu-verify: keys-index-split not applied", "err", err)
+		} else {
+			g.KeysIndexSplit = cfg.KeysIndexSplit
 		}
 	}
 	g.Logger = logger.With("module", "gpuverify")

@@ -18,6 +18,20 @@ and gv_keys_replace of --replace slots with the option off and on (arenas
 already at capacity: the same kernels, no growth), and k_kidx_find's own time
 over one batch from HIP events ("time_kernels", "keys_index_find_ns").
 
+--miss M[,M...]: instead of the above, the same batch with M of its items
+re-keyed to fresh keys that are NOT resident (valid signatures, at positions
+spread evenly over the batch), per M and per process
+
+  split  by gv_dev_verify_digests, "keys_index" 1, "keys_index_split" M
+         (the resident items on the arena, the M others as a sub-batch)
+  off    the same with "keys_index_split" 0: the whole batch falls through
+         (on the parent's library: its only behaviour)
+
+and, once per process, `resident`: the all-resident batch with "keys_index" 1.
+The summary names the routes taken, the mismatches against construction and,
+per M, whether split's slowest run beats the parent's fastest `off` by more
+than the +-3 % box spread.
+
 Timing as bench.py's timed loop: --warmup calls, a device synchronise, then
 --steps pipelined calls between two host clock reads, the second after a
 device synchronise.  One GPU.  Prints one JSON line per process and a summary.
@@ -130,6 +144,91 @@ def child(args):
     return 1 if any(isinstance(v, dict) and v.get("mismatches") for v in out.values()) else 0
 
 
+def spread(n, m):
+    """m distinct positions spread evenly over n items."""
+    return (np.arange(m, dtype=np.int64) * n) // m
+
+
+def child_miss(args):
+    """One process, one context: `resident`, then per M `split` and `off` (--legacy: `off` alone)."""
+    import bench
+    import gpuverify as gvm
+    w = np.load(args.child)
+    pub, sig, dig, exp = w["pub"], w["sig"], w["dig"], w["exp"]
+    fpub, fsig, fdig = w["fpub"], w["fsig"], w["fdig"]
+    n, nkeys = len(exp), args.keys
+    out = {"lib": "parent" if args.legacy else "this", "items": n, "keys": nkeys}
+    ver = gvm.Verifier([0])
+    try:
+        ver.set_option("keys_index", 1)
+        ver.keys_load(np.ascontiguousarray(pub[:nkeys]))
+        out["keys_index_live"] = ver.get_option("keys_index_live")
+        out["keys_index_left_out"] = ver.get_option("keys_index_left_out")
+        nw = (n + 63) // 64
+        d_pub, d_sig, d_dig = (ver.dev_alloc(a.nbytes) for a in (pub, sig, dig))
+        d_bits = ver.dev_alloc(nw * 8)
+
+        def run(name, want, split):
+            if split is not None:
+                ver.set_option("keys_index_split", split)
+            r0 = ver.route_stats()
+            c0 = {k: ver.get_option("keys_index_" + k) for k in ("hit", "miss")}
+            rate = timed(ver, lambda: ver.dev_verify_digests(0, n, d_pub, d_sig, d_dig, d_bits), args.warmup,
+                         args.steps, n)
+            r1 = ver.route_stats()
+            bits = np.zeros(nw, np.uint64)
+            ver.dev_download(bits, d_bits)
+            out[name] = {"rate": round(rate, 1), "routes": {k: r1[k] - r0[k] for k in r1 if r1[k] != r0[k]},
+                         "hit": ver.get_option("keys_index_hit") - c0["hit"],
+                         "miss": ver.get_option("keys_index_miss") - c0["miss"],
+                         "mismatches": int(np.count_nonzero(bench.unpack_bits(bits, n) != want))}
+
+        for ptr, a in ((d_pub, pub), (d_sig, sig), (d_dig, dig)):
+            ver.dev_upload(ptr, a)
+        run("resident", exp, None)
+        for m in args.miss_list:
+            at = spread(n, m)
+            p2, s2, g2, e2 = pub.copy(), sig.copy(), dig.copy(), exp.copy()
+            p2[at], s2[at], g2[at], e2[at] = fpub[:m], fsig[:m], fdig[:m], 1
+            for ptr, a in ((d_pub, p2), (d_sig, s2), (d_dig, g2)):
+                ver.dev_upload(ptr, a)
+            if not args.legacy:
+                i0 = ver.get_option("keys_index_split_items")
+                run("split_%d" % m, e2, m)
+                out["split_%d" % m]["split_items"] = ver.get_option("keys_index_split_items") - i0
+            run("off_%d" % m, e2, None if args.legacy else 0)
+        for ptr in (d_pub, d_sig, d_dig, d_bits):
+            ver.dev_free(ptr)
+        ver.keys_reset()
+    finally:
+        ver.close()
+    print(json.dumps(out), flush=True)
+    return 1 if any(isinstance(v, dict) and v.get("mismatches") for v in out.values()) else 0
+
+
+def summarise_miss(args, runs):
+    this = [r for r in runs if r["lib"] == "this"]
+    parent = [r for r in runs if r["lib"] == "parent"]
+    rates = lambda rs, k: [r[k]["rate"] for r in rs if k in r]
+    per_m = {}
+    for m in args.miss_list:
+        sp, off, par = rates(this, "split_%d" % m), rates(this, "off_%d" % m), rates(parent, "off_%d" % m)
+        per_m[str(m)] = {"split": sp, "off": off, "parent": par,
+                         "routes_split": next((r["split_%d" % m]["routes"] for r in this), None),
+                         "routes_off": next((r["off_%d" % m]["routes"] for r in this), None),
+                         "split_over_parent": round(float(np.median(sp) / np.median(par)), 4) if par else None,
+                         "off_over_parent": round(float(np.median(off) / np.median(par)), 4) if par else None,
+                         "split_over_resident": round(float(np.median(sp) / np.median(rates(this, "resident"))), 4),
+                         # beats the fall-through by more than the +-3 % box spread
+                         "split_beats_parent": bool(par and min(sp) > 1.03 * max(par))}
+    res, pres = rates(this, "resident"), rates(parent, "resident")
+    return {"items": args.n, "keys": args.keys, "steps": args.steps, "rounds": args.rounds, "unit": "verifies/s",
+            "resident": res, "parent_resident": pres,
+            "resident_over_parent": round(float(np.median(res) / np.median(pres)), 4) if pres else None,
+            "miss": per_m,
+            "mismatches": sum(v["mismatches"] for r in runs for v in r.values() if isinstance(v, dict))}
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--parent-lib", default="", help="libgpuverify.so built from the parent commit (none: no d runs)")
@@ -142,13 +241,17 @@ def main():
     ap.add_argument("--seed", type=int, default=0xCA9)
     ap.add_argument("--threads", type=int, default=16, help="host threads of the workload generator")
     ap.add_argument("--timeout", type=int, default=240, help="seconds per process")
+    ap.add_argument("--miss", default="", help="M[,M...]: batches with M non-resident items, split against fall-through")
     ap.add_argument("--child", default="", help=argparse.SUPPRESS)       # the workload file: run one process's part
     ap.add_argument("--legacy", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
     if args.keys < 1 or args.keys > args.n or not 1 <= args.replace <= args.keys:
         ap.error("1 <= --replace <= --keys <= --n")
+    args.miss_list = [int(x) for x in args.miss.split(",") if x]
+    if any(m < 1 or m > args.n for m in args.miss_list):
+        ap.error("1 <= M <= --n")
     if args.child:
-        return child(args)
+        return child_miss(args) if args.miss_list else child(args)
 
     import bench
     t0 = time.perf_counter()
@@ -157,10 +260,19 @@ def main():
     exp[::8] = 0
     tmp = tempfile.mkdtemp()
     wl = os.path.join(tmp, "workload.npz")
-    np.savez(wl, pub=pub, sig=sig, dig=dig, exp=exp)
+    extra = {}
+    if args.miss_list:                                         # fresh keys (another seed) with valid signatures
+        fpub, fsig, fdig, _ = bench.make_digest_workload(max(args.miss_list), args.seed + 1, max(args.miss_list), 0.0,
+                                                         args.threads)
+        resident = {k.tobytes() for k in pub[:args.keys]}
+        assert not any(k.tobytes() in resident for k in fpub)
+        extra = dict(fpub=fpub, fsig=fsig, fdig=fdig)
+    np.savez(wl, pub=pub, sig=sig, dig=dig, exp=exp, **extra)
     t_work = time.perf_counter() - t0
     base = [sys.executable, os.path.abspath(__file__), "--child", wl, "--keys", str(args.keys), "--replace",
             str(args.replace), "--steps", str(args.steps), "--warmup", str(args.warmup)]
+    if args.miss_list:
+        base += ["--miss", args.miss]
     runs, rc = [], 0
     try:
         for _ in range(args.rounds):
@@ -184,6 +296,9 @@ def main():
     finally:
         os.remove(wl)
         os.rmdir(tmp)
+    if args.miss_list:
+        print(json.dumps(summarise_miss(args, runs)), flush=True)
+        return rc
     rates = {m: [r[m]["rate"] for r in runs if m in r] for m in "abcd"}
     this = [r for r in runs if r["lib"] == "this"]
     summary = {"items": args.n, "keys": args.keys, "steps": args.steps, "rounds": args.rounds, "unit": "verifies/s",
