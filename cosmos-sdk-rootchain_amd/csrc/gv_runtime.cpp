@@ -3787,11 +3787,14 @@ int gv_get_option(gv_ctx* ctx, const char* key, long long* val) {
   // (0: no slot has wide tables) and its groups; its pubkey index -- whether
   // it covers the arena, the slots in it, the keys its probe bound left out,
   // its table words; its wide ed25519 arena as gv_ed_keys_load left it -- its
-  // radix bits (0: no slot has wide tables) and the slots that have them
+  // radix bits (0: no slot has wide tables) and the slots that have them;
+  // whether it holds a built radix-2^16 comb table of B ("ed_btab16_live":
+  // 0 also when the build failed and k_ed_keyed adds [s]B from the radix-256
+  // table; reading it never builds the table)
   const bool ed = !strcmp(key, "ed_kw_rb") || !strcmp(key, "ed_kw_keys");
   static const char* const kDev[] = {"kw_arena_qw", "kw_arena_ng", "keys_index_live", "keys_index_keys",
                                      "keys_index_left_out", "keys_index_words", "group_reuse_rows", "group_layout",
-                                     "hbm_optional_bytes"};
+                                     "hbm_optional_bytes", "ed_btab16_live"};
   if (!ed && std::none_of(std::begin(kDev), std::end(kDev), [&](const char* k) { return !strcmp(key, k); }))
     return GV_EINVAL;
   if (ctx->devs.empty()) return GV_EINVAL;
@@ -3806,6 +3809,7 @@ int gv_get_option(gv_ctx* ctx, const char* key, long long* val) {
          // bytes of optional tables the HBM budget counts on the device
          : !strcmp(key, "group_layout")        ? (long long)d->group_layout
          : !strcmp(key, "hbm_optional_bytes")  ? (long long)d->opt_bytes
+         : !strcmp(key, "ed_btab16_live")      ? (long long)(d->edtab16 ? 1 : 0)
          : !strcmp(key, "kw_arena_qw")         ? (kw ? d->kw.lay.qw() : 0)
          : !strcmp(key, "kw_arena_ng")         ? (kw ? (int)d->kw.lay.ng : 0)
          : !strcmp(key, "keys_index_live")     ? (long long)kidx_live(ctx, d)

@@ -296,6 +296,11 @@ class Verifier:
         _check(self._L.gv_set_option(self._ctx, key.encode(), int(val)), f"gv_set_option({key})")
 
     def get_option(self, key: str) -> int:
+        """gv_get_option: a readable tunable or a read-only live value (include/gpuverify.h lists
+        them), e.g. "ed_kw_rb" (the wide ed25519 arena's radix bits), "ed_keyed_wide" (keyed
+        ed25519 batches on wide tables) or "ed_btab16_live" (1 when the first device holds a
+        built radix-2^16 comb table of B; 0 before the first call that uses it, or when its
+        allocation or build failed and [s]B comes from the radix-256 table; never builds it)."""
         v = ctypes.c_longlong(0)
         _check(self._L.gv_get_option(self._ctx, key.encode(), ctypes.byref(v)), f"gv_get_option({key})")
         return int(v.value)

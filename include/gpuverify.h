@@ -514,7 +514,11 @@ int gv_ed_keys_wide_point(gv_ctx* ctx, size_t n, const uint32_t* slots, uint32_t
  * "ed_btab16" (0/1: k_ed_keyed -- cached keys past "ed_lat_max" and grouped
  * keys -- and the per-item throughput kernels add [s]B from a radix-2^16 comb table of B, j * 65536^w * B for
  * w < 16 and j <= 2^15 (56.6 MB per device, built on first use): 16
- * additions instead of 32; same verdicts; default 1, env GV_ED_BTAB16),
+ * additions instead of 32; same verdicts; default 1, env GV_ED_BTAB16; when
+ * the table's allocation or build fails the same kernels add [s]B from the
+ * radix-256 table, and gv_get_option "ed_btab16_live" (read only) tells:
+ * 1 when the first device holds a built table, else 0 -- reading it never
+ * builds the table),
  * "sort_keys" (0/1: keyed throughput batches on the 4-group ladder -- cached
  * slots, grouped keys -- run their lanes in slot order: a counting sort by
  * slot, the signature rows read in that order, the accept bits gathered back
@@ -640,6 +644,9 @@ int gv_set_option(gv_ctx* ctx, const char* key, long long val);
  * bits of the first device's wide ed25519 arena (0: no slot has wide tables),
  * "ed_kw_keys", the slots that have them, and "ed_keyed_wide", the keyed
  * ed25519 batches (host calls: chunks) that ran on wide tables since gv_open,
+ * and (read only) "ed_btab16_live" (1: the first device holds a built
+ * radix-2^16 comb table of B, see "ed_btab16"; 0: not built yet, or its
+ * allocation or build failed and [s]B comes from the radix-256 table),
  * and "keys_index" with (read only) "keys_index_live" (1: the first device's
  * index covers the arena as it stands), "keys_index_keys" (the slots in it),
  * "keys_index_left_out" (keys the probe bound kept out of the table),

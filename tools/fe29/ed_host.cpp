@@ -65,4 +65,15 @@ int edh_verify(const u32* pw, const u32* sw, const uint8_t* msg, u32 len, const 
   std::vector<u32> tab(ED_ATAB_WORDS);
   return ed_verify_item(pw, sw, [&](u32 i) { return (u32)msg[i]; }, len, tab.data(), 1, btab);
 }
+// the radix-2^16 comb table of B: one entry, and a verification whose [s]B
+// comes from it (ed_add_sb16) -- btab16 holds ED_BTAB16_WORDS words, of which
+// the caller may have filled only the entries it expects to be read
+void edh_btab16_entry(int w, int j, u32* out) { ed_btab16_entry(out, w, j); }
+int edh_verify16(const u32* pw, const u32* sw, const uint8_t* msg, u32 len, const u32* btab, const u32* btab16) {
+  std::vector<u32> tab(ED_ATAB_WORDS);
+  u32 h[8];
+  const bool pre_ok = ed_prep_item(pw, sw, [&](u32 i) { return (u32)msg[i]; }, len, tab.data(), 1, h);
+  const bool r_ok = ed_ladder_check(h, sw + 8, tab.data(), 1, btab, sw, btab16);
+  return pre_ok && r_ok;
+}
 }
