@@ -434,8 +434,8 @@ hipError_t gvk_keys_build_rows_kg(uint32_t n, uint32_t C, const uint32_t* in_x, 
                                   uint32_t kC, uint32_t* kok, uint32_t* kqt2, uint32_t* kzq2, int ng, hipStream_t st);
 hipError_t gvk_verify_lat(const gvk_lat* b, hipStream_t st);
 hipError_t gvk_verify_lat16(const gvk_lat* b, hipStream_t st);
-hipError_t gvk_verify_lat_sl(const gvk_lat* b, hipStream_t st);
-hipError_t gvk_verify_lat16_sl(const gvk_lat* b, hipStream_t st); // keyed, limb-sliced (one signature per block)   // pub33, limb-sliced (one signature per block)
+hipError_t gvk_verify_lat_sl(const gvk_lat* b, hipStream_t st);    // pub33, limb-sliced (one signature per block)
+hipError_t gvk_verify_lat16_sl(const gvk_lat* b, hipStream_t st);  // keyed, limb-sliced (one signature per block)
 hipError_t gvk_sha256(const uint8_t* blob, const uint64_t* off, const uint32_t* len, uint32_t n, uint32_t C,
                       uint32_t* e, hipStream_t st);
 hipError_t gvk_verify(const gvk_batch* b, hipStream_t st);

@@ -45,17 +45,17 @@ static_assert(F29_NCH == 2, "gv_lat.hip is built with -DF29_NCH=2");
 
 namespace gv {
 
-// Q digit width of a shared-state type: kQ6 (the kn arena's 6-bit windows),
-// kKW (the wide arena's GV_KW_QW-bit windows), else k4's 5-bit ones.
+// Q digit width of a shared-state type: its own kQW / kQWIN where it names
+// them (Lat16RowsShared: the kn and kw arenas), else k4's 5-bit windows.
 template <class SH, class = void>
 struct lat_q_width {
-  static constexpr int qw = SH::kQ6 ? GV_K6_QW : GV_QW;
-  static constexpr int qwin = SH::kQ6 ? GV_K6_QWIN : GV_QWIN;
+  static constexpr int qw = GV_QW;
+  static constexpr int qwin = GV_QWIN;
 };
 template <class SH>
-struct lat_q_width<SH, std::void_t<decltype(SH::kKW)>> {
-  static constexpr int qw = GV_KW_QW;
-  static constexpr int qwin = GV_KW_QWIN;
+struct lat_q_width<SH, std::void_t<decltype(SH::kQW)>> {
+  static constexpr int qw = SH::kQW;
+  static constexpr int qwin = SH::kQWIN;
 };
 
 // GV_LAT_TRACE (A/B builds only): per block, wall-clock stamps (100 MHz) of
@@ -89,7 +89,6 @@ static __constant__ const u32 kLP[8] = {0xFFFFFC2Fu, 0xFFFFFFFEu, 0xFFFFFFFFu, 0
 struct LatShared {
   static constexpr bool kG5 = false;         // G digits: 20-bit windows (dg)
   static constexpr bool kG24 = false;
-  static constexpr bool kQ6 = false;          // Q digits: 5-bit windows (6-bit: the kn arena)
   u32 qtab[GV_LAT_SIGS][2][GV_QTAB_N][18];  // Q, lambda*Q entries: x, y raw 29-bit limbs (effective affine)
   u32 ratio[64][GV_QTAB_N - 1][9];          // per-lane Z-ratio scratch of the table build (raw limbs)
   u32 dq[GV_LAT_SIGS][GV_QWIN];             // packed int16 Q / lambda*Q digits per window
@@ -121,6 +120,51 @@ GV_DEV void lds_put_ent(u32* e, const fe29& x, const fe29& y) {
 GV_DEV void lds_get_ent(fe29& x, fe29& y, const u32* e) {
 #pragma unroll
   for (int i = 0; i < 9; ++i) { x.n[i] = e[i]; y.n[i] = e[9 + i]; }
+}
+
+// beta (lambda (x, y) = (beta x, y)) as a field element of each layer
+GV_DEV void f29_beta(fe29& beta) {
+  u32 w[8];
+#pragma unroll
+  for (int i = 0; i < 8; ++i) w[i] = kLBeta[i];
+  f29_from_words(beta, w);
+}
+GV_DEV u32 fsl_beta(const fslk& k) {
+  u32 w[8];
+#pragma unroll
+  for (int i = 0; i < 8; ++i) w[i] = kLBeta[i];
+  return fsl_from_words(w, k);
+}
+
+// A G table entry (16 affine words: x, y) and a key arena entry
+// (GV_QENT_WORDS: nine raw 29-bit limbs of x, nine of y) into one lane.
+GV_DEV void lat_load_gent29(fe29& x, fe29& y, const u32* e) {
+  const uint4* p = (const uint4*)e;
+  const uint4 a = p[0], b = p[1], c = p[2], d = p[3];
+  const u32 wx[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
+  const u32 wy[8] = {c.x, c.y, c.z, c.w, d.x, d.y, d.z, d.w};
+  f29_from_words(x, wx);
+  f29_from_words(y, wy);
+}
+GV_DEV void lat_load_qent29(fe29& x, fe29& y, const u32* ent) {
+  const uint4* p = (const uint4*)ent;
+  const uint4 a = p[0], b = p[1], c = p[2], d = p[3], e = p[4];
+  x.n[0] = a.x; x.n[1] = a.y; x.n[2] = a.z; x.n[3] = a.w;
+  x.n[4] = b.x; x.n[5] = b.y; x.n[6] = b.z; x.n[7] = b.w;
+  x.n[8] = c.x; y.n[0] = c.y; y.n[1] = c.z; y.n[2] = c.w;
+  y.n[3] = d.x; y.n[4] = d.y; y.n[5] = d.z; y.n[6] = d.w;
+  y.n[7] = e.x; y.n[8] = e.y;
+}
+
+// The arena slot a keyed item reads and its key verdict: a slot past kcount
+// reads slot 0 (always in the arena) and fails, as does a key rejected at load
+// (kok 0).  Written out in k_verify_lat16 and k_verify_lat16_sl, where the helper
+// changes the register allocation: a fix here goes there too.
+GV_DEV u32 lat_keyed_slot(bool& ok, u32 sl, const u32* kok, u32 kcount) {
+  ok = sl < kcount;
+  if (!ok) sl = 0;
+  ok = ok && kok[sl] != 0u;
+  return sl;
 }
 
 // Wave 0 prep for one signature (all four lanes of it compute; slot 0 stores).
@@ -220,12 +264,7 @@ GV_DEV void lat_pubkey_and_tables(LatShared& sh, int sig, int slot, bool live, c
   // above (same wave, earlier instructions: LDS executes one wave's operations
   // in order); the lambda*Q entry (beta*x, y) is written alongside.
   fe29 acc, beta;
-  {
-    u32 w[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) w[i] = kLBeta[i];
-    f29_from_words(beta, w);
-  }
+  f29_beta(beta);
 #if GV_LAT_SPLITBP
   // (1) the suffix products acc_m = prod_{k=m..15} ratio_k, m = 15..2, on every
   // lane alike; slot 0 overwrites its ratio scratch with them (read back by the
@@ -313,27 +352,14 @@ GV_DEV void lat_pubkey_and_tables(LatShared& sh, int sig, int slot, bool live, c
 // entries k, k+4, k+8, k+12 and forms their lambda*Q entries (beta*x, y).
 GV_DEV void lat_keyed_tables(LatShared& sh, int sig, int slot, bool live, u32 kslot, const u32* kqt,
                              const u32* kzq, const u32* kok, u32 kC, u32 kcount) {
-  u32 sl = live ? kslot : 0xFFFFFFFFu;
-  bool ok = sl < kcount;
-  if (!ok) sl = 0;                                    // the arena always holds slot 0's memory
-  ok = ok && kok[sl] != 0u;
+  bool ok;
+  const u32 sl = lat_keyed_slot(ok, live ? kslot : 0xFFFFFFFFu, kok, kcount);
   fe29 beta;
-  {
-    u32 w[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) w[i] = kLBeta[i];
-    f29_from_words(beta, w);
-  }
+  f29_beta(beta);
 #pragma unroll 1
   for (int m = slot; m < GV_QTAB_N; m += 4) {
-    const uint4* p = (const uint4*)(kqt + ((size_t)sl * GV_QTAB_N + m) * GV_QENT_WORDS);
-    const uint4 a = p[0], b = p[1], c = p[2], d = p[3], e = p[4];
     fe29 x, y, t;
-    x.n[0] = a.x; x.n[1] = a.y; x.n[2] = a.z; x.n[3] = a.w;
-    x.n[4] = b.x; x.n[5] = b.y; x.n[6] = b.z; x.n[7] = b.w;
-    x.n[8] = c.x; y.n[0] = c.y; y.n[1] = c.z; y.n[2] = c.w;
-    y.n[3] = d.x; y.n[4] = d.y; y.n[5] = d.z; y.n[6] = d.w;
-    y.n[7] = e.x; y.n[8] = e.y;
+    lat_load_qent29(x, y, kqt + ((size_t)sl * GV_QTAB_N + m) * GV_QENT_WORDS);
     lds_put_ent(sh.qtab[sig][0][m], x, y);
     f29_mul(t, x, beta);
     lds_put_ent(sh.qtab[sig][1][m], t, y);
@@ -349,7 +375,6 @@ GV_DEV void lat_keyed_tables(LatShared& sh, int sig, int slot, bool live, u32 ks
 struct Lat16Shared {
   static constexpr bool kG5 = true;          // G digits: 5-bit windows like Q (dg5)
   static constexpr bool kG24 = false;
-  static constexpr bool kQ6 = false;          // Q digits: 5-bit windows (6-bit: the kn arena)
   u32 dq[GV_LAT16_SIGS][GV_QWIN];            // packed int16 Q / lambda*Q digits per window
   u32 dg5[GV_LAT16_SIGS][GV_QWIN];           // packed int16 G / lambda*G digits per window
   u32 r[GV_LAT16_SIGS][8];
@@ -472,6 +497,43 @@ GV_DEV void lat_scalars(SH& sh, int sig, bool live, const uint8_t* sig64, const 
   });
 }
 
+// The prologue of the keyed one-signature-per-block kernels (256 threads,
+// every thread of the block calls this): wave 0 runs the scalar chain; on the
+// message path wave 1 hashes the sign bytes meanwhile and hands the digest
+// over through sh.eh.  Ends with the block barrier that publishes the digits.
+//
+// Barriers: b.msg_len is a kernel argument, so the whole block takes the same
+// path.  Message path: wave 0 reaches one barrier inside get_e (which
+// lat_scalars_e calls exactly once, outside any branch, after s^-1) and the
+// closing one; waves 1..3 reach the one after the hash (waves 2, 3 go straight
+// to it) and the closing one -- two each.  Digest path: nobody waits inside,
+// every thread reaches the closing barrier only -- one each.
+template <class SH>
+GV_DEV void lat_keyed_scalars(SH& sh, const gvk_lat& b, u32 gi) {
+  if (b.msg_len) {
+    if (threadIdx.x < 64) {
+      lat_scalars_e<true>(sh, 0, true, b.sig64 + (size_t)gi * 64u, [&](u32 e[8]) {
+        __syncthreads();
+#pragma unroll
+        for (int i = 0; i < 8; ++i) e[i] = sh.eh[7 - i];
+      });
+    } else {
+      if (threadIdx.x < 128) {
+        u32 eh[8];
+        sha256_msg_wave(eh, b.msg_blob + b.msg_off[gi], b.msg_len[gi]);
+        if (threadIdx.x == 64) {
+#pragma unroll
+          for (int i = 0; i < 8; ++i) sh.eh[i] = eh[i];
+        }
+      }
+      __syncthreads();
+    }
+  } else if (threadIdx.x < 64) {                        // wave 0: the scalar chain, whole wave
+    lat_scalars<true>(sh, 0, true, b.sig64 + (size_t)gi * 64u, b.dig32 + (size_t)gi * 32u, nullptr, b.C, gi);
+  }
+  __syncthreads();
+}
+
 GV_DEV void shfl_xor_gej(gej29& o, bool& oinf, const gej29& a, bool ainf, int m) {
 #pragma unroll
   for (int i = 0; i < 9; ++i) {
@@ -527,6 +589,35 @@ GV_DEV void lat_add_affine(gej29& acc, bool& inf, const fe29& x, const fe29& y) 
 #endif
 }
 
+// The final check (as k_ecmult), inversion-free: x(R) mod n == r, that is X == r Z^2, or (r + n) Z^2
+// when r < p - n (fl bit 1).  fl: the scalar chain's flags (sh.oks), r: its words, key_ok: the key's verdict.
+GV_DEV bool lat_final29(u32 fl, const u32* r, const gej29 acc, bool inf, bool key_ok) {
+  const bool ok = (fl & 1u) && key_ok && !inf;
+  fe29 zz, rf, t;
+  f29_sqr(zz, acc.z);
+  u32 rw[8], X[8], tw[8];
+#pragma unroll
+  for (int i = 0; i < 8; ++i) rw[i] = r[i];
+  f29_from_words(rf, rw);
+  f29_mul(t, rf, zz);
+  f29_to_words(X, acc.x);
+  f29_to_words(tw, t);
+  bool eq = true;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) eq &= (X[i] == tw[i]);
+  if (!eq && (fl & 2u)) {
+    u32 rn[8], c = 0;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) rn[i] = __builtin_addc(rw[i], kN[i], c, &c);
+    f29_from_words(rf, rn);
+    f29_mul(t, rf, zz);
+    f29_to_words(tw, t);
+    eq = true;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) eq &= (X[i] == tw[i]);
+  }
+  return ok && eq;
+}
 
 // One block = GV_LAT_SIGS signatures, 128 threads.  Inputs: AoS bytes as in
 // gv_verify_digests; e from dig32 (digest path) or from the SoA rows e_soa
@@ -582,12 +673,7 @@ __global__ __launch_bounds__(128) void k_verify_lat(const u32* gtab, const uint8
       if (slot < 2) {
         lds_get_ent(x, y, sh.qtab[sig][slot][e]);
       } else {
-        const uint4* p = (const uint4*)(gtab + ((size_t)(slot == 3 ? GV_GTAB_N : 0) + e) * 16);
-        uint4 a = p[0], b = p[1], c = p[2], dd = p[3];
-        u32 wx[8] = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-        u32 wy[8] = {c.x, c.y, c.z, c.w, dd.x, dd.y, dd.z, dd.w};
-        f29_from_words(x, wx);
-        f29_from_words(y, wy);
+        lat_load_gent29(x, y, gtab + ((size_t)(slot == 3 ? GV_GTAB_N : 0) + e) * 16);
       }
       if (d < 0) f29_neg<1>(y, y);
       // Q slots live on the isomorphic curve of the shared table Z, G slots on
@@ -617,32 +703,7 @@ __global__ __launch_bounds__(128) void k_verify_lat(const u32* gtab, const uint8
 
   LAT_STAMP(5);
   // ---- final check (as k_ecmult): x(R) mod n == r, without inversion
-  const u32 fl = sh.oks[sig];
-  bool ok = (fl & 1u) && sh.okp[sig] && !inf;
-  fe29 zz, rf, t;
-  f29_sqr(zz, acc.z);
-  u32 rw[8], X[8], tw[8];
-#pragma unroll
-  for (int i = 0; i < 8; ++i) rw[i] = sh.r[sig][i];
-  f29_from_words(rf, rw);
-  f29_mul(t, rf, zz);
-  f29_to_words(X, acc.x);
-  f29_to_words(tw, t);
-  bool eq = true;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) eq &= (X[i] == tw[i]);
-  if (!eq && (fl & 2u)) {
-    u32 rn[8], c = 0;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) rn[i] = __builtin_addc(rw[i], kN[i], c, &c);
-    f29_from_words(rf, rn);
-    f29_mul(t, rf, zz);
-    f29_to_words(tw, t);
-    eq = true;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) eq &= (X[i] == tw[i]);
-  }
-  ok &= eq;
+  const bool ok = lat_final29(sh.oks[sig], sh.r[sig], acc, inf, sh.okp[sig] != 0u);
   const uint64_t m = __ballot(ok && slot == 0);
   if (lane == 0) {
     u32 b16 = 0;
@@ -675,7 +736,7 @@ __global__ __launch_bounds__(128) void k_verify_lat16(const gvk_lat b) {
   const u32 gi = blockIdx.x * GV_LAT16_SIGS + sig;
   const bool live = gi < b.n;
   const u32 gs = live ? gi : 0u;
-  u32 sl = live ? b.kslot[gs] : 0xFFFFFFFFu;
+  u32 sl = live ? b.kslot[gs] : 0xFFFFFFFFu;            // lat_keyed_slot, written out (as in k_verify_lat16_sl)
   bool kok = sl < b.kcount;
   if (!kok) sl = 0;                                     // the arena always holds slot 0's memory
   kok = kok && b.kok[sl] != 0u;
@@ -687,12 +748,7 @@ __global__ __launch_bounds__(128) void k_verify_lat16(const gvk_lat b) {
   const int part = (int)(j & 3u), grp = (int)(j >> 2);
   const int w_lo = kL16Win[grp], w_hi = kL16Win[grp + 1] - 1;
   fe29 beta;
-  {
-    u32 w[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) w[i] = kLBeta[i];
-    f29_from_words(beta, w);
-  }
+  f29_beta(beta);
   const u32* qrow = grp == 0 ? b.kqt + (size_t)sl * GV_QTAB_N * GV_QENT_WORDS
                              : b.kqt2 + ((size_t)sl * GV_KEY2_TABLES + (grp - 1)) * GV_QTAB_N * GV_QENT_WORDS;
   const u32* grow = b.glat + (size_t)(grp * 2 + (part & 1)) * GV_QTAB_N * 16;
@@ -711,21 +767,10 @@ __global__ __launch_bounds__(128) void k_verify_lat16(const gvk_lat b) {
       const u32 e = (u32)((d < 0 ? -d : d) - 1);
       fe29 x, y;
       if (part < 2) {                                   // Q / lambda Q: arena row, 29-bit limbs
-        const uint4* p = (const uint4*)(qrow + (size_t)e * GV_QENT_WORDS);
-        const uint4 a = p[0], bb = p[1], c = p[2], dd = p[3], ee = p[4];
-        x.n[0] = a.x; x.n[1] = a.y; x.n[2] = a.z; x.n[3] = a.w;
-        x.n[4] = bb.x; x.n[5] = bb.y; x.n[6] = bb.z; x.n[7] = bb.w;
-        x.n[8] = c.x; y.n[0] = c.y; y.n[1] = c.z; y.n[2] = c.w;
-        y.n[3] = dd.x; y.n[4] = dd.y; y.n[5] = dd.z; y.n[6] = dd.w;
-        y.n[7] = ee.x; y.n[8] = ee.y;
+        lat_load_qent29(x, y, qrow + (size_t)e * GV_QENT_WORDS);
         if (part == 1) f29_mul(x, x, beta);             // lambda Q = (beta x, y), same Z
       } else {                                          // G / lambda G: affine words
-        const uint4* p = (const uint4*)(grow + (size_t)e * 16);
-        const uint4 a = p[0], bb = p[1], c = p[2], dd = p[3];
-        u32 wx[8] = {a.x, a.y, a.z, a.w, bb.x, bb.y, bb.z, bb.w};
-        u32 wy[8] = {c.x, c.y, c.z, c.w, dd.x, dd.y, dd.z, dd.w};
-        f29_from_words(x, wx);
-        f29_from_words(y, wy);
+        lat_load_gent29(x, y, grow + (size_t)e * 16);
       }
       if (d < 0) f29_neg<1>(y, y);
       lat_add_affine(acc, inf, x, y);
@@ -748,34 +793,7 @@ __global__ __launch_bounds__(128) void k_verify_lat16(const gvk_lat b) {
     shfl_xor_gej(other, oinf, acc, inf, m);
     gej29_add_gej(acc, inf, acc, inf, other, oinf);
   }
-  if (j == 0) {
-    const u32 fl = sh.oks[sig];
-    bool ok = (fl & 1u) && kok && !inf;
-    fe29 zz, rf, t;
-    f29_sqr(zz, acc.z);
-    u32 rw[8], X[8], tw[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) rw[i] = sh.r[sig][i];
-    f29_from_words(rf, rw);
-    f29_mul(t, rf, zz);
-    f29_to_words(X, acc.x);
-    f29_to_words(tw, t);
-    bool eq = true;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) eq &= (X[i] == tw[i]);
-    if (!eq && (fl & 2u)) {
-      u32 rn[8], c = 0;
-#pragma unroll
-      for (int i = 0; i < 8; ++i) rn[i] = __builtin_addc(rw[i], kN[i], c, &c);
-      f29_from_words(rf, rn);
-      f29_mul(t, rf, zz);
-      f29_to_words(tw, t);
-      eq = true;
-#pragma unroll
-      for (int i = 0; i < 8; ++i) eq &= (X[i] == tw[i]);
-    }
-    sh.res[sig] = (ok && eq) ? 1u : 0u;
-  }
+  if (j == 0) sh.res[sig] = lat_final29(sh.oks[sig], sh.r[sig], acc, inf, kok) ? 1u : 0u;
   __syncthreads();
   if (tid == 0) {
     u32 b8 = 0;
@@ -804,7 +822,6 @@ __global__ __launch_bounds__(128) void k_verify_lat16(const gvk_lat b) {
 struct LatSlShared {
   static constexpr bool kG5 = false;         // G digits: 20-bit windows (dg)
   static constexpr bool kG24 = false;
-  static constexpr bool kQ6 = false;          // Q digits: 5-bit windows (6-bit: the kn arena)
   u32 qtab[2][GV_QTAB_N][18];               // Q, lambda*Q entries: x, y sliced limbs (effective affine)
   u32 ratio[GV_QTAB_N - 1][9];              // Z ratios, then their suffix products
   u32 dq[1][GV_QWIN];
@@ -909,13 +926,7 @@ GV_DEV void lat_sl_tables(SH& sh, u32 qx, u32 qy, const fslk& k) {
     if (st) sh.ratio[m - 2][L] = acc;
   }
   wave_lds_sync();
-  u32 beta;
-  {
-    u32 w[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) w[i] = kLBeta[i];
-    beta = fsl_from_words(w, k);
-  }
+  const u32 beta = fsl_beta(k);
 #pragma unroll 1
   for (int j = 0; j < GV_QTAB_N / 4; ++j) {
     const int e = 4 * j + (int)row;
@@ -949,6 +960,83 @@ GV_DEV void lat_sl_prep(SH& sh, const gvk_lat& b, u32 gi, const fslk& k) {
   LAT_STAMP(2);                                         // trace builds: tables done
 }
 
+// A += the affine point (x, y) of the row's curve (sliced limbs, y < 2^30.1);
+// A may be infinity.  gj4_add_affine is the row-parallel sibling.
+GV_DEV void gjsl_set_or_add(gjsl& A, bool& inf, u32 x, u32 y, const fslk& k) {
+  if (inf) {
+    A.x = x; A.y = fsl_norm(y, k); A.z = k.L == 0u ? 1u : 0u;
+    inf = false;
+  } else {
+    gjsl_add_scaled(A, inf, x, y, A.z, k);
+  }
+}
+
+// The sum of a wave's four rows (points of the real curve), in every row:
+// two rounds of complete additions across the rows.
+GV_DEV void gjsl_rows_sum(gjsl& A, bool& inf, const fslk& k) {
+#pragma unroll 1
+  for (int m = 16; m < 64; m <<= 1) {
+    gjsl O;
+    O.x = (u32)__shfl_xor((int)A.x, m, 64);
+    O.y = (u32)__shfl_xor((int)A.y, m, 64);
+    O.z = (u32)__shfl_xor((int)A.z, m, 64);
+    const bool oinf = __shfl_xor((int)inf, m, 64) != 0;
+    gjsl_add_gej(A, inf, A, inf, O, oinf, k);
+  }
+}
+
+// A row's point to / from an LDS triple of sliced elements and its flag
+// (inf by reference: by value, k_verify_lat_sl4's ladder loop gains mask moves)
+GV_DEV void lds_put_pt(u32 (&pt)[3][16], u32& pinf, const gjsl& A, const bool& inf, const fslk& k) {
+  if (k.L < 9u) { pt[0][k.L] = A.x; pt[1][k.L] = A.y; pt[2][k.L] = A.z; }
+  if (k.L == 0u) pinf = inf ? 1u : 0u;
+}
+GV_DEV void lds_get_pt(gjsl& A, bool& inf, const u32 (&pt)[3][16], const u32& pinf, const fslk& k) {
+  const bool lo = k.L < 9u;
+  A.x = lo ? pt[0][k.L] : 0u;
+  A.y = lo ? pt[1][k.L] : 0u;
+  A.z = lo ? pt[2][k.L] : 0u;
+  inf = pinf != 0u;
+}
+
+// A.z *= Z of the key tables' curve (kzq / kzq2 row: 8 words of stride kC): back to the real curve
+GV_DEV void lat_sl_lift(gjsl& A, const u32* zrow, u32 kC, u32 sl, const fslk& k) {
+  u32 w[8];
+#pragma unroll
+  for (int i = 0; i < 8; ++i) w[i] = zrow[(size_t)i * kC + sl];
+  A.z = fsl_mul(A.z, fsl_from_words(w, k), k);
+}
+
+// lat_final29 on a sliced sum (A, inf) in wave 0, and the verdict write:
+// thread 0 writes out8[gi] or sets the bitmap bit (zeroed by the launcher).
+GV_DEV void lat_sl_final(const gvk_lat& b, u32 gi, u32 fl, const u32* r, const gjsl& A, bool inf, bool key_ok,
+                         const fslk& k) {
+  bool okv = (fl & 1u) && key_ok && !inf;
+  u32 rw[8], X[8], T[8];
+#pragma unroll
+  for (int i = 0; i < 8; ++i) rw[i] = r[i];
+  const u32 zz = fsl_sqr(A.z, k);
+  fsl_to_words(X, A.x);
+  fsl_to_words(T, fsl_mul(fsl_from_words(rw, k), zz, k));
+  bool eq = true;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) eq &= (X[i] == T[i]);
+  if (!eq && (fl & 2u)) {
+    u32 rn[8], c = 0;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) rn[i] = __builtin_addc(rw[i], kN[i], c, &c);
+    fsl_to_words(T, fsl_mul(fsl_from_words(rn, k), zz, k));
+    eq = true;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) eq &= (X[i] == T[i]);
+  }
+  okv &= eq;
+  if (threadIdx.x == 0) {
+    if (b.out8) b.out8[gi] = okv ? 1u : 0u;
+    else if (okv) atomicOr((unsigned long long*)&b.bits[gi >> 6], 1ull << (gi & 63u));
+  }
+}
+
 // GV_LAT_SL_SPLIT: batches of at most this many signatures split the pub33
 // ladder's windows over two waves (even windows + G on wave 0, odd windows on
 // wave 2; 192-thread blocks): each runs the 125 doublings but only half the
@@ -958,6 +1046,9 @@ GV_DEV void lat_sl_prep(SH& sh, const gvk_lat& b, u32 gi, const fslk& k) {
 #ifndef GV_LAT_SL_SPLIT
 #define GV_LAT_SL_SPLIT 512
 #endif
+// Keeps its own text of gjsl_set_or_add, gjsl_rows_sum, lds_put_pt / lds_get_pt
+// and lat_sl_final (a fix to one of them goes here too): through the helpers its
+// ladder loops are scheduled differently, 1 % slower at 1,024 (profiles/r08/lat_helpers).
 __global__ __launch_bounds__(192) void k_verify_lat_sl(const gvk_lat b) {
   __shared__ LatSlShared sh;
   const u32 gi = blockIdx.x;                            // grid = n: every block is live
@@ -1112,7 +1203,6 @@ __global__ __launch_bounds__(192) void k_verify_lat_sl(const gvk_lat b) {
 struct LatSl4Shared {
   static constexpr bool kG5 = false;
   static constexpr bool kG24 = true;
-  static constexpr bool kQ6 = false;          // Q digits: 5-bit windows (6-bit: the kn arena)
   u32 qtab[2][GV_QTAB_N][18];               // Q', lambda*Q' entries (effective affine, sliced limbs)
   u32 ratio[GV_QTAB_N - 1][9];
   u32 dq[1][GV_QWIN];
@@ -1298,10 +1388,7 @@ __global__ __launch_bounds__(256) void k_verify_lat_sl4(const gvk_lat b) {
       if (sh.dg24[0][j] == 0) continue;
       gj4_add_affine(A, inf, lo ? sh.gent[j][L] : 0u, lo ? sh.gent[j][9 + L] : 0u, row, k);
     }
-    if (row == 0u) {
-      if (lo) { sh.pt[3][0][L] = A.x; sh.pt[3][1][L] = A.y; sh.pt[3][2][L] = A.z; }
-      if (L == 0u) sh.pinf[3] = inf ? 1u : 0u;
-    }
+    if (row == 0u) lds_put_pt(sh.pt[3], sh.pinf[3], A, inf, k);
     LAT_STAMP(7);                                       // trace builds: G sum done
     A.x = 0u; A.y = 0u; A.z = 0u;
     inf = true;
@@ -1332,10 +1419,7 @@ __global__ __launch_bounds__(256) void k_verify_lat_sl4(const gvk_lat b) {
     }
   }
   if (wave == 0u) LAT_STAMP(5);
-  if (wave != 0u && row == 0u) {                        // partial sums into LDS, wave 0 adds them
-    if (lo) { sh.pt[wave - 1][0][L] = A.x; sh.pt[wave - 1][1][L] = A.y; sh.pt[wave - 1][2][L] = A.z; }
-    if (L == 0u) sh.pinf[wave - 1] = inf ? 1u : 0u;
-  }
+  if (wave != 0u && row == 0u) lds_put_pt(sh.pt[wave - 1], sh.pinf[wave - 1], A, inf, k);   // wave 0 adds them
   __syncthreads();
   if (wave != 0u) return;
   // the Q' partial sums (the tables' curve), then back to E: Z * zq * y
@@ -1343,39 +1427,13 @@ __global__ __launch_bounds__(256) void k_verify_lat_sl4(const gvk_lat b) {
   for (int j = 0; j < 4; ++j) {
     if (j == 3 && !inf) A.z = fsl_mul(A.z, fsl_mul(lo ? sh.zq[L] : 0u, lo ? sh.ysl[L] : 0u, k), k);
     gjsl O;
-    O.x = lo ? sh.pt[j][0][L] : 0u;
-    O.y = lo ? sh.pt[j][1][L] : 0u;
-    O.z = lo ? sh.pt[j][2][L] : 0u;
-    gj4_add_gej(A, inf, O, sh.pinf[j] != 0u, row, k);
+    bool oinf;
+    lds_get_pt(O, oinf, sh.pt[j], sh.pinf[j], k);
+    gj4_add_gej(A, inf, O, oinf, row, k);
   }
   LAT_STAMP(6);
   // ---- final check (as k_verify_lat_sl): x(R) mod n == r, without inversion
-  const bool ok = sh.okp != 0u;
-  const u32 fl = sh.oks[0];
-  bool okv = (fl & 1u) && ok && !inf;
-  u32 rw[8], X[8], T[8];
-#pragma unroll
-  for (int i = 0; i < 8; ++i) rw[i] = sh.r[0][i];
-  const u32 zz = fsl_sqr(A.z, k);
-  fsl_to_words(X, A.x);
-  fsl_to_words(T, fsl_mul(fsl_from_words(rw, k), zz, k));
-  bool eq = true;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) eq &= (X[i] == T[i]);
-  if (!eq && (fl & 2u)) {
-    u32 rn[8], c = 0;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) rn[i] = __builtin_addc(rw[i], kN[i], c, &c);
-    fsl_to_words(T, fsl_mul(fsl_from_words(rn, k), zz, k));
-    eq = true;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) eq &= (X[i] == T[i]);
-  }
-  okv &= eq;
-  if (threadIdx.x == 0) {
-    if (b.out8) b.out8[gi] = okv ? 1u : 0u;
-    else if (okv) atomicOr((unsigned long long*)&b.bits[gi >> 6], 1ull << (gi & 63u));
-  }
+  lat_sl_final(b, gi, sh.oks[0], sh.r[0], A, inf, sh.okp != 0u, k);
 }
 
 // ---------------------------------------------------------------------------
@@ -1389,7 +1447,6 @@ __global__ __launch_bounds__(256) void k_verify_lat_sl4(const gvk_lat b) {
 struct Lat16SlShared {
   static constexpr bool kG5 = true;
   static constexpr bool kG24 = false;
-  static constexpr bool kQ6 = false;          // Q digits: 5-bit windows (6-bit: the kn arena)
   u32 eh[8];                                // message path: the SHA-256 state of the sign bytes (wave 1)
   u32 dq[1][GV_QWIN];
   u32 dg5[1][GV_QWIN];
@@ -1402,45 +1459,17 @@ struct Lat16SlShared {
 __global__ __launch_bounds__(256) void k_verify_lat16_sl(const gvk_lat b) {
   __shared__ Lat16SlShared sh;
   const u32 gi = blockIdx.x;                            // grid = n: every block is live
+  // lat_keyed_slot, written out (93 VGPRs, 5 waves/SIMD through the helper: profiles/r08/lat_helpers)
   u32 sl = b.kslot[gi];
   bool kok = sl < b.kcount;
   if (!kok) sl = 0;                                     // the arena always holds slot 0's memory
   kok = kok && b.kok[sl] != 0u;
-  if (b.msg_len) {
-    // message path: wave 1 hashes the sign bytes while wave 0 runs the
-    // scalar chain up to s^-1; one extra barrier hands the digest over
-    if (threadIdx.x < 64) {
-      lat_scalars_e<true>(sh, 0, true, b.sig64 + (size_t)gi * 64u, [&](u32 e[8]) {
-        __syncthreads();
-#pragma unroll
-        for (int i = 0; i < 8; ++i) e[i] = sh.eh[7 - i];
-      });
-    } else {
-      if (threadIdx.x < 128) {
-        u32 eh[8];
-        sha256_msg_wave(eh, b.msg_blob + b.msg_off[gi], b.msg_len[gi]);
-        if (threadIdx.x == 64) {
-#pragma unroll
-          for (int i = 0; i < 8; ++i) sh.eh[i] = eh[i];
-        }
-      }
-      __syncthreads();
-    }
-  } else if (threadIdx.x < 64) {                        // wave 0: the scalar chain, whole wave
-    lat_scalars<true>(sh, 0, true, b.sig64 + (size_t)gi * 64u, b.dig32 + (size_t)gi * 32u, nullptr, b.C, gi);
-  }
-  __syncthreads();
+  lat_keyed_scalars(sh, b, gi);
   const fslk k = fsl_consts();
   const u32 L = k.L, part = (threadIdx.x >> 4) & 3u, grp = threadIdx.x >> 6;
   const bool lo = L < 9u;
   const int w_lo = kL16Win[grp], w_hi = kL16Win[grp + 1] - 1;
-  u32 beta;
-  {
-    u32 w[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) w[i] = kLBeta[i];
-    beta = fsl_from_words(w, k);
-  }
+  const u32 beta = fsl_beta(k);
   const u32* qrow = grp == 0u ? b.kqt + (size_t)sl * GV_QTAB_N * GV_QENT_WORDS
                               : b.kqt2 + ((size_t)sl * GV_KEY2_TABLES + (grp - 1u)) * GV_QTAB_N * GV_QENT_WORDS;
   const u32* grow = b.glat + (size_t)(grp * 2u + (part & 1u)) * GV_QTAB_N * 16u;
@@ -1473,74 +1502,18 @@ __global__ __launch_bounds__(256) void k_verify_lat16_sl(const gvk_lat b) {
     if (d != 0) {
       if (part == 1u) x = fsl_mul(x, beta, k);          // lambda Q = (beta x, y), same Z
       if (d < 0) y = k.bias - y;
-      if (inf) {
-        A.x = x; A.y = fsl_norm(y, k); A.z = L == 0u ? 1u : 0u;
-        inf = false;
-      } else {
-        gjsl_add_scaled(A, inf, x, y, A.z, k);
-      }
+      gjsl_set_or_add(A, inf, x, y, k);
     }
   }
-  if (part < 2u) {                                      // Q parts: back to the real curve
-    const u32* zrow = grp == 0u ? b.kzq : b.kzq2 + (size_t)(grp - 1u) * 8u * b.kC;
-    u32 w[8];
-#pragma unroll
-    for (int i = 0; i < 8; ++i) w[i] = zrow[(size_t)i * b.kC + sl];
-    A.z = fsl_mul(A.z, fsl_from_words(w, k), k);
-  }
-#pragma unroll 1
-  for (int m = 16; m < 64; m <<= 1) {                   // the group's four parts
-    gjsl O;
-    O.x = (u32)__shfl_xor((int)A.x, m, 64);
-    O.y = (u32)__shfl_xor((int)A.y, m, 64);
-    O.z = (u32)__shfl_xor((int)A.z, m, 64);
-    const bool oinf = __shfl_xor((int)inf, m, 64) != 0;
-    gjsl_add_gej(A, inf, A, inf, O, oinf, k);
-  }
-  if (part == 0u) {
-    if (lo) { sh.pt[grp][0][L] = A.x; sh.pt[grp][1][L] = A.y; sh.pt[grp][2][L] = A.z; }
-    if (L == 0u) sh.pinf[grp] = inf ? 1u : 0u;
-  }
+  if (part < 2u)                                        // Q parts: back to the real curve
+    lat_sl_lift(A, grp == 0u ? b.kzq : b.kzq2 + (size_t)(grp - 1u) * 8u * b.kC, b.kC, sl, k);
+  gjsl_rows_sum(A, inf, k);                             // the group's four parts
+  if (part == 0u) lds_put_pt(sh.pt[grp], sh.pinf[grp], A, inf, k);
   __syncthreads();
   if (grp != 0u) return;
-  A.x = lo ? sh.pt[part][0][L] : 0u;                    // wave 0, row r: group r's sum
-  A.y = lo ? sh.pt[part][1][L] : 0u;
-  A.z = lo ? sh.pt[part][2][L] : 0u;
-  inf = sh.pinf[part] != 0u;
-#pragma unroll 1
-  for (int m = 16; m < 64; m <<= 1) {
-    gjsl O;
-    O.x = (u32)__shfl_xor((int)A.x, m, 64);
-    O.y = (u32)__shfl_xor((int)A.y, m, 64);
-    O.z = (u32)__shfl_xor((int)A.z, m, 64);
-    const bool oinf = __shfl_xor((int)inf, m, 64) != 0;
-    gjsl_add_gej(A, inf, A, inf, O, oinf, k);
-  }
-  const u32 fl = sh.oks[0];
-  bool okv = (fl & 1u) && kok && !inf;
-  u32 rw[8], X[8], T[8];
-#pragma unroll
-  for (int i = 0; i < 8; ++i) rw[i] = sh.r[0][i];
-  const u32 zz = fsl_sqr(A.z, k);
-  fsl_to_words(X, A.x);
-  fsl_to_words(T, fsl_mul(fsl_from_words(rw, k), zz, k));
-  bool eq = true;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) eq &= (X[i] == T[i]);
-  if (!eq && (fl & 2u)) {
-    u32 rn[8], c = 0;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) rn[i] = __builtin_addc(rw[i], kN[i], c, &c);
-    fsl_to_words(T, fsl_mul(fsl_from_words(rn, k), zz, k));
-    eq = true;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) eq &= (X[i] == T[i]);
-  }
-  okv &= eq;
-  if (threadIdx.x == 0) {
-    if (b.out8) b.out8[gi] = okv ? 1u : 0u;
-    else if (okv) atomicOr((unsigned long long*)&b.bits[gi >> 6], 1ull << (gi & 63u));
-  }
+  lds_get_pt(A, inf, sh.pt[part], sh.pinf[part], k);    // wave 0, row r: group r's sum
+  gjsl_rows_sum(A, inf, k);
+  lat_sl_final(b, gi, sh.oks[0], sh.r[0], A, inf, kok, k);
 }
 
 // ---------------------------------------------------------------------------
@@ -1554,12 +1527,22 @@ __global__ __launch_bounds__(256) void k_verify_lat16_sl(const gvk_lat b) {
 // G windows j == row - 12 (mod 4); row 11 has nothing to add.  The 16 sums
 // are joined four per wave with the row-parallel complete addition
 // (gj4_add_gej), then by wave 0.  Same verdicts as k_verify_lat16_sl.
-struct Lat16KnShared {
+//
+// On the wide-window tables (k_verify_lat16_kw): the slot's GV_KW_NG1 group
+// tables of 2^(QW-1) entries (one QW-bit Booth window per group and GLV half,
+// 64-B canonical entries on one Z) need no doubling at all; row g < GV_KW_NG1
+// adds group g's Q and lambda*Q entries and lifts its sum.
+//
+// The two kernels differ in their Q rows only: the prologue, the G rows
+// (lat_g24_rows), the join (lat_rows16_sum) and the final check are shared,
+// and so is the shared state, up to the Q digit width.
+template <int QW, int QWIN>
+struct Lat16RowsShared {
   static constexpr bool kG5 = false;
   static constexpr bool kG24 = true;
-  static constexpr bool kQ6 = true;
+  static constexpr int kQW = QW, kQWIN = QWIN;   // Q digits: QWIN windows of QW bits (lat_q_width)
   u32 eh[8];                                // message path: the SHA-256 state of the sign bytes (wave 1)
-  u32 dq[1][GV_QWIN];                       // GV_K6_QWIN used
+  u32 dq[1][GV_QWIN];                       // QWIN used
   int dg24[1][GV_K6_GWIN];
   u32 r[1][8];
   u32 oks[1];
@@ -1568,52 +1551,73 @@ struct Lat16KnShared {
   u32 pw[4][3][16];                         // the waves' sums
   u32 pwinf[4];
 };
+using Lat16KnShared = Lat16RowsShared<GV_K6_QW, GV_K6_QWIN>;
+using Lat16KwShared = Lat16RowsShared<GV_KW_QW, GV_KW_QWIN>;
+static_assert(lat_q_width<Lat16KnShared>::qw == GV_K6_QW && lat_q_width<Lat16KnShared>::qwin == GV_K6_QWIN &&
+                  lat_q_width<Lat16KwShared>::qw == GV_KW_QW && lat_q_width<Lat16KwShared>::qwin == GV_KW_QWIN &&
+                  lat_q_width<Lat16SlShared>::qw == GV_QW && lat_q_width<Lat16SlShared>::qwin == GV_QWIN,
+              "digit widths of the keyed kernels");
 static_assert(GV_K6_QWIN == 2 * GV_KN_ARENA_NG && GV_KN_ARENA_NG <= 12 && GV_K6_GWIN <= 12, "kn rows");
+static_assert(GV_KW_NG1 == GV_KW_QWIN && GV_KW_NG1 <= 12 && GV_KW_QWIN <= GV_QWIN && GV_K6_GWIN <= 12 &&
+                  GV_KW_ENT_WORDS == 16,
+              "kw rows: one window per group in rows 0..11, 64-B canonical entries");
+
+// Rows 12..15 (wave 3): row r adds the G windows j == r (mod 4) of u1's 24-bit
+// digits from gtab6 (no doublings).
+GV_DEV void lat_g24_rows(gjsl& A, bool& inf, const int* dg24, const u32* gtab6, u32 row, const fslk& k) {
+#pragma unroll 1
+  for (u32 j = row; j < GV_K6_GWIN; j += 4u) {
+    const int d = dg24[j];
+    if (d == 0) continue;
+    const u32* pe = gtab6 + ((size_t)j * GV_K6_GTAB_N + (u32)((d < 0 ? -d : d) - 1)) * 16u;
+    const u32 x = fsl_load_words(pe, k);
+    u32 y = fsl_load_words(pe + 8, k);
+    if (d < 0) y = k.bias - y;
+    gjsl_set_or_add(A, inf, x, y, k);
+  }
+}
+
+// The sum of the block's 16 row sums (real curve; all 256 threads call this,
+// two block barriers): each wave adds its four rows' sums row-parallel, then
+// wave 0 adds the waves' sums.  True in wave 0, which holds the sum.
+template <class SH>
+GV_DEV bool lat_rows16_sum(SH& sh, gjsl& A, bool& inf, const fslk& k) {
+  const u32 r16 = threadIdx.x >> 4, wave = threadIdx.x >> 6, row = r16 & 3u, r0 = wave * 4u;
+  gjsl O;
+  bool oinf;
+  lds_put_pt(sh.pt[r16], sh.pinf[r16], A, inf, k);
+  __syncthreads();
+  lds_get_pt(A, inf, sh.pt[r0], sh.pinf[r0], k);
+#pragma unroll 1
+  for (u32 j = 1; j < 4u; ++j) {
+    lds_get_pt(O, oinf, sh.pt[r0 + j], sh.pinf[r0 + j], k);
+    gj4_add_gej(A, inf, O, oinf, row, k);
+  }
+  if (row == 0u) lds_put_pt(sh.pw[wave], sh.pwinf[wave], A, inf, k);
+  __syncthreads();
+  if (wave != 0u) return false;
+#pragma unroll 1
+  for (u32 j = 1; j < 4u; ++j) {
+    lds_get_pt(O, oinf, sh.pw[j], sh.pwinf[j], k);
+    gj4_add_gej(A, inf, O, oinf, row, k);
+  }
+  return true;
+}
 
 __global__ __launch_bounds__(256) void k_verify_lat16_kn(const gvk_lat b) {
   __shared__ Lat16KnShared sh;
   const u32 gi = blockIdx.x;                            // grid = n: every block is live
-  u32 sl = b.kslot[gi];
-  bool kok = sl < b.kcount;
-  if (!kok) sl = 0;                                     // the arena always holds slot 0's memory
-  kok = kok && b.kok[sl] != 0u;
-  if (b.msg_len) {
-    if (threadIdx.x < 64) {
-      lat_scalars_e<true>(sh, 0, true, b.sig64 + (size_t)gi * 64u, [&](u32 e[8]) {
-        __syncthreads();
-#pragma unroll
-        for (int i = 0; i < 8; ++i) e[i] = sh.eh[7 - i];
-      });
-    } else {
-      if (threadIdx.x < 128) {
-        u32 eh[8];
-        sha256_msg_wave(eh, b.msg_blob + b.msg_off[gi], b.msg_len[gi]);
-        if (threadIdx.x == 64) {
-#pragma unroll
-          for (int i = 0; i < 8; ++i) sh.eh[i] = eh[i];
-        }
-      }
-      __syncthreads();
-    }
-  } else if (threadIdx.x < 64) {
-    lat_scalars<true>(sh, 0, true, b.sig64 + (size_t)gi * 64u, b.dig32 + (size_t)gi * 32u, nullptr, b.C, gi);
-  }
-  __syncthreads();
+  bool kok;
+  const u32 sl = lat_keyed_slot(kok, b.kslot[gi], b.kok, b.kcount);
+  lat_keyed_scalars(sh, b, gi);
   const fslk k = fsl_consts();
-  const u32 L = k.L, r16 = threadIdx.x >> 4, wave = threadIdx.x >> 6, row = r16 & 3u;
+  const u32 L = k.L, g = threadIdx.x >> 4, wave = threadIdx.x >> 6;
   const bool lo = L < 9u;
   gjsl A;
   A.x = 0u; A.y = 0u; A.z = 0u;
   bool inf = true;
   if (wave < 3u) {                                      // rows 0..11: Q groups (row 11: none)
-    const u32 g = r16;
-    u32 beta;
-    {
-      u32 w[8];
-#pragma unroll
-      for (int i = 0; i < 8; ++i) w[i] = kLBeta[i];
-      beta = fsl_from_words(w, k);
-    }
+    const u32 beta = fsl_beta(k);
     const u32* tab = g == 0u ? b.kqt + (size_t)sl * GV_K6_KEY_WORDS
                              : b.kqt2 + ((size_t)sl * (GV_KN_ARENA_NG - 1) + (g - 1u)) * GV_K6_KEY_WORDS;
 #pragma unroll 1
@@ -1632,163 +1636,31 @@ __global__ __launch_bounds__(256) void k_verify_lat16_kn(const gvk_lat b) {
         u32 y = lo ? pe[9 + L] : 0u;
         if (t == 1) x = fsl_mul(x, beta, k);            // lambda Q = (beta x, y), same Z
         if (d < 0) y = k.bias - y;
-        if (inf) {
-          A.x = x; A.y = fsl_norm(y, k); A.z = L == 0u ? 1u : 0u;
-          inf = false;
-        } else {
-          gjsl_add_scaled(A, inf, x, y, A.z, k);
-        }
+        gjsl_set_or_add(A, inf, x, y, k);
       }
     }
-    {                                                   // back to the real curve: Z * (the tables' Z)
-      u32 w[8];
-#pragma unroll
-      for (int i = 0; i < 8; ++i) w[i] = b.kzq[(size_t)i * b.kC + sl];
-      A.z = fsl_mul(A.z, fsl_from_words(w, k), k);
-    }
+    lat_sl_lift(A, b.kzq, b.kC, sl, k);                 // back to the real curve
   } else {                                              // rows 12..15: G windows j = row (mod 4)
-#pragma unroll 1
-    for (u32 j = row; j < GV_K6_GWIN; j += 4u) {
-      const int d = sh.dg24[0][j];
-      if (d == 0) continue;
-      const u32* pe = b.gtab6 + ((size_t)j * GV_K6_GTAB_N + (u32)((d < 0 ? -d : d) - 1)) * 16u;
-      const u32 x = fsl_load_words(pe, k);
-      u32 y = fsl_load_words(pe + 8, k);
-      if (d < 0) y = k.bias - y;
-      if (inf) {
-        A.x = x; A.y = fsl_norm(y, k); A.z = L == 0u ? 1u : 0u;
-        inf = false;
-      } else {
-        gjsl_add_scaled(A, inf, x, y, A.z, k);
-      }
-    }
+    lat_g24_rows(A, inf, sh.dg24[0], b.gtab6, g & 3u, k);
   }
-  if (lo) { sh.pt[r16][0][L] = A.x; sh.pt[r16][1][L] = A.y; sh.pt[r16][2][L] = A.z; }
-  if (L == 0u) sh.pinf[r16] = inf ? 1u : 0u;
-  __syncthreads();
-  // each wave: its four rows' sums, replicated over its rows, row-parallel additions
-  {
-    const u32 r0 = wave * 4u;
-    A.x = lo ? sh.pt[r0][0][L] : 0u; A.y = lo ? sh.pt[r0][1][L] : 0u; A.z = lo ? sh.pt[r0][2][L] : 0u;
-    inf = sh.pinf[r0] != 0u;
-#pragma unroll 1
-    for (u32 j = 1; j < 4u; ++j) {
-      gjsl O;
-      O.x = lo ? sh.pt[r0 + j][0][L] : 0u; O.y = lo ? sh.pt[r0 + j][1][L] : 0u; O.z = lo ? sh.pt[r0 + j][2][L] : 0u;
-      gj4_add_gej(A, inf, O, sh.pinf[r0 + j] != 0u, row, k);
-    }
-    if (row == 0u) {
-      if (lo) { sh.pw[wave][0][L] = A.x; sh.pw[wave][1][L] = A.y; sh.pw[wave][2][L] = A.z; }
-      if (L == 0u) sh.pwinf[wave] = inf ? 1u : 0u;
-    }
-  }
-  __syncthreads();
-  if (wave != 0u) return;
-#pragma unroll 1
-  for (u32 j = 1; j < 4u; ++j) {
-    gjsl O;
-    O.x = lo ? sh.pw[j][0][L] : 0u; O.y = lo ? sh.pw[j][1][L] : 0u; O.z = lo ? sh.pw[j][2][L] : 0u;
-    gj4_add_gej(A, inf, O, sh.pwinf[j] != 0u, row, k);
-  }
-  const u32 fl = sh.oks[0];
-  bool okv = (fl & 1u) && kok && !inf;
-  u32 rw[8], X[8], T[8];
-#pragma unroll
-  for (int i = 0; i < 8; ++i) rw[i] = sh.r[0][i];
-  const u32 zz = fsl_sqr(A.z, k);
-  fsl_to_words(X, A.x);
-  fsl_to_words(T, fsl_mul(fsl_from_words(rw, k), zz, k));
-  bool eq = true;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) eq &= (X[i] == T[i]);
-  if (!eq && (fl & 2u)) {
-    u32 rn[8], c = 0;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) rn[i] = __builtin_addc(rw[i], kN[i], c, &c);
-    fsl_to_words(T, fsl_mul(fsl_from_words(rn, k), zz, k));
-    eq = true;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) eq &= (X[i] == T[i]);
-  }
-  okv &= eq;
-  if (threadIdx.x == 0) {
-    if (b.out8) b.out8[gi] = okv ? 1u : 0u;
-    else if (okv) atomicOr((unsigned long long*)&b.bits[gi >> 6], 1ull << (gi & 63u));
-  }
+  if (!lat_rows16_sum(sh, A, inf, k)) return;
+  lat_sl_final(b, gi, sh.oks[0], sh.r[0], A, inf, kok, k);
 }
-
-// Keyed small batches on the resident arena's wide-window tables
-// (k_verify_lat16_kw, round 6): the slot's GV_KW_NG1 group tables of
-// 2^(QW-1) entries (one QW-bit Booth window per group and GLV half, 64-B
-// canonical entries on one Z) need no doubling at all.  One signature per
-// 256-thread block, 16 rows: row g < GV_KW_NG1 adds group g's Q and lambda*Q
-// entries and lifts its sum by the tables' Z; rows 12..15 (wave 3) add the G
-// windows j == row - 12 (mod 4) from the 24-bit tables.  The 16 sums are
-// joined as in k_verify_lat16_kn.  Same verdicts as k_verify_lat16_sl.
-struct Lat16KwShared {
-  static constexpr bool kG5 = false;
-  static constexpr bool kG24 = true;
-  static constexpr bool kQ6 = false;
-  static constexpr bool kKW = true;         // Q digits: GV_KW_QW-bit windows (lat_q_width)
-  u32 eh[8];
-  u32 dq[1][GV_QWIN];                       // GV_KW_QWIN used
-  int dg24[1][GV_K6_GWIN];
-  u32 r[1][8];
-  u32 oks[1];
-  u32 pt[16][3][16];
-  u32 pinf[16];
-  u32 pw[4][3][16];
-  u32 pwinf[4];
-};
-static_assert(GV_KW_NG1 == GV_KW_QWIN && GV_KW_NG1 <= 12 && GV_KW_QWIN <= GV_QWIN && GV_K6_GWIN <= 12 &&
-                  GV_KW_ENT_WORDS == 16,
-              "kw rows: one window per group in rows 0..11, 64-B canonical entries");
 
 __global__ __launch_bounds__(256) void k_verify_lat16_kw(const gvk_lat b) {
   __shared__ Lat16KwShared sh;
   const u32 gi = blockIdx.x;                            // grid = n: every block is live
-  u32 sl = b.kslot[gi];
-  bool kok = sl < b.kcount;
-  if (!kok) sl = 0;                                     // the arena always holds slot 0's memory
-  kok = kok && b.kok[sl] != 0u;
-  if (b.msg_len) {
-    if (threadIdx.x < 64) {
-      lat_scalars_e<true>(sh, 0, true, b.sig64 + (size_t)gi * 64u, [&](u32 e[8]) {
-        __syncthreads();
-#pragma unroll
-        for (int i = 0; i < 8; ++i) e[i] = sh.eh[7 - i];
-      });
-    } else {
-      if (threadIdx.x < 128) {
-        u32 eh[8];
-        sha256_msg_wave(eh, b.msg_blob + b.msg_off[gi], b.msg_len[gi]);
-        if (threadIdx.x == 64) {
-#pragma unroll
-          for (int i = 0; i < 8; ++i) sh.eh[i] = eh[i];
-        }
-      }
-      __syncthreads();
-    }
-  } else if (threadIdx.x < 64) {
-    lat_scalars<true>(sh, 0, true, b.sig64 + (size_t)gi * 64u, b.dig32 + (size_t)gi * 32u, nullptr, b.C, gi);
-  }
-  __syncthreads();
+  bool kok;
+  const u32 sl = lat_keyed_slot(kok, b.kslot[gi], b.kok, b.kcount);
+  lat_keyed_scalars(sh, b, gi);
   const fslk k = fsl_consts();
-  const u32 L = k.L, r16 = threadIdx.x >> 4, wave = threadIdx.x >> 6, row = r16 & 3u;
-  const bool lo = L < 9u;
+  const u32 g = threadIdx.x >> 4, wave = threadIdx.x >> 6;
   gjsl A;
   A.x = 0u; A.y = 0u; A.z = 0u;
   bool inf = true;
   if (wave < 3u) {                                      // rows 0..11: Q groups
-    const u32 g = r16;
     if (g < (u32)GV_KW_NG1) {
-      u32 beta;
-      {
-        u32 w[8];
-#pragma unroll
-        for (int i = 0; i < 8; ++i) w[i] = kLBeta[i];
-        beta = fsl_from_words(w, k);
-      }
+      const u32 beta = fsl_beta(k);
       const u32* tab = g == 0u ? b.kqt + (size_t)sl * GV_KW_KEY_WORDS
                                : b.kqt2 + ((size_t)sl * (GV_KW_NG1 - 1) + (g - 1u)) * GV_KW_KEY_WORDS;
       const u32 dq = sh.dq[0][g];
@@ -1801,88 +1673,15 @@ __global__ __launch_bounds__(256) void k_verify_lat16_kw(const gvk_lat b) {
         u32 y = fsl_load_words(pe + 8, k);
         if (t == 1) x = fsl_mul(x, beta, k);            // lambda Q = (beta x, y), same Z
         if (d < 0) y = k.bias - y;
-        if (inf) {
-          A.x = x; A.y = fsl_norm(y, k); A.z = L == 0u ? 1u : 0u;
-          inf = false;
-        } else {
-          gjsl_add_scaled(A, inf, x, y, A.z, k);
-        }
+        gjsl_set_or_add(A, inf, x, y, k);
       }
-      {                                                 // back to the real curve: Z * (the tables' Z)
-        u32 w[8];
-#pragma unroll
-        for (int i = 0; i < 8; ++i) w[i] = b.kzq[(size_t)i * b.kC + sl];
-        A.z = fsl_mul(A.z, fsl_from_words(w, k), k);
-      }
+      lat_sl_lift(A, b.kzq, b.kC, sl, k);               // back to the real curve
     }
   } else {                                              // rows 12..15: G windows j = row (mod 4)
-#pragma unroll 1
-    for (u32 j = row; j < GV_K6_GWIN; j += 4u) {
-      const int d = sh.dg24[0][j];
-      if (d == 0) continue;
-      const u32* pe = b.gtab6 + ((size_t)j * GV_K6_GTAB_N + (u32)((d < 0 ? -d : d) - 1)) * 16u;
-      const u32 x = fsl_load_words(pe, k);
-      u32 y = fsl_load_words(pe + 8, k);
-      if (d < 0) y = k.bias - y;
-      if (inf) {
-        A.x = x; A.y = fsl_norm(y, k); A.z = L == 0u ? 1u : 0u;
-        inf = false;
-      } else {
-        gjsl_add_scaled(A, inf, x, y, A.z, k);
-      }
-    }
+    lat_g24_rows(A, inf, sh.dg24[0], b.gtab6, g & 3u, k);
   }
-  if (lo) { sh.pt[r16][0][L] = A.x; sh.pt[r16][1][L] = A.y; sh.pt[r16][2][L] = A.z; }
-  if (L == 0u) sh.pinf[r16] = inf ? 1u : 0u;
-  __syncthreads();
-  {
-    const u32 r0 = wave * 4u;
-    A.x = lo ? sh.pt[r0][0][L] : 0u; A.y = lo ? sh.pt[r0][1][L] : 0u; A.z = lo ? sh.pt[r0][2][L] : 0u;
-    inf = sh.pinf[r0] != 0u;
-#pragma unroll 1
-    for (u32 j = 1; j < 4u; ++j) {
-      gjsl O;
-      O.x = lo ? sh.pt[r0 + j][0][L] : 0u; O.y = lo ? sh.pt[r0 + j][1][L] : 0u; O.z = lo ? sh.pt[r0 + j][2][L] : 0u;
-      gj4_add_gej(A, inf, O, sh.pinf[r0 + j] != 0u, row, k);
-    }
-    if (row == 0u) {
-      if (lo) { sh.pw[wave][0][L] = A.x; sh.pw[wave][1][L] = A.y; sh.pw[wave][2][L] = A.z; }
-      if (L == 0u) sh.pwinf[wave] = inf ? 1u : 0u;
-    }
-  }
-  __syncthreads();
-  if (wave != 0u) return;
-#pragma unroll 1
-  for (u32 j = 1; j < 4u; ++j) {
-    gjsl O;
-    O.x = lo ? sh.pw[j][0][L] : 0u; O.y = lo ? sh.pw[j][1][L] : 0u; O.z = lo ? sh.pw[j][2][L] : 0u;
-    gj4_add_gej(A, inf, O, sh.pwinf[j] != 0u, row, k);
-  }
-  const u32 fl = sh.oks[0];
-  bool okv = (fl & 1u) && kok && !inf;
-  u32 rw[8], X[8], T[8];
-#pragma unroll
-  for (int i = 0; i < 8; ++i) rw[i] = sh.r[0][i];
-  const u32 zz = fsl_sqr(A.z, k);
-  fsl_to_words(X, A.x);
-  fsl_to_words(T, fsl_mul(fsl_from_words(rw, k), zz, k));
-  bool eq = true;
-#pragma unroll
-  for (int i = 0; i < 8; ++i) eq &= (X[i] == T[i]);
-  if (!eq && (fl & 2u)) {
-    u32 rn[8], c = 0;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) rn[i] = __builtin_addc(rw[i], kN[i], c, &c);
-    fsl_to_words(T, fsl_mul(fsl_from_words(rn, k), zz, k));
-    eq = true;
-#pragma unroll
-    for (int i = 0; i < 8; ++i) eq &= (X[i] == T[i]);
-  }
-  okv &= eq;
-  if (threadIdx.x == 0) {
-    if (b.out8) b.out8[gi] = okv ? 1u : 0u;
-    else if (okv) atomicOr((unsigned long long*)&b.bits[gi >> 6], 1ull << (gi & 63u));
-  }
+  if (!lat_rows16_sum(sh, A, inf, k)) return;
+  lat_sl_final(b, gi, sh.oks[0], sh.r[0], A, inf, kok, k);
 }
 
 // --------------------------------------------------------------- k_debug_sl

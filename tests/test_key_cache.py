@@ -99,6 +99,73 @@ def test_ragged_keyed_and_unloaded_slots(ver, n, path):
     assert np.array_equal(ver.verify_batch_digests_keyed(bad, sig, dig), exp)
 
 
+def _special_msg_items(n, seed):
+    """n message items, one key each, e = SHA-256 of the message: item 0 sums
+    to the point at infinity (d = -e / r), item 1 has R.x = n + delta with
+    r = n + delta ("x_in_n_p_rbig": reject), item 2 the same R with r = delta
+    (accept), item 3 a valid signature over a message with one bit flipped
+    afterwards; the rest valid.  n == 1: `seed` picks which of the four."""
+    import random
+
+    import special_cases as S
+    rng = random.Random(seed)
+    items = []
+
+    def add(pub, r, s, msg):
+        items.append((np.frombuffer(pub, np.uint8), np.frombuffer(S._b32(r) + S._b32(s), np.uint8), msg))
+
+    for i in ([seed % 4] if n == 1 else range(n)):
+        msg = rng.randbytes(rng.randrange(1, 300))
+        e = int.from_bytes(O.sha256(msg), "big")
+        if i == 0:                                              # infinity
+            r = rng.randrange(1, S.N)
+            add(S.R.compress(S._mul(-e * pow(r, S.N - 2, S.N))), r, rng.randrange(1, 2**62), msg)
+        elif i in (1, 2):                                       # R.x in [n, p)
+            Q = None
+            while Q is None:
+                delta = rng.choice(S._deltas())
+                s = rng.randrange(1, S.HALF_N)
+                Q = S._recover(S._lift(S.N + delta, rng.randrange(2)), delta, s, e)
+            add(S.R.compress(Q), S.N + delta if i == 1 else delta, s, msg)
+        else:
+            priv = rng.randrange(1, S.N).to_bytes(32, "big")
+            sig = O.sign(priv, O.sha256(msg))
+            if i == 3:                                          # wrong message
+                msg = bytes([msg[0] ^ 1]) + msg[1:]
+            items.append((np.frombuffer(O.pubkey(priv), np.uint8), np.frombuffer(bytes(sig), np.uint8), msg))
+    pub, sig, msgs = (np.array([it[0] for it in items]), np.array([it[1] for it in items]), [it[2] for it in items])
+    want = np.array([O.verify_bytes(bytes(p), m, bytes(s)) for p, s, m in zip(pub, sig, msgs)], np.uint8)
+    return pub, sig, msgs, want
+
+
+@pytest.mark.parametrize("n", [1, 63, 65])
+@pytest.mark.parametrize("arena", ["kn", "k4"])
+def test_keyed_messages_staged_bitmap_kn_and_k4(ver, arena, n):
+    """k_verify_lat16_kn (lat_kw 0) and k_verify_lat16_sl (keys_k6 0, keys_wide
+    0) on the message path with bitmap verdicts (lat_zero_copy 0: staged input,
+    the kernel sets bits): the point at infinity, R.x in [n, p) with r = R.x
+    (reject) and r = R.x - n (accept), a wrong message, against the oracle."""
+    ver.keys_reset()
+    for k, v in ({"lat_kw": 0} if arena == "kn" else {"keys_k6": 0, "keys_wide": 0}).items():
+        ver.set_option(k, v)
+    ver.set_option("lat_zero_copy", 0)
+    try:
+        for seed in (range(4) if n == 1 else [n]):              # n == 1: each special item as its own batch
+            pub, sig, msgs, want = _special_msg_items(n, seed)
+            if n > 1:
+                assert list(want[:4]) == [0, 0, 1, 0] and want[4:].all()
+            slots = ver.keys_load(pub)
+            before = ver.route_stats()["lat_keyed"]
+            assert np.array_equal(ver.verify_batch_msgs_keyed(slots, sig, msgs), want)
+            assert ver.route_stats()["lat_keyed"] == before + 1
+    finally:
+        ver.set_option("lat_zero_copy", 1)
+        ver.set_option("lat_kw", 1)
+        ver.set_option("keys_k6", 1)
+        ver.set_option("keys_wide", 2)
+        ver.keys_reset()
+
+
 def test_arena_growth_keeps_earlier_slots(ver):
     """Many loads grow the arena (re-allocation + copy); earlier slots stay valid."""
     ver.keys_reset()
