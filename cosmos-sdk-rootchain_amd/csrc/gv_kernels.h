@@ -495,6 +495,18 @@ hipError_t gvk_kidx_put(uint32_t* table, uint32_t tslots, const uint32_t* rows, 
                         const uint32_t* slots, uint64_t seed, uint32_t* left_out, hipStream_t st);
 hipError_t gvk_kidx_find(const uint32_t* table, uint32_t tslots, const uint32_t* rows, uint32_t count, uint64_t seed,
                          const uint8_t* pub33, uint32_t n, uint32_t* slot_out, uint32_t* miss, hipStream_t st);
+// The ed25519 arena's pubkey index (option "ed_keys_index"): the same table
+// over GV_EDKIDX_ROW-word rows, which are the arena's ekpub rows (written by
+// gvk_ed_keys), so there is no row kernel.
+// gvk_edkidx_put: slots base.. (or slots[g]) enter the table; *left_out += the
+// keys that found no word within GV_KIDX_PROBE.
+// gvk_edkidx_find: item g's 32 bytes (AoS, any alignment) -> slot_out[g], the
+// lowest slot below count holding exactly those bytes, or GV_KIDX_EMPTY; *miss
+// (may be null) += the items not found.
+hipError_t gvk_edkidx_put(uint32_t* table, uint32_t tslots, const uint32_t* rows, uint32_t n, uint32_t base,
+                          const uint32_t* slots, uint64_t seed, uint32_t* left_out, hipStream_t st);
+hipError_t gvk_edkidx_find(const uint32_t* table, uint32_t tslots, const uint32_t* rows, uint32_t count, uint64_t seed,
+                           const uint8_t* pub32, uint32_t n, uint32_t* slot_out, uint32_t* miss, hipStream_t st);
 // A routed batch with a few keys that are not resident (option
 // "keys_index_split"): the dense sub-batch of those items, `cap` rows (device).
 // count: one word, the rows taken; idx[j]: the item of row j; pub33 / sig64 /

@@ -28,6 +28,7 @@
 #define GV_KIDX_PROBE 64
 #define GV_KIDX_EMPTY 0xFFFFFFFFu
 #define GV_KIDX_ROW 9
+#define GV_EDKIDX_ROW 8
 
 // Row of the 33 key bytes at p (any alignment).
 GV_KIDX_FN void gv_kidx_row(const uint8_t* p, uint32_t row[GV_KIDX_ROW]) {
@@ -38,20 +39,29 @@ GV_KIDX_FN void gv_kidx_row(const uint8_t* p, uint32_t row[GV_KIDX_ROW]) {
   }
 }
 
-GV_KIDX_FN bool gv_kidx_equal(const uint32_t* a, const uint32_t* b) {
+// The routines below serve a row of R words (gv_kidx_*_n<R>); the names
+// without _n are their 9-word instances, the secp256k1 arena's.  The ed25519
+// arena's row (option "ed_keys_index") is the slot's
+// ekpub row, GV_EDKIDX_ROW = 8 words: word i = the little-endian bytes
+// 4 i .. 4 i + 3 of the 32 key bytes as sent -- a non-canonical encoding and
+// its canonical twin are different keys, as they are to the hash of a verify.
+template <int R>
+GV_KIDX_FN bool gv_kidx_equal_n(const uint32_t* a, const uint32_t* b) {
   bool eq = true;
-  for (int i = 0; i < GV_KIDX_ROW; ++i) eq &= a[i] == b[i];
+  for (int i = 0; i < R; ++i) eq &= a[i] == b[i];
   return eq;
 }
+GV_KIDX_FN bool gv_kidx_equal(const uint32_t* a, const uint32_t* b) { return gv_kidx_equal_n<GV_KIDX_ROW>(a, b); }
 
 // key_hash (gv_kernels.hip) over the prefix and all 8 words, started from the
 // context's 64-bit seed and closed with it: accounts are chosen by whoever
 // sends transactions and the index outlives a batch, so the home word of a
 // key must not be computable without the seed.  (The probe bound, not the
 // hash, is what keeps run time and verdicts independent of the keys.)
-GV_KIDX_FN uint32_t gv_kidx_hash(const uint32_t row[GV_KIDX_ROW], uint64_t seed) {
+template <int R>
+GV_KIDX_FN uint32_t gv_kidx_hash_n(const uint32_t* row, uint64_t seed) {
   uint64_t h = 0x9E3779B97F4A7C15ull ^ seed;
-  for (int i = 0; i < GV_KIDX_ROW; ++i) {
+  for (int i = 0; i < R; ++i) {
     h ^= row[i];
     h *= 0xFF51AFD7ED558CCDull;
     h ^= h >> 29;
@@ -60,6 +70,9 @@ GV_KIDX_FN uint32_t gv_kidx_hash(const uint32_t row[GV_KIDX_ROW], uint64_t seed)
   h *= 0xC4CEB9FE1A85EC53ull;
   h ^= h >> 33;
   return (uint32_t)(h ^ (h >> 32));
+}
+GV_KIDX_FN uint32_t gv_kidx_hash(const uint32_t row[GV_KIDX_ROW], uint64_t seed) {
+  return gv_kidx_hash_n<GV_KIDX_ROW>(row, seed);
 }
 
 // Probe step i (0 .. GV_KIDX_PROBE - 1) of a key whose hash is h: the table
@@ -86,37 +99,55 @@ GV_KIDX_FN void gv_kidx_min(uint32_t* w, uint32_t val) {
 #endif
 }
 
-// Enter slot `slot` (its row already in rows, GV_KIDX_ROW words per slot).
+// Enter slot `slot` (its row already in rows, R words per slot).
 // An empty word is taken; a word whose slot holds the same bytes keeps the
 // lower of the two slots (the same key in two slots is legal: the index names
 // the lowest); another key's word sends the probe on.  Returns false when the
 // bound ran out: the key stays out of the index.
-GV_KIDX_FN bool gv_kidx_put(uint32_t* table, uint32_t tmask, const uint32_t* rows, uint32_t slot, uint64_t seed) {
-  const uint32_t* row = rows + (size_t)slot * GV_KIDX_ROW;
-  const uint32_t h = gv_kidx_hash(row, seed);
+template <int R>
+GV_KIDX_FN bool gv_kidx_put_n(uint32_t* table, uint32_t tmask, const uint32_t* rows, uint32_t slot, uint64_t seed) {
+  const uint32_t* row = rows + (size_t)slot * R;
+  const uint32_t h = gv_kidx_hash_n<R>(row, seed);
   for (uint32_t i = 0; i < GV_KIDX_PROBE; ++i) {
     uint32_t* w = table + gv_kidx_word(h, i, tmask);
     const uint32_t cur = gv_kidx_cas(w, GV_KIDX_EMPTY, slot);
     if (cur == GV_KIDX_EMPTY || cur == slot) return true;
-    if (gv_kidx_equal(rows + (size_t)cur * GV_KIDX_ROW, row)) {
+    if (gv_kidx_equal_n<R>(rows + (size_t)cur * R, row)) {
       gv_kidx_min(w, slot);
       return true;
     }
   }
   return false;
 }
+GV_KIDX_FN bool gv_kidx_put(uint32_t* table, uint32_t tmask, const uint32_t* rows, uint32_t slot, uint64_t seed) {
+  return gv_kidx_put_n<GV_KIDX_ROW>(table, tmask, rows, slot, seed);
+}
 
 // The slot whose row equals `row` (the lowest, by gv_kidx_put), or
 // GV_KIDX_EMPTY: an empty word ends the probe, and so does the bound.  A
 // table word at or past `count` (never written by gv_kidx_put over
 // [0, count)) is passed over like another key's.
-GV_KIDX_FN uint32_t gv_kidx_find(const uint32_t* table, uint32_t tmask, const uint32_t* rows, uint32_t count,
-                                 const uint32_t row[GV_KIDX_ROW], uint64_t seed) {
-  const uint32_t h = gv_kidx_hash(row, seed);
+template <int R>
+GV_KIDX_FN uint32_t gv_kidx_find_n(const uint32_t* table, uint32_t tmask, const uint32_t* rows, uint32_t count,
+                                   const uint32_t* row, uint64_t seed) {
+  const uint32_t h = gv_kidx_hash_n<R>(row, seed);
   for (uint32_t i = 0; i < GV_KIDX_PROBE; ++i) {
     const uint32_t cur = table[gv_kidx_word(h, i, tmask)];
     if (cur == GV_KIDX_EMPTY) return GV_KIDX_EMPTY;
-    if (cur < count && gv_kidx_equal(rows + (size_t)cur * GV_KIDX_ROW, row)) return cur;
+    if (cur < count && gv_kidx_equal_n<R>(rows + (size_t)cur * R, row)) return cur;
   }
   return GV_KIDX_EMPTY;
+}
+GV_KIDX_FN uint32_t gv_kidx_find(const uint32_t* table, uint32_t tmask, const uint32_t* rows, uint32_t count,
+                                 const uint32_t row[GV_KIDX_ROW], uint64_t seed) {
+  return gv_kidx_find_n<GV_KIDX_ROW>(table, tmask, rows, count, row, seed);
+}
+
+// The ed25519 row of the 32 key bytes at p (any alignment): what k_ed_keys /
+// k_ed_keys_chain write to the slot's ekpub row.
+GV_KIDX_FN void gv_edkidx_row(const uint8_t* p, uint32_t row[GV_EDKIDX_ROW]) {
+  for (int i = 0; i < GV_EDKIDX_ROW; ++i) {
+    const uint8_t* q = p + 4 * i;
+    row[i] = (uint32_t)q[0] | ((uint32_t)q[1] << 8) | ((uint32_t)q[2] << 16) | ((uint32_t)q[3] << 24);
+  }
 }

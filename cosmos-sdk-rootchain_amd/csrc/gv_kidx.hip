@@ -58,6 +58,44 @@ __global__ __launch_bounds__(256) void k_kidx_find(const u32* table, u32 tmask, 
   wave_count(g < n && slot == GV_KIDX_EMPTY, miss);
 }
 
+// ---- the ed25519 arena's pubkey index (option "ed_keys_index"; DESIGN
+// section 4.3e): the same table and routines over 8-word rows, which are the
+// arena's own ekpub rows (k_ed_keys / k_ed_keys_chain write them), so no
+// row-writing kernel exists.
+//
+// Slot base + g (or slots[g]) enters the table; the lanes share table words
+// only (atomicCAS / atomicMin, gv_kidx.h).
+__global__ __launch_bounds__(256) void k_edkidx_put(u32* table, u32 tmask, const u32* rows, u32 n, u32 base,
+                                                     const u32* slots, uint64_t seed, u32* left_out) {
+  const u32 g = blockIdx.x * blockDim.x + threadIdx.x;
+  bool out = false;
+  if (g < n) out = !gv_kidx_put_n<GV_EDKIDX_ROW>(table, tmask, rows, slots ? slots[g] : base + g, seed);
+  wave_count(out, left_out);
+}
+
+// Item g's 32 bytes (the caller's AoS pub32, any alignment) -> slot_out[g]:
+// the lowest slot below `count` holding exactly those bytes, or GV_KIDX_EMPTY.
+// miss (may be null) counts the items not found.
+__global__ __launch_bounds__(256) void k_edkidx_find(const u32* table, u32 tmask, const u32* rows, u32 count,
+                                                      uint64_t seed, const uint8_t* pub32, u32 n, u32* slot_out,
+                                                      u32* miss) {
+  const u32 g = blockIdx.x * blockDim.x + threadIdx.x;
+  u32 slot = 0;
+  if (g < n) {
+    u32 row[GV_EDKIDX_ROW];
+    const uint8_t* p = pub32 + (size_t)g * 32u;
+    if (((uintptr_t)pub32 & 3u) == 0) {                  // kernel-uniform: whole words
+#pragma unroll
+      for (int i = 0; i < GV_EDKIDX_ROW; ++i) row[i] = ((const u32*)p)[i];
+    } else {
+      gv_edkidx_row(p, row);
+    }
+    slot = gv_kidx_find_n<GV_EDKIDX_ROW>(table, tmask, rows, count, row, seed);
+    slot_out[g] = slot;
+  }
+  wave_count(g < n && slot == GV_KIDX_EMPTY, miss);
+}
+
 // ---- a routed batch with a few keys that are not resident (option
 // "keys_index_split").
 //
@@ -221,7 +259,25 @@ hipError_t gvk_kidx_find(const uint32_t* table, uint32_t tslots, const uint32_t*
   return hipGetLastError();
 }
 
-hipError_t gvk_kidx_split(const gvk_split* s, const uint32_t* slot, uint32_t n, const uint8_t* pub33,
+hipError_t gvk_edkidx_put(uint32_t* table, uint32_t tslots, const uint32_t* rows, uint32_t n, uint32_t base,
+                          const uint32_t* slots, uint64_t seed, uint32_t* left_out, hipStream_t st) {
+  if (n == 0) return hipSuccess;
+  if (tslots == 0 || (tslots & (tslots - 1))) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(gv::k_edkidx_put, dim3((n + 255) / 256), dim3(256), 0, st, table, tslots - 1, rows, n, base, slots,
+                     seed, left_out);
+  return hipGetLastError();
+}
+
+hipError_t gvk_edkidx_find(const uint32_t* table, uint32_t tslots, const uint32_t* rows, uint32_t count, uint64_t seed,
+                           const uint8_t* pub32, uint32_t n, uint32_t* slot_out, uint32_t* miss, hipStream_t st) {
+  if (n == 0) return hipSuccess;
+  if (tslots == 0 || (tslots & (tslots - 1))) return hipErrorInvalidValue;
+  hipLaunchKernelGGL(gv::k_edkidx_find, dim3((n + 255) / 256), dim3(256), 0, st, table, tslots - 1, rows, count, seed,
+                     pub32, n, slot_out, miss);
+  return hipGetLastError();
+}
+
+hipError_t gvk_kidx_split(const gvk_split* s,const uint32_t* slot, uint32_t n, const uint8_t* pub33,
                           const uint8_t* sig64, const uint8_t* dig32, const uint64_t* off, const uint32_t* len,
                           hipStream_t st) {
   if (n == 0) return hipSuccess;

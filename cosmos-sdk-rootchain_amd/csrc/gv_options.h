@@ -156,6 +156,12 @@ struct Options {
                                  // slot 0; 0 stops their use at once
   size_t ed_keys_wide_bytes = 0; // the wide ed25519 arena is never allocated larger than this ("ed_keys_wide_mb",
                                  // GV_ED_KEYS_WIDE_MB; 0 = no limit)
+  bool ed_keys_index = false;    // gv_ed_keys_load also keeps a device index of the ed25519 arena, 32 key bytes -> slot
+                                 // (gv_kidx.h at 8-word rows: the arena's own ekpub rows), and
+                                 // gv_dev_verify_ed25519_msgs runs a batch whose keys are all resident as the keyed
+                                 // call would ("ed_keys_index", GV_ED_KEYS_INDEX): taken by an
+                                 // arena started from slot 0; 0 stops its use at once
+  uint64_t ed_kidx_seed = 0;     // its hash seed, drawn at gv_open ("ed_keys_index_seed": a test hook)
   size_t ed_unc_lat_max = 2048;  // uncached ed25519 host batches up to this size take k_ed_lat_unc (one signature per block)
 };
 
@@ -178,7 +184,8 @@ enum Effect {
   FX_QUIESCE,      // every device lock, drain the pipelined ladders: no call launches on a mix of old and new state
   FX_ED_KEYS_MU,   // hold ed_keys_mu
   FX_KEYS_EMPTY,   // hold keys_mu; rejected unless the resident arena is empty
-  FX_POOLS         // every device lock; replace the staging pools after the store
+  FX_POOLS,        // every device lock; replace the staging pools after the store
+  FX_ED_KEYS_EMPTY // hold ed_keys_mu; rejected unless the ed25519 arena is empty
 };
 // How gv_open reads the row's environment variable.
 enum EnvRule {
@@ -303,6 +310,11 @@ constexpr Row kRowsLater[] = {
     {"group_promote_min", GVO(group_promote_min), A_RANGE, 0, kMaxItems, X_ASIS, FX_NONE, true},
     // the most non-resident items of a routed batch that are still split off (0: none; no variable)
     {"keys_index_split", GVO(keys_index_split), A_RANGE, 0, kMaxItems, X_ASIS, FX_NONE, true},
+    // taken by an ed25519 arena started from slot 0 from now on (a running arena
+    // keeps what it has until gv_ed_keys_reset); 0 stops the use of the index at once
+    {"ed_keys_index", GVO(ed_keys_index), A_BOOL, 0, 1, X_ASIS, FX_ED_KEYS_MU, true, "GV_ED_KEYS_INDEX", E_IS1},
+    // test hook: that index hash's seed, while no key is in the ed25519 arena
+    {"ed_keys_index_seed", GVO(ed_kidx_seed), A_ANY, 0, 0, X_ASIS, FX_ED_KEYS_EMPTY, false},
 };
 #undef GVO
 

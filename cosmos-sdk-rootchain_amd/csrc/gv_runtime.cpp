@@ -380,6 +380,19 @@ struct Dev {
   size_t edkd_s_cap = 0;
   hipEvent_t edkd_last = nullptr;
   hipStream_t edkd_last_st = nullptr;
+  // the ed25519 arena's pubkey index (option "ed_keys_index"; gv_kidx.h at
+  // GV_EDKIDX_ROW words): its rows are the arena's ekpub rows, so only the
+  // table is kept -- edkidx_T words (kidx_table_words(ekcap); a slot or
+  // GV_KIDX_EMPTY); edkidx_keys leading slots went through k_edkidx_put.
+  // edkidx_on: the running arena took the option at slot 0.  edkidx_failed: an
+  // allocation was refused or a launch failed (no index until
+  // gv_ed_keys_reset).  edkidx_cnt (device): [0] keys k_edkidx_put left out
+  // since the last refill, [16] the misses of the lookup in flight; edkidx_h:
+  // its pinned copy
+  uint32_t *edkidx_tab = nullptr, *edkidx_cnt = nullptr, *edkidx_h = nullptr;
+  size_t edkidx_T = 0, edkidx_keys = 0;
+  bool edkidx_on = false, edkidx_failed = false;
+  uint64_t edkidx_left_out = 0;
   uint8_t* edl_h = nullptr;                      // small keyed ed25519 batches: pinned inputs + verdicts (zero-copy)
   size_t edl_h_cap = 0;
   // ed25519 in-batch key grouping: per-batch key arena (comb tables of -A), pinned count, stats
@@ -781,6 +794,9 @@ struct gv_ctx {
   std::mutex ed_keys_mu;
   std::vector<uint8_t> ed_kpub;  // the raw keys per slot (large keyed batches run the throughput kernels on them)
   std::atomic<uint64_t> ed_keyed_wide{0};   // keyed batches / chunks that ran on wide tables since gv_open ("ed_keyed_wide")
+  // the ed25519 index (option "ed_keys_index"): pub32 device batches run keyed / that fell through, and
+  // k_edkidx_* launches since gv_open ("ed_keys_index_hit", "_miss", "_launches")
+  std::atomic<uint64_t> edkidx_hit{0}, edkidx_miss{0}, edkidx_launches{0};
 };
 
 namespace {
@@ -2380,6 +2396,7 @@ int gv_open(const int* dev_ids, int n_dev, gv_ctx** out) {
     ctx->opt.kidx_seed = ((uint64_t)rd() << 32) ^ (uint64_t)rd() ^
                      (uint64_t)std::chrono::steady_clock::now().time_since_epoch().count() * 0x9E3779B97F4A7C15ull ^
                      (uint64_t)(uintptr_t)ctx;
+    ctx->opt.ed_kidx_seed = ctx->opt.kidx_seed;     // (the ed25519 index: another table, the same secret)
   }
   ctx->opt.stage_threads = gvstage::stage_pool_threads(host_cpus(), (int)ids.size());
   for (size_t k = 0; k < ids.size(); ++k) {
@@ -2489,6 +2506,8 @@ void gv_close(gv_ctx* ctx) {
     for (uint32_t* p : {d->ektab, d->ekpub, d->ekok, d->ektabw}) if (p) (void)hipFree(p);
     if (d->edkd_s) (void)hipFree(d->edkd_s);
     if (d->edkd_last) (void)hipEventDestroy(d->edkd_last);
+    for (uint32_t* p : {d->edkidx_tab, d->edkidx_cnt}) if (p) (void)hipFree(p);
+    if (d->edkidx_h) (void)hipHostFree(d->edkidx_h);
     for (uint32_t* p : {d->kidx_rows, d->kidx_cnt}) if (p) (void)hipFree(p);   // (the table rides behind the rows)
     if (d->kidx_h) (void)hipHostFree(d->kidx_h);
     for (hipEvent_t e : d->kidx_ev) if (e) (void)hipEventDestroy(e);
@@ -2661,20 +2680,7 @@ int gv_verify_ed25519_msgs(gv_ctx* ctx, size_t n, const uint8_t* pub32, const ui
   return run_ed_host(ctx, n, hb);
 }
 
-int gv_dev_verify_ed25519_msgs(gv_ctx* ctx, int dev_slot, size_t n, const void* d_pub32, const void* d_sig64,
-                               const void* d_msg_blob, const void* d_msg_off, const void* d_msg_len, void* d_bits,
-                               void* stream) {
-  Dev* d = nullptr;
-  int rc = dev_common(ctx, dev_slot, n, d_pub32, d_sig64, d_bits, &d);
-  if (rc || n == 0) return rc;
-  if (!d_msg_off || !d_msg_len || ((uintptr_t)d_pub32 & 15) || ((uintptr_t)d_sig64 & 15)) return GV_EINVAL;
-  std::lock_guard<std::mutex> lk(d->mu);
-  CK(hipSetDevice(d->id));
-  hipStream_t st = stream ? (hipStream_t)stream : d->set[0].st;
-  order_after_pipeline(d, st);
-  return ed_launch(ctx->opt.time_kernels, d, n, (const uint8_t*)d_pub32, (const uint8_t*)d_sig64, (const uint8_t*)d_msg_blob,
-                   (const uint64_t*)d_msg_off, (const uint32_t*)d_msg_len, (uint64_t*)d_bits, st, ed_group_cfg(ctx));
-}
+// gv_dev_verify_ed25519_msgs: below, behind the keyed call whose body it shares (ed_dev_keyed).
 
 // ---- key arena
 namespace {
@@ -3143,6 +3149,98 @@ int ed_arena_quiesce(Dev* d) {
   if (d->edkd_last_st) CK(hipEventSynchronize(d->edkd_last));
   return GV_OK;
 }
+
+// ---- the ed25519 arena's pubkey index (option "ed_keys_index"; gv_kidx.h at
+// GV_EDKIDX_ROW words).  Its rows are d->ekpub, which the
+// table builds write; the callers hold ed_keys_mu and d->mu and have waited
+// for edkd_last.
+constexpr size_t kEdKidxCntBytes = 256;
+
+void edkidx_free(Dev* d) {
+  opt_free(d, d->edkidx_tab, d->edkidx_T * 4);
+  d->edkidx_T = 0;
+}
+// No index on this device until gv_ed_keys_reset: every call takes the routes
+// it takes without one.
+void edkidx_stop(Dev* d) {
+  (void)hipGetLastError();
+  edkidx_free(d);
+  d->edkidx_failed = true;
+  d->edkidx_keys = 0;
+  d->edkidx_left_out = 0;
+}
+// The index covers the arena as it stands (an empty arena: every key misses).
+bool edkidx_live(const gv_ctx* ctx, const Dev* d) {
+  if (!ctx->opt.ed_keys_index || d->edkidx_failed || d->edkidx_keys != ctx->ed_keys) return false;
+  return ctx->ed_keys == 0 || (d->edkidx_on && d->edkidx_tab);
+}
+
+// Empty the table and enter slots [0, count) from their ekpub rows.
+int edkidx_refill(gv_ctx* ctx, Dev* d, size_t count, hipStream_t st) {
+  CK(hipMemsetAsync(d->edkidx_tab, 0xFF, d->edkidx_T * 4, st));
+  CK(hipMemsetAsync(d->edkidx_cnt, 0, 4, st));
+  if (count) {
+    CK(gvk_edkidx_put(d->edkidx_tab, (uint32_t)d->edkidx_T, d->ekpub, (uint32_t)count, 0, nullptr, ctx->opt.ed_kidx_seed,
+                      d->edkidx_cnt, st));
+    ctx->edkidx_launches++;
+  }
+  return GV_OK;
+}
+
+int edkidx_read_left_out(Dev* d, hipStream_t st) {
+  CK(hipMemcpyAsync(d->edkidx_h + 8, d->edkidx_cnt, 4, hipMemcpyDeviceToHost, st));
+  CK(hipStreamSynchronize(st));
+  d->edkidx_left_out = d->edkidx_h[8];
+  return GV_OK;
+}
+
+// After a load has written the rows of slots [base, base + n): the table for
+// the arena's capacity (d->ekcap), charged to the HBM budget like the other
+// optional tables, and the new slots into it.  A table that had to grow, and
+// one of an arena restarted from slot 0, is filled from every row.
+int edkidx_load(gv_ctx* ctx, Dev* d, hipStream_t st, size_t n, size_t base) {
+  if (!d->edkidx_cnt) {
+    if (!(d->edkidx_cnt = opt_alloc(ctx, d, kEdKidxCntBytes))) return GV_ENOMEM;
+    CK(hipMemsetAsync(d->edkidx_cnt, 0, kEdKidxCntBytes, st));
+  }
+  if (!d->edkidx_h && hipHostMalloc((void**)&d->edkidx_h, 64, hipHostMallocDefault) != hipSuccess) {
+    d->edkidx_h = nullptr;
+    return GV_ENOMEM;
+  }
+  const size_t T = kidx_table_words(d->ekcap);
+  if (T > (size_t(1) << 31)) return GV_ENOMEM;
+  int rc;
+  if (!d->edkidx_tab || d->edkidx_T < T) {
+    uint32_t* tab = opt_alloc(ctx, d, T * 4);
+    if (!tab) return GV_ENOMEM;
+    edkidx_free(d);
+    d->edkidx_tab = tab;
+    d->edkidx_T = T;
+    if ((rc = edkidx_refill(ctx, d, base + n, st))) return rc;
+  } else if (base == 0) {
+    if ((rc = edkidx_refill(ctx, d, n, st))) return rc;
+  } else {
+    CK(gvk_edkidx_put(d->edkidx_tab, (uint32_t)d->edkidx_T, d->ekpub, (uint32_t)n, (uint32_t)base, nullptr,
+                      ctx->opt.ed_kidx_seed, d->edkidx_cnt, st));
+    ctx->edkidx_launches++;
+  }
+  return edkidx_read_left_out(d, st);
+}
+
+// The slots of a pub32 device batch (n items, device AoS) into `out` (n
+// words): k_edkidx_find on st, then one 4-byte read-back of the miss count and
+// a sync, as kidx_lookup.  *nmiss: the items whose key was not found.
+int edkidx_lookup(gv_ctx* ctx, Dev* d, size_t n, const uint8_t* pub, uint32_t* out, hipStream_t st, size_t* nmiss) {
+  uint32_t* miss = d->edkidx_cnt + 16;
+  CK(hipMemsetAsync(miss, 0, 4, st));
+  CK(gvk_edkidx_find(d->edkidx_tab, (uint32_t)d->edkidx_T, d->ekpub, (uint32_t)ctx->ed_keys, ctx->opt.ed_kidx_seed, pub,
+                     (uint32_t)n, out, miss, st));
+  ctx->edkidx_launches++;
+  CK(hipMemcpyAsync(d->edkidx_h, miss, 4, hipMemcpyDeviceToHost, st));
+  CK(hipStreamSynchronize(st));
+  *nmiss = *d->edkidx_h;
+  return GV_OK;
+}
 }  // namespace
 
 int gv_ed_keys_load(gv_ctx* ctx, size_t n, const uint8_t* pub32, uint32_t* slot_out) {
@@ -3165,7 +3263,14 @@ int gv_ed_keys_load(gv_ctx* ctx, size_t n, const uint8_t* pub32, uint32_t* slot_
         free_ed_keys_wide(d);
         d->ekw_rb = ctx->opt.ed_keys_wide;
       }
+      d->edkidx_keys = 0;
+      d->edkidx_left_out = 0;
+      d->edkidx_failed = false;
+      d->edkidx_on = ctx->opt.ed_keys_index;        // the arena takes the option here
     }
+    // an earlier load that failed on a later device left this one's index ahead
+    // of the arena (slots the count does not cover): no index until gv_ed_keys_reset
+    if (d->edkidx_keys > base) edkidx_stop(d);
     rc = ensure_ed_keys(d, base + n, base, st, ctx->opt.ed_key_cap);
     if (!rc) rc = ed_build(ctx, d, st, pub32, n, base, nullptr);
     if (rc) return rc;
@@ -3180,6 +3285,13 @@ int gv_ed_keys_load(gv_ctx* ctx, size_t n, const uint8_t* pub32, uint32_t* slot_
         free_ed_keys_wide(d);
         d->ekw_full = true;
       }
+    }
+    // the index, behind the builds that wrote the slots' ekpub rows (the wide
+    // chain rewrites them with the same words); a refusal or a failure stops
+    // it until gv_ed_keys_reset: never an error
+    if (ctx->opt.ed_keys_index && d->edkidx_on && !d->edkidx_failed && d->edkidx_keys == base) {
+      if (edkidx_load(ctx, d, st, n, base) != GV_OK) edkidx_stop(d);
+      else d->edkidx_keys = base + n;
     }
   }
   ctx->ed_kpub.insert(ctx->ed_kpub.end(), pub32, pub32 + n * 32);
@@ -3205,7 +3317,16 @@ int gv_ed_keys_replace(gv_ctx* ctx, size_t n, const uint32_t* slots, const uint8
     if (count > d->ekcap || d->ekeysw > d->ekcapw) return GV_EINVAL;   // (never: the arenas hold their slots)
     int rc = ed_arena_quiesce(d);               // a batch already enqueued runs against the old keys
     if (!rc) rc = ed_build(ctx, d, d->set[0].st, pub32, n, 0, slots);
-    if (rc) return rc;
+    // the index names bytes: once rows may have changed it is refilled from
+    // every row or stopped, whatever "ed_keys_index" says now
+    const bool indexed = d->edkidx_tab && d->edkidx_keys && !d->edkidx_failed;
+    if (rc) {
+      if (indexed) edkidx_stop(d);
+      return rc;
+    }
+    if (indexed && (edkidx_refill(ctx, d, std::min(d->edkidx_keys, count), d->set[0].st) != GV_OK ||
+                    edkidx_read_left_out(d, d->set[0].st) != GV_OK))
+      edkidx_stop(d);
     if (d->ektabw && d->ekeysw) {               // the wide tables of the named slots that have them
       const uint32_t* sl = slots;
       const uint8_t* pb = pub32;
@@ -3269,6 +3390,9 @@ int gv_ed_keys_reset(gv_ctx* ctx) {
     std::lock_guard<std::mutex> lk(d->mu);
     d->ekeysw = 0;
     d->ekw_full = false;
+    d->edkidx_keys = 0;                           // the index too (its table is cleared by the next load from slot 0)
+    d->edkidx_left_out = 0;
+    d->edkidx_failed = false;
   }
   ctx->ed_keys_gen.fetch_add(1);
   return GV_OK;
@@ -3431,6 +3555,66 @@ int gv_verify_ed25519_msgs_keyed(gv_ctx* ctx, size_t n, const uint32_t* slot, co
 // verdict byte per item into the device's scratch; k_ed_pack_bits makes the
 // bitmap.  ed_keys_mu is held while the batch is enqueued and edkd_last is
 // recorded behind its last kernel: the arena's writers wait for it.
+//
+// ed_dev_keyed is that batch for both of its callers, which hold ed_keys_mu
+// and d->mu: gv_dev_verify_ed25519_msgs_keyed with the caller's d_slot, and
+// gv_dev_verify_ed25519_msgs (option "ed_keys_index") with d_slot null and the
+// batch's d_pub32 -- the slots are then looked up into the same scratch, n
+// words behind the sort's, by one k_edkidx_find ordered behind edkd_last like
+// every other user of it, and the host waits for the miss count.  Any miss:
+// *missed is set and nothing else was enqueued (the caller takes the pub32
+// route).  kcount > 0.
+namespace {
+int ed_dev_keyed(gv_ctx* ctx, Dev* d, size_t n, size_t kcount, const uint32_t* d_slot, const uint8_t* d_pub32,
+                 const void* d_sig64, const void* d_msg_blob, const void* d_msg_off, const void* d_msg_len, void* d_bits,
+                 hipStream_t st, bool* missed) {
+  int rc;
+  if ((rc = ed_ensure(d, 256, st))) return rc;    // the resident comb table of B
+  if (!d->edkd_last) CK(hipEventCreateWithFlags(&d->edkd_last, hipEventDisableTiming));
+  const bool small = n <= ctx->opt.ed_lat_max;
+  const bool sorted = !small && ctx->opt.sort_keys;
+  const size_t C = round_up(n, 256), nb = kcount + 1, tb = gvk_sort_temp_bytes((uint32_t)nb);
+  const size_t sw = sorted ? sort_words(C, nb, tb) : 0;
+  const size_t need = C + sw * 4 + (d_slot ? 0 : n * 4);
+  if (need > d->edkd_s_cap) {                     // the scratch grows: the last batch on it first
+    if (d->edkd_last_st) CK(hipEventSynchronize(d->edkd_last));
+    if ((rc = ensure_dev(&d->edkd_s, &d->edkd_s_cap, need))) return rc;
+  }
+  if (d->edkd_last_st && d->edkd_last_st != st) CK(hipStreamWaitEvent(st, d->edkd_last, 0));
+  if (!d_slot) {
+    uint32_t* found = (uint32_t*)(d->edkd_s + C + sw * 4);
+    size_t nmiss = 0;
+    if ((rc = edkidx_lookup(ctx, d, n, d_pub32, found, st, &nmiss))) return rc;
+    if (nmiss) {
+      *missed = true;
+      return GV_OK;
+    }
+    d_slot = found;
+  }
+  uint8_t* out8 = d->edkd_s;
+  if (small) {
+    const gvk_edl b = fill_edl(d, n, kcount, d_slot, (const uint8_t*)d_sig64, (const uint8_t*)d_msg_blob,
+                               (const uint64_t*)d_msg_off, (const uint32_t*)d_msg_len, out8);
+    CK(gvk_ed_lat(&b, st));
+  } else {
+    const uint32_t* btab16 = ed_btab16(d, ctx->opt.ed_btab16, st);
+    const uint32_t* perm = nullptr;
+    if (sorted) {
+      const gvk_sort so = carve_sort((uint32_t*)(d->edkd_s + C), C, nb, tb);
+      CK(gvk_sort_slots(&so, (uint32_t)n, d_slot, (uint32_t)kcount, st));
+      perm = so.perm;
+    }
+    const gvk_edk b = fill_edk(ctx, d, n, kcount, perm, d_slot, (const uint8_t*)d_sig64, (const uint8_t*)d_msg_blob,
+                               (const uint64_t*)d_msg_off, (const uint32_t*)d_msg_len, out8, btab16);
+    CK(gvk_ed_keyed(&b, st));
+  }
+  CK(gvk_ed_pack_bits((uint32_t)n, out8, (uint64_t*)d_bits, st));
+  CK(hipEventRecord(d->edkd_last, st));
+  d->edkd_last_st = st;
+  return GV_OK;
+}
+}  // namespace
+
 int gv_dev_verify_ed25519_msgs_keyed(gv_ctx* ctx, int dev_slot, size_t n, const void* d_slot, const void* d_sig64,
                                      const void* d_msg_blob, const void* d_msg_off, const void* d_msg_len,
                                      void* d_bits, void* stream) {
@@ -3449,36 +3633,93 @@ int gv_dev_verify_ed25519_msgs_keyed(gv_ctx* ctx, int dev_slot, size_t n, const 
     CK(hipMemsetAsync(d_bits, 0, (n + 63) / 64 * 8, st));
     return GV_OK;
   }
-  if ((rc = ed_ensure(d, 256, st))) return rc;    // the resident comb table of B
+  return ed_dev_keyed(ctx, d, n, kcount, (const uint32_t*)d_slot, nullptr, d_sig64, d_msg_blob, d_msg_off, d_msg_len,
+                      d_bits, st, nullptr);
+}
+
+// gv_dev_verify_ed25519_msgs: device-resident pub32 items.  With
+// "ed_keys_index" on it takes ed_keys_mu, then d->mu, and a batch whose keys
+// the live index all names runs as gv_dev_verify_ed25519_msgs_keyed would with
+// those slots (one hit); any miss (one miss) and every other case run
+// ed_launch as before.  Off: d->mu alone, as ever.
+int gv_dev_verify_ed25519_msgs(gv_ctx* ctx, int dev_slot, size_t n, const void* d_pub32, const void* d_sig64,
+                               const void* d_msg_blob, const void* d_msg_off, const void* d_msg_len, void* d_bits,
+                               void* stream) {
+  Dev* d = nullptr;
+  int rc = dev_common(ctx, dev_slot, n, d_pub32, d_sig64, d_bits, &d);
+  if (rc || n == 0) return rc;
+  if (!d_msg_off || !d_msg_len || ((uintptr_t)d_pub32 & 15) || ((uintptr_t)d_sig64 & 15)) return GV_EINVAL;
+  std::unique_lock<std::mutex> kl;
+  if (ctx->opt.ed_keys_index) kl = std::unique_lock<std::mutex>(ctx->ed_keys_mu);
+  std::lock_guard<std::mutex> lk(d->mu);
+  CK(hipSetDevice(d->id));
+  hipStream_t st = stream ? (hipStream_t)stream : d->set[0].st;
+  order_after_pipeline(d, st);
+  if (kl.owns_lock() && ctx->opt.ed_keys_index && ctx->ed_keys && ctx->ed_keys <= d->ekcap && edkidx_live(ctx, d)) {
+    bool missed = false;
+    if ((rc = ed_dev_keyed(ctx, d, n, ctx->ed_keys, nullptr, (const uint8_t*)d_pub32, d_sig64, d_msg_blob, d_msg_off,
+                           d_msg_len, d_bits, st, &missed)))
+      return rc;
+    (missed ? ctx->edkidx_miss : ctx->edkidx_hit)++;
+    if (!missed) return GV_OK;
+  }
+  return ed_launch(ctx->opt.time_kernels, d, n, (const uint8_t*)d_pub32, (const uint8_t*)d_sig64, (const uint8_t*)d_msg_blob,
+                   (const uint64_t*)d_msg_off, (const uint32_t*)d_msg_len, (uint64_t*)d_bits, st, ed_group_cfg(ctx));
+}
+
+int gv_ed_keys_find(gv_ctx* ctx, size_t n, const uint8_t* pub32, uint32_t* slot_out) {
+  if (!ctx) return GV_EINVAL;
+  if (n == 0) return GV_OK;
+  if (!pub32 || !slot_out || n > kMaxItems) return GV_EINVAL;
+  std::lock_guard<std::mutex> kl(ctx->ed_keys_mu);
+  Dev* d = ctx->devs[0];
+  std::lock_guard<std::mutex> lk(d->mu);
+  if (!edkidx_live(ctx, d)) return GV_EINVAL;   // cannot tell (not: not resident)
+  if (ctx->ed_keys == 0) {
+    memset(slot_out, 0xFF, n * 4);
+    return GV_OK;
+  }
+  CK(hipSetDevice(d->id));
+  hipStream_t st = d->set[0].st;
+  uint8_t* buf = nullptr;
+  const size_t pb = round_up(n * 32, 256);
+  if (hipMalloc(&buf, pb + n * 4) != hipSuccess) return GV_ENOMEM;
+  int rc = GV_OK;
+  if (hipMemcpyAsync(buf, pub32, n * 32, hipMemcpyHostToDevice, st) != hipSuccess ||
+      gvk_edkidx_find(d->edkidx_tab, (uint32_t)d->edkidx_T, d->ekpub, (uint32_t)ctx->ed_keys, ctx->opt.ed_kidx_seed, buf,
+                      (uint32_t)n, (uint32_t*)(buf + pb), nullptr, st) != hipSuccess ||
+      hipMemcpyAsync(slot_out, buf + pb, n * 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
+      hipStreamSynchronize(st) != hipSuccess)
+    rc = GV_EHIP;
+  ctx->edkidx_launches++;
+  (void)hipFree(buf);
+  return rc;
+}
+
+// Asynchronous on `stream`: the lookup reads the table and the arena's rows,
+// so it is ordered behind edkd_last and recorded as the last reader of the
+// arena, like a keyed batch (gv_ed_keys_load / _replace wait for it).
+int gv_dev_ed_keys_find(gv_ctx* ctx, int dev_slot, size_t n, const void* d_pub32, void* d_slot_out, void* stream) {
+  if (!ctx) return GV_EINVAL;
+  if (dev_slot < 0 || dev_slot >= (int)ctx->devs.size()) return GV_ENODEV;
+  if (n == 0) return GV_OK;
+  if (!d_pub32 || !d_slot_out || ((uintptr_t)d_slot_out & 3) || n > kMaxItems) return GV_EINVAL;
+  Dev* d = ctx->devs[dev_slot];
+  std::lock_guard<std::mutex> kl(ctx->ed_keys_mu);
+  std::lock_guard<std::mutex> lk(d->mu);
+  if (!edkidx_live(ctx, d)) return GV_EINVAL;
+  CK(hipSetDevice(d->id));
+  hipStream_t st = stream ? (hipStream_t)stream : d->set[0].st;
+  order_after_pipeline(d, st);
+  if (ctx->ed_keys == 0) {
+    CK(hipMemsetAsync(d_slot_out, 0xFF, n * 4, st));
+    return GV_OK;
+  }
   if (!d->edkd_last) CK(hipEventCreateWithFlags(&d->edkd_last, hipEventDisableTiming));
-  const bool small = n <= ctx->opt.ed_lat_max;
-  const bool sorted = !small && ctx->opt.sort_keys;
-  const size_t C = round_up(n, 256), nb = kcount + 1, tb = gvk_sort_temp_bytes((uint32_t)nb);
-  const size_t sw = sorted ? sort_words(C, nb, tb) : 0;
-  if (C + sw * 4 > d->edkd_s_cap) {               // the scratch grows: the last batch on it first
-    if (d->edkd_last_st) CK(hipEventSynchronize(d->edkd_last));
-    if ((rc = ensure_dev(&d->edkd_s, &d->edkd_s_cap, C + sw * 4))) return rc;
-  }
   if (d->edkd_last_st && d->edkd_last_st != st) CK(hipStreamWaitEvent(st, d->edkd_last, 0));
-  uint8_t* out8 = d->edkd_s;
-  if (small) {
-    const gvk_edl b = fill_edl(d, n, kcount, (const uint32_t*)d_slot, (const uint8_t*)d_sig64,
-                               (const uint8_t*)d_msg_blob, (const uint64_t*)d_msg_off, (const uint32_t*)d_msg_len, out8);
-    CK(gvk_ed_lat(&b, st));
-  } else {
-    const uint32_t* btab16 = ed_btab16(d, ctx->opt.ed_btab16, st);
-    const uint32_t* perm = nullptr;
-    if (sorted) {
-      const gvk_sort so = carve_sort((uint32_t*)(d->edkd_s + C), C, nb, tb);
-      CK(gvk_sort_slots(&so, (uint32_t)n, (const uint32_t*)d_slot, (uint32_t)kcount, st));
-      perm = so.perm;
-    }
-    const gvk_edk b = fill_edk(ctx, d, n, kcount, perm, (const uint32_t*)d_slot, (const uint8_t*)d_sig64,
-                               (const uint8_t*)d_msg_blob, (const uint64_t*)d_msg_off, (const uint32_t*)d_msg_len, out8,
-                               btab16);
-    CK(gvk_ed_keyed(&b, st));
-  }
-  CK(gvk_ed_pack_bits((uint32_t)n, out8, (uint64_t*)d_bits, st));
+  CK(gvk_edkidx_find(d->edkidx_tab, (uint32_t)d->edkidx_T, d->ekpub, (uint32_t)ctx->ed_keys, ctx->opt.ed_kidx_seed,
+                     (const uint8_t*)d_pub32, (uint32_t)n, (uint32_t*)d_slot_out, nullptr, st));
+  ctx->edkidx_launches++;
   CK(hipEventRecord(d->edkd_last, st));
   d->edkd_last_st = st;
   return GV_OK;
@@ -3765,6 +4006,10 @@ int gv_get_option(gv_ctx* ctx, const char* key, long long* val) {
               {"keys_index_hit", (long long)ctx->kidx_hit.load()},     // pub33 device batches routed keyed
               {"keys_index_miss", (long long)ctx->kidx_miss.load()},   // ... that fell through on a miss
               {"keys_index_launches", (long long)ctx->kidx_launches.load()},   // k_kidx_* launches so far
+              // the same three for the ed25519 arena's index ("ed_keys_index"): pub32 device batches
+              {"ed_keys_index_hit", (long long)ctx->edkidx_hit.load()},
+              {"ed_keys_index_miss", (long long)ctx->edkidx_miss.load()},
+              {"ed_keys_index_launches", (long long)ctx->edkidx_launches.load()},
               // routed batches whose non-resident items were split off ("keys_index_split"), and those items
               {"keys_index_split_calls", (long long)ctx->kidx_split_calls.load()},
               {"keys_index_split_items", (long long)ctx->kidx_split_items.load()},
@@ -3791,10 +4036,16 @@ int gv_get_option(gv_ctx* ctx, const char* key, long long* val) {
   // whether it holds a built radix-2^16 comb table of B ("ed_btab16_live":
   // 0 also when the build failed and k_ed_keyed adds [s]B from the radix-256
   // table; reading it never builds the table)
-  const bool ed = !strcmp(key, "ed_kw_rb") || !strcmp(key, "ed_kw_keys");
+  // ... and its pubkey index, under the same four names behind "ed_"
+  const bool edi = !strncmp(key, "ed_keys_index_", 14);
+  const bool ed = !strcmp(key, "ed_kw_rb") || !strcmp(key, "ed_kw_keys") || edi;
   static const char* const kDev[] = {"kw_arena_qw", "kw_arena_ng", "keys_index_live", "keys_index_keys",
                                      "keys_index_left_out", "keys_index_words", "group_reuse_rows", "group_layout",
                                      "hbm_optional_bytes", "ed_btab16_live"};
+  static const char* const kEdIdx[] = {"ed_keys_index_live", "ed_keys_index_keys", "ed_keys_index_left_out",
+                                       "ed_keys_index_words"};
+  if (edi && std::none_of(std::begin(kEdIdx), std::end(kEdIdx), [&](const char* k) { return !strcmp(key, k); }))
+    return GV_EINVAL;
   if (!ed && std::none_of(std::begin(kDev), std::end(kDev), [&](const char* k) { return !strcmp(key, k); }))
     return GV_EINVAL;
   if (ctx->devs.empty()) return GV_EINVAL;
@@ -3803,6 +4054,7 @@ int gv_get_option(gv_ctx* ctx, const char* key, long long* val) {
   Dev* d = ctx->devs[0];
   std::lock_guard<std::mutex> lk(d->mu);
   const bool kw = d->kw.qt && d->keysw, has = d->kidx_tab && !d->kidx_failed, ekw = d->ektabw && d->ekeysw;
+  const bool ehas = d->edkidx_tab && !d->edkidx_failed;
   // (the row capacity of the first scratch set's grouping arena; 0: none yet)
   *val = !strcmp(key, "group_reuse_rows")      ? (long long)d->set[0].gk.cap
          // groups per key of the device's last grouped call (4: k4's and k6's layouts; 0: none yet); the
@@ -3816,6 +4068,10 @@ int gv_get_option(gv_ctx* ctx, const char* key, long long* val) {
          : !strcmp(key, "keys_index_keys")     ? (long long)(has ? d->kidx_keys : 0)
          : !strcmp(key, "keys_index_left_out") ? (long long)(has ? d->kidx_left_out : 0)
          : !strcmp(key, "keys_index_words")    ? (long long)(has ? d->kidx_T : 0)
+         : !strcmp(key, "ed_keys_index_live")     ? (long long)edkidx_live(ctx, d)
+         : !strcmp(key, "ed_keys_index_keys")     ? (long long)(ehas ? d->edkidx_keys : 0)
+         : !strcmp(key, "ed_keys_index_left_out") ? (long long)(ehas ? d->edkidx_left_out : 0)
+         : !strcmp(key, "ed_keys_index_words")    ? (long long)(ehas ? d->edkidx_T : 0)
          : !strcmp(key, "ed_kw_rb")            ? (ekw ? d->ekw_rb : 0)
                                                : (long long)(ekw ? d->ekeysw : 0);
   return GV_OK;
@@ -3853,6 +4109,10 @@ int gv_set_option(gv_ctx* ctx, const char* key, long long val) {
     case gvopt::FX_KEYS_EMPTY:
       kl = std::unique_lock<std::mutex>(ctx->keys_mu);
       if (ctx->keys != 0) return GV_EINVAL;
+      break;
+    case gvopt::FX_ED_KEYS_EMPTY:
+      kl = std::unique_lock<std::mutex>(ctx->ed_keys_mu);
+      if (ctx->ed_keys != 0) return GV_EINVAL;
       break;
   }
   // a quiescing option may pick the grouped route's table layout, and a fault

@@ -49,6 +49,7 @@ EXPORTED_SYMBOLS = (
     "gv_ed_keys_replace", "gv_ed_keys_point", "gv_dev_verify_ed25519_msgs_keyed", "gv_ed_keys_wide_point",
     "gv_submit_digests", "gv_submit_digests_keyed", "gv_submit_msgs", "gv_submit_msgs_keyed", "gv_wait",
     "gv_keys_find", "gv_dev_keys_find", "gv_debug_sl_op", "gv_keys_entry", "gv_group_entry",
+    "gv_ed_keys_find", "gv_dev_ed_keys_find",
 )
 
 # gv_debug_sl_op (csrc/gv_kernels.h): words per item, flags, status words, op codes
@@ -189,7 +190,8 @@ def load(path: str = LIB_PATH):
             getattr(L, name).restype = i32
     # (a library from before the pubkey index, loaded through GV_LIB for an A/B
     # run, lacks these two: the wrappers then raise AttributeError when called)
-    for name, args in (("gv_keys_find", [vp, sz, vp, vp]), ("gv_dev_keys_find", [vp, i32, sz, vp, vp, vp])):
+    for name, args in (("gv_keys_find", [vp, sz, vp, vp]), ("gv_dev_keys_find", [vp, i32, sz, vp, vp, vp]),
+                       ("gv_ed_keys_find", [vp, sz, vp, vp]), ("gv_dev_ed_keys_find", [vp, i32, sz, vp, vp, vp])):
         if hasattr(L, name):
             getattr(L, name).argtypes = args
             getattr(L, name).restype = i32
@@ -612,6 +614,42 @@ class Verifier:
             _check(self._L.gv_ed_keys_point(self._ctx, n, _ptr(slots), w, j, _ptr(enc), _ptr(pub), _ptr(ok)),
                    "gv_ed_keys_point")
         return enc, pub, ok
+
+    def ed_keys_find(self, pub32: np.ndarray) -> np.ndarray:
+        """The ed25519 arena's pubkey index (option "ed_keys_index"): for each (32,) key the
+        lowest slot holding exactly those bytes, or KEY_NOT_FOUND.  GpuVerifyError(GV_EINVAL)
+        when the context has no live index -- "cannot tell", not "not resident"."""
+        pub32 = np.asarray(pub32)
+        if pub32.dtype != np.uint8 or pub32.ndim != 2 or pub32.shape[1] != 32:
+            raise ValueError("ed_keys_find: pub32 must be an (n, 32) uint8 array")
+        pub32 = np.ascontiguousarray(pub32)
+        n = pub32.shape[0]
+        slots = np.full(n, self.KEY_NOT_FOUND, dtype=np.uint32)
+        if n:
+            _check(self._L.gv_ed_keys_find(self._ctx, n, _ptr(pub32), _ptr(slots)), "gv_ed_keys_find")
+        return slots
+
+    def dev_ed_keys_find(self, slot: int, n: int, d_pub, d_slots_out, stream=None):
+        """Device-resident ed_keys_find on device slot `slot`: d_pub = n x 32 key bytes (any
+        alignment), d_slots_out = n u32 words (4-byte aligned) -- device addresses (ints);
+        asynchronous on stream (a hipStream_t int; None: the library's).  The output feeds
+        dev_verify_ed25519_keyed."""
+        if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or n < 0:
+            raise ValueError("dev_ed_keys_find: n must be a non-negative integer")
+        if isinstance(slot, bool) or not isinstance(slot, (int, np.integer)):
+            raise ValueError("dev_ed_keys_find: slot must be a device slot number")
+        for name, a in (("d_pub", d_pub), ("d_slots_out", d_slots_out), ("stream", stream)):
+            if a is not None and (isinstance(a, bool) or not isinstance(a, (int, np.integer)) or a < 0):
+                raise ValueError(f"dev_ed_keys_find: {name} must be a device address (int)")
+        if n == 0:
+            return
+        if not d_pub or not d_slots_out:
+            raise ValueError("dev_ed_keys_find: d_pub and d_slots_out must not be null")
+        if d_slots_out & 3:
+            raise ValueError("dev_ed_keys_find: d_slots_out must be 4-byte aligned")
+        _check(self._L.gv_dev_ed_keys_find(self._ctx, int(slot), int(n), ctypes.c_void_p(d_pub),
+                                           ctypes.c_void_p(d_slots_out), ctypes.c_void_p(stream or 0)),
+               "gv_dev_ed_keys_find")
 
     def ed_keys_reset(self):
         _check(self._L.gv_ed_keys_reset(self._ctx), "gv_ed_keys_reset")

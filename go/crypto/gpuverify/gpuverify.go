@@ -261,6 +261,12 @@ type GPU struct {
 	// either way (default 0; no environment variable: the server forwards its
 	// keys-index-split with SetOption after "keys_index" and records it here).
 	KeysIndexSplit int
+	// EdKeysIndex: the same index for the ed25519 key arena, 32 key bytes ->
+	// slot (gv_set_option "ed_keys_index"): EdKeysFind answers from it, and
+	// device-resident pub32 batches whose keys are all resident run on the
+	// arena's tables.  Applies to an arena started from slot 0 (default false,
+	// env GV_ED_KEYS_INDEX=1).
+	EdKeysIndex bool
 	// Logger, when set, reports every call that fell back to the CPU.
 	Logger Logger
 
@@ -303,7 +309,7 @@ func Open(devices []int) (*GPU, error) {
 	g := &GPU{ctx: ctx, CPUBelow: DefaultCPUBelow, Keyed: true, KeyLoadMin: DefaultKeyLoadMin,
 		KeyCap: envInt("GV_KEY_CAP", DefaultKeyCap), EdKeyCap: envInt("GV_ED_KEY_CAP", DefaultEdKeyCap),
 		KeysWideQW: envInt("GV_KEYS_WIDE_QW", 0), EdKeysWide: envInt("GV_ED_KEYS_WIDE", 0),
-		KeysIndex: envInt("GV_KEYS_INDEX", 0) == 1,
+		KeysIndex: envInt("GV_KEYS_INDEX", 0) == 1, EdKeysIndex: envInt("GV_ED_KEYS_INDEX", 0) == 1,
 		slots: map[secp256k1.PubKeySecp256k1]uint32{}, edSlots: map[ed25519.PubKeyEd25519]uint32{}}
 	g.pool.ctx = ctx
 	// the library's arena growth doubles up to the reset points the shim uses
@@ -326,6 +332,12 @@ func Open(devices []int) (*GPU, error) {
 	}
 	if g.KeysIndex {
 		if err := g.SetOption("keys_index", 1); err != nil {
+			g.Close()
+			return nil, err
+		}
+	}
+	if g.EdKeysIndex {
+		if err := g.SetOption("ed_keys_index", 1); err != nil {
 			g.Close()
 			return nil, err
 		}
@@ -906,6 +918,31 @@ func (g *GPU) KeysFind(pub33 []byte) ([]uint32, error) {
 	copy(pb.b, pub33)
 	if rc := C.gv_keys_find(g.ctx, C.size_t(n), (*C.uint8_t)(pb.p), (*C.uint32_t)(sb.p)); rc != 0 {
 		return nil, fmt.Errorf("gpuverify: gv_keys_find: %d", int(rc))
+	}
+	slots := make([]uint32, n)
+	copy(slots, (*[maxBatchBytes / 4]uint32)(sb.p)[:n:n])
+	return slots, nil
+}
+
+// EdKeysFind is KeysFind for the ed25519 arena (gv_ed_keys_find, option
+// "ed_keys_index"): slots[i] is the lowest slot holding exactly the bytes
+// pub32[32*i:], or KeyNotFound.  The byte string is the identity: a
+// non-canonical encoding and its canonical twin are different keys.  An error
+// means "cannot tell" (no live index on this context), never "not resident".
+func (g *GPU) EdKeysFind(pub32 []byte) ([]uint32, error) {
+	if len(pub32)%32 != 0 {
+		return nil, fmt.Errorf("gpuverify: EdKeysFind: %d key bytes", len(pub32))
+	}
+	n := len(pub32) / 32
+	if n == 0 {
+		return nil, nil
+	}
+	pb := g.newCBuf(len(pub32))
+	sb := g.newCBuf(4 * n)
+	defer func() { pb.free(); sb.free() }()
+	copy(pb.b, pub32)
+	if rc := C.gv_ed_keys_find(g.ctx, C.size_t(n), (*C.uint8_t)(pb.p), (*C.uint32_t)(sb.p)); rc != 0 {
+		return nil, fmt.Errorf("gpuverify: gv_ed_keys_find: %d", int(rc))
 	}
 	slots := make([]uint32, n)
 	copy(slots, (*[maxBatchBytes / 4]uint32)(sb.p)[:n:n])

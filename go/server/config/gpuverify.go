@@ -59,6 +59,10 @@ type GPUVerifyConfig struct {
 	// verified by key bytes beside it (gv_set_option keys_index_split; 0 =
 	// any such item sends the whole batch to the pub33 routes).
 	KeysIndexSplit int `mapstructure:"keys-index-split"`
+	// EdKeysIndex: the same index for the ed25519 key arena (gv_set_option
+	// ed_keys_index; gv_ed_keys_find): device-resident pub32 batches whose keys
+	// are all resident run on the arena's tables.
+	EdKeysIndex bool `mapstructure:"ed-keys-index"`
 	// CacheEntries: the verdict cache (0 = no cache).
 	CacheEntries int `mapstructure:"cache-entries"`
 	// CheckTxWindowTxs / CheckTxWindow: the concurrent-CheckTx accumulation
@@ -77,7 +81,7 @@ type GPUVerifyConfig struct {
 func DefaultGPUVerifyConfig() GPUVerifyConfig {
 	return GPUVerifyConfig{
 		Enable: false, Devices: "", MaxBatch: 1 << 20, CPUBelow: 4, Keyed: true, KeyLoadMin: 4096,
-		KeyCap: 1 << 22, EdKeyCap: 1 << 16, KeyResident: 0, EdKeyResident: 0, KeysWideQW: 0, EdKeysWide: 0, KeysIndex: false, KeysIndexSplit: 0, CacheEntries: 1 << 20,
+		KeyCap: 1 << 22, EdKeyCap: 1 << 16, KeyResident: 0, EdKeyResident: 0, KeysWideQW: 0, EdKeysWide: 0, KeysIndex: false, KeysIndexSplit: 0, EdKeysIndex: false, CacheEntries: 1 << 20,
 		CheckTxWindowTxs: 64, CheckTxWindow: 200 * time.Microsecond, PreVerifyBlocks: true,
 	}
 }
@@ -181,6 +185,12 @@ keys-index = {{ .GPUVerify.KeysIndex }}
 # their key bytes beside it (0 = one such signature sends the whole batch to
 # the per-key route).  Same verdicts either way.
 keys-index-split = {{ .GPUVerify.KeysIndexSplit }}
+
+# Device-side index of the ed25519 key arena (32 key bytes -> slot, 8 bytes of
+# GPU memory per slot of capacity): ed25519 batches staged on the GPU run on the
+# resident tables when all their keys are resident.  Taken when the arena next
+# starts from slot 0.
+ed-keys-index = {{ .GPUVerify.EdKeysIndex }}
 
 # Verdict cache entries (0 disables it).
 cache-entries = {{ .GPUVerify.CacheEntries }}

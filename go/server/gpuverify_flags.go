@@ -28,6 +28,7 @@ const (
 	FlagGPUVerifyEdWide   = "gpu-verify.ed-keys-wide"
 	FlagGPUVerifyKeysIdx  = "gpu-verify.keys-index"
 	FlagGPUVerifyKeysSplt = "gpu-verify.keys-index-split"
+	FlagGPUVerifyEdIdx    = "gpu-verify.ed-keys-index"
 )
 
 // AddGPUVerifyFlags registers the flags that override app.toml.
@@ -44,9 +45,10 @@ func AddGPUVerifyFlags(cmd *cobra.Command) {
 	cmd.Flags().Int(FlagGPUVerifyEdWide, d.EdKeysWide, "Wide ed25519 key tables: 0 (off), 6 or 8 radix bits")
 	cmd.Flags().Bool(FlagGPUVerifyKeysIdx, d.KeysIndex, "Device-side pubkey index of the account-key arena")
 	cmd.Flags().Int(FlagGPUVerifyKeysSplt, d.KeysIndexSplit, "Non-resident signatures per batch still verified beside the arena (0 = off)")
+	cmd.Flags().Bool(FlagGPUVerifyEdIdx, d.EdKeysIndex, "Device-side pubkey index of the ed25519 key arena")
 	for _, f := range []string{FlagGPUVerify, FlagGPUVerifyDevices, FlagGPUVerifyMaxBatch, FlagGPUVerifyCPUBelow,
 		FlagGPUVerifyKeyed, FlagGPUVerifyWindow, FlagGPUVerifyResident, FlagGPUVerifyEdRes, FlagGPUVerifyEdWide,
-		FlagGPUVerifyKeysIdx, FlagGPUVerifyKeysSplt} {
+		FlagGPUVerifyKeysIdx, FlagGPUVerifyKeysSplt, FlagGPUVerifyEdIdx} {
 		_ = viper.BindPFlag(f, cmd.Flags().Lookup(f))
 	}
 }
@@ -98,6 +100,13 @@ func NewGPUVerifier(cfg config.GPUVerifyConfig, logger log.Logger) (gv.Verifier,
 			logger.Error("gpu-verify: keys-index-split not applied", "err", err)
 		} else {
 			g.KeysIndexSplit = cfg.KeysIndexSplit
+		}
+	}
+	if cfg.EdKeysIndex {
+		if err := g.SetOption("ed_keys_index", 1); err != nil {
+			logger.Error("gpu-verify: ed-keys-index not applied", "err", err)
+		} else {
+			g.EdKeysIndex = true
 		}
 	}
 	g.Logger = logger.With("module", "gpuverify")

@@ -306,7 +306,20 @@ int gv_verify_ed25519_msgs(gv_ctx* ctx, size_t n, const uint8_t* pub32, const ui
                            uint8_t* out_ok);
 /* Device-resident: d_pub32 (n x 32) and d_sig64 (n x 64) 16-byte aligned,
  * d_msg_off u64 / d_msg_len u32 per item; accept bitmap into d_bits
- * (ceil(n/64) u64 words).  Asynchronous on `stream` (NULL: the library's). */
+ * (ceil(n/64) u64 words).  Asynchronous on `stream` (NULL: the library's).
+ * With option "ed_keys_index" on, a non-empty ed25519 arena and a live index
+ * (gv_ed_keys_find, below) the call, at every n >= 1, first looks the batch's
+ * keys up on the device: one small kernel, then a 4-byte read-back of the
+ * miss count, for which the HOST WAITS -- the call blocks until everything
+ * enqueued on `stream` before it and the lookup have finished, as the routed
+ * secp256k1 calls do.  When every key is resident the batch then runs exactly
+ * as gv_dev_verify_ed25519_msgs_keyed would with those slots (same kernels by
+ * size, the wide tables when every slot has them, same bitmap write) and is
+ * asynchronous from there on; one or more keys not found sends the whole batch
+ * down the route it takes without the index.  Same verdicts either way; an
+ * index that cannot answer is never an error (only HIP failures are GV_EHIP).
+ * With the option on the call takes the arena's lock, then the device's, as
+ * the keyed call; off, the device's alone. */
 int gv_dev_verify_ed25519_msgs(gv_ctx* ctx, int dev_slot, size_t n, const void* d_pub32, const void* d_sig64,
                                const void* d_msg_blob, const void* d_msg_off, const void* d_msg_len, void* d_bits,
                                void* stream);
@@ -392,6 +405,34 @@ int gv_dev_verify_ed25519_msgs_keyed(gv_ctx* ctx, int dev_slot, size_t n, const 
  * device's wide arena under gv_ed_keys_point's locks. */
 int gv_ed_keys_wide_point(gv_ctx* ctx, size_t n, const uint32_t* slots, uint32_t w, uint32_t j, uint8_t* out_enc32,
                           uint8_t* out_ok);
+/* The ed25519 arena's pubkey index (option "ed_keys_index", below): which slot
+ * holds a key.  The arena already keeps each slot's 32 bytes as they were
+ * given (a key FromBytes rejects too); with the option on, gv_ed_keys_load and
+ * gv_ed_keys_replace also keep on every device a hash table over them.  The
+ * byte string is the identity, not the point: a non-canonical encoding and
+ * its canonical twin are different keys, as they are to the hash inside
+ * Verify.  A lookup returns a slot only after comparing all 32 bytes with
+ * that slot's, so verifying by the slot it returns gives exactly the pub32
+ * verdict.  The index may be incomplete -- a key whose probe finds no free
+ * word within 64 steps is left out ("ed_keys_index_left_out") and answers as
+ * not resident -- but it never names a slot with other bytes.
+ * gv_ed_keys_find: slot_out[i] = the lowest slot holding exactly the bytes
+ * pub32 + 32*i, or 0xFFFFFFFF.  Host buffers, the first device's index, under
+ * gv_ed_keys_point's locks.  GV_OK with every entry 0xFFFFFFFF on an empty
+ * arena (no launch); n == 0 is GV_OK; GV_EINVAL when ctx, pub32 or slot_out
+ * is NULL or the context has no live index ("ed_keys_index" 0, an arena
+ * started without it, an index its device's HBM budget refused): "cannot
+ * tell", which a caller must not take for "not resident". */
+int gv_ed_keys_find(gv_ctx* ctx, size_t n, const uint8_t* pub32, uint32_t* slot_out);
+/* The device-resident form, on dev_slot's index: d_pub32 = n x 32 key bytes
+ * (any alignment), d_slot_out = n u32 words (4-byte aligned; NULL or
+ * misaligned: GV_EINVAL and nothing is written).  Asynchronous on `stream`
+ * (NULL: the library's); its output can be passed straight to
+ * gv_dev_verify_ed25519_msgs_keyed on the same stream (across two streams the
+ * caller orders them).  It reads the arena as a keyed batch does and leaves
+ * the same event behind, so loads and replacements wait for it.  Same results
+ * and errors as gv_ed_keys_find; GV_ENODEV for a bad dev_slot. */
+int gv_dev_ed_keys_find(gv_ctx* ctx, int dev_slot, size_t n, const void* d_pub32, void* d_slot_out, void* stream);
 
 /* Options: "max_batch" (lanes per device launch, default 1<<20, at most
  * 0xFFFFFF00),
@@ -511,6 +552,19 @@ int gv_ed_keys_wide_point(gv_ctx* ctx, size_t n, const uint32_t* slots, uint32_t
  * gv_ed_keys_replace rebuilds the wide tables of the slots that have them),
  * "ed_keys_wide_mb" (MiB, 0 = no limit, the default; env GV_ED_KEYS_WIDE_MB:
  * the wide ed25519 arena is never allocated larger),
+ * "ed_keys_index" (0/1, else GV_EINVAL; default 0, env GV_ED_KEYS_INDEX: on for
+ * exactly "1": gv_ed_keys_load and gv_ed_keys_replace also keep the ed25519
+ * arena's pubkey index on every device -- a table of 4 B x T, T the power of
+ * two >= 2 x the arena's capacity and >= 512, over the key bytes the arena
+ * holds anyway; charged to "hbm_budget_mb"; a refused or failed allocation or
+ * a failed launch stops the index on that device until gv_ed_keys_reset and is
+ * never a gv_ed_keys_load / gv_ed_keys_replace error -- gv_ed_keys_find /
+ * gv_dev_ed_keys_find answer from it, and gv_dev_verify_ed25519_msgs runs a
+ * batch whose keys are all resident as the keyed call would, see there.  Taken
+ * by an arena started from slot 0: a running arena keeps what it has until
+ * gv_ed_keys_reset; 0 stops the use of the index at once),
+ * "ed_keys_index_seed" (test hook: the 64-bit seed of that index's hash, drawn
+ * per context at gv_open; GV_EINVAL unless the ed25519 arena is empty),
  * "ed_btab16" (0/1: k_ed_keyed -- cached keys past "ed_lat_max" and grouped
  * keys -- and the per-item throughput kernels add [s]B from a radix-2^16 comb table of B, j * 65536^w * B for
  * w < 16 and j <= 2^15 (56.6 MB per device, built on first use): 16
@@ -655,7 +709,13 @@ int gv_set_option(gv_ctx* ctx, const char* key, long long val);
  * that fell through on a miss, since gv_open), "keys_index_launches" (index
  * kernels launched since gv_open: 0 while the option has never been on) and
  * "keys_index_find_ns" (the last routed lookup's kernel, HIP events, with
- * "time_kernels" on), and "keys_index_split" with (read only)
+ * "time_kernels" on), and "ed_keys_index" with (read only)
+ * "ed_keys_index_live", "ed_keys_index_keys", "ed_keys_index_left_out",
+ * "ed_keys_index_words" (the first device's ed25519 index) and
+ * "ed_keys_index_hit" / "ed_keys_index_miss" / "ed_keys_index_launches" (pub32
+ * device batches run keyed / that fell through on a miss, and k_edkidx_*
+ * launches, since gv_open), each meaning what its "keys_index_*" counterpart
+ * means, and "keys_index_split" with (read only)
  * "keys_index_split_calls" / "keys_index_split_items" (routed batches whose
  * non-resident items were split off, and the sum of those items, since
  * gv_open: a split call counts in "keys_index_hit", not in "keys_index_miss"
