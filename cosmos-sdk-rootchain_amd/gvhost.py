@@ -104,7 +104,9 @@ def lib():
         L.gvh_deliver_block_codes.argtypes = [vp, sz, cpp, ctypes.POINTER(sz), ctypes.POINTER(ctypes.c_uint32)]
         L.gvh_deliver_blocks.argtypes = [vp, sz, ctypes.POINTER(sz), cpp, ctypes.POINTER(sz),
                                          ctypes.POINTER(ctypes.c_uint32)]
-        L.gvh_deliver_gentxs.argtypes = [vp, sz, cpp, ctypes.POINTER(sz), ctypes.POINTER(Result), ctypes.POINTER(sz)]
+        L.gvh_deliver_blocks_results.argtypes = [vp, sz, ctypes.POINTER(sz), cpp, ctypes.POINTER(sz),
+                                                 ctypes.POINTER(Result)]
+        L.gvh_deliver_gentxs.argtypes =[vp, sz, cpp, ctypes.POINTER(sz), ctypes.POINTER(Result), ctypes.POINTER(sz)]
         L.gvh_checktx.argtypes = [vp, ctypes.c_char_p, sz, ctypes.POINTER(Result)]
         L.gvh_set_window.argtypes = [vp, sz, ctypes.c_int64]
         L.gvh_set_cache_capacity.argtypes = [vp, sz]
@@ -265,6 +267,19 @@ class HostApp:
         out, k = [], 0
         for b in blocks:
             out.append(codes[k:k + len(b)])
+            k += len(b)
+        return rc, out
+
+    def deliver_blocks_results(self, blocks):
+        """deliver_blocks with every tx's full result: (rc, [[result dict per tx] per block])."""
+        flat = [tx for blk in blocks for tx in blk]
+        arr, lens = _arrays(flat)
+        bn = (ctypes.c_size_t * max(1, len(blocks)))(*[len(b) for b in blocks])
+        res = (Result * max(1, len(flat)))()
+        rc = self._L.gvh_deliver_blocks_results(self._app, len(blocks), bn, arr, lens, res)
+        out, k = [], 0
+        for b in blocks:
+            out.append([res[k + i].as_dict() for i in range(len(b))])
             k += len(b)
         return rc, out
 

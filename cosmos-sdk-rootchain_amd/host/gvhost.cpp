@@ -3134,7 +3134,7 @@ int deliver_block(gvh_app* app, size_t ntx, const uint8_t* const* txs, const siz
 // prediction that turns out wrong is a memo miss: the ante run rebuilds the
 // plan from the state and verifies it, never a different verdict).
 int deliver_blocks(gvh_app* app, size_t nb, const size_t* bn, const uint8_t* const* txs, const size_t* lens,
-                   uint32_t* codes) {
+                   gvh_result* out, uint32_t* codes) {
   if (nb == 0) return GVH_OK;
   auto ns_since = [](std::chrono::steady_clock::time_point t) {
     return (uint64_t)std::chrono::duration_cast<std::chrono::nanoseconds>(std::chrono::steady_clock::now() - t).count();
@@ -3178,7 +3178,7 @@ int deliver_blocks(gvh_app* app, size_t nb, const size_t* bn, const uint8_t* con
       if (prof) fprintf(stderr, "blocks %zu: front %.3f ms\n", b + 1, ns_since(tp) / 1e6);
     }
     const auto tl = std::chrono::steady_clock::now();
-    rc = deliver_memos(app, memos, nullptr, codes + off);
+    rc = deliver_memos(app, memos, out ? out + off : nullptr, codes ? codes + off : nullptr);
     app->st_loop_ns += ns_since(tl);
     release_memos(app, memos);
     if (prof) fprintf(stderr, "blocks %zu: loop+release %.3f ms\n", b, ns_since(tl) / 1e6);
@@ -3224,7 +3224,16 @@ int gvh_deliver_blocks(gvh_app* app, size_t n_blocks, const size_t* block_ntx, c
   size_t ntx = 0;
   for (size_t b = 0; b < n_blocks; ++b) ntx += block_ntx[b];
   if (ntx && (!txs || !lens || !codes)) return GVH_EINVAL;
-  return deliver_blocks(app, n_blocks, block_ntx, txs, lens, codes);
+  return deliver_blocks(app, n_blocks, block_ntx, txs, lens, nullptr, codes);
+}
+
+int gvh_deliver_blocks_results(gvh_app* app, size_t n_blocks, const size_t* block_ntx, const uint8_t* const* txs,
+                               const size_t* lens, gvh_result* out) {
+  if (!app || (n_blocks && !block_ntx)) return GVH_EINVAL;
+  size_t ntx = 0;
+  for (size_t b = 0; b < n_blocks; ++b) ntx += block_ntx[b];
+  if (ntx && (!txs || !lens || !out)) return GVH_EINVAL;
+  return deliver_blocks(app, n_blocks, block_ntx, txs, lens, out, nullptr);
 }
 
 int gvh_deliver_gentxs(gvh_app* app, size_t ntx, const uint8_t* const* txs, const size_t* lens, gvh_result* out,

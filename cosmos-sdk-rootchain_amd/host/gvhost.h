@@ -132,6 +132,9 @@ int gvh_deliver_block_codes(gvh_app* app, size_t ntx, const uint8_t* const* txs,
  * DeliverTx loop runs. */
 int gvh_deliver_blocks(gvh_app* app, size_t n_blocks, const size_t* block_ntx, const uint8_t* const* txs,
                        const size_t* lens, uint32_t* codes);
+/* Same, returning every tx's full result (out[i], concatenated like txs). */
+int gvh_deliver_blocks_results(gvh_app* app, size_t n_blocks, const size_t* block_ntx, const uint8_t* const* txs,
+                               const size_t* lens, gvh_result* out);
 /* genutil.DeliverGenTxs: the block path at height 0 (account number 0,
  * infinite gas); *first_failed = index of the first tx whose result is not OK
  * (the reference panics on it), or ntx if all passed. */

@@ -21,6 +21,10 @@ An account read is gaskv Get: 1000 + 3 x len(value); a write is Set: 2000 +
 The value is proto std.Account{BaseAccount} (std/codec.go:41-48,
 x/auth/types/types.proto:11-19).  GetParams = five Gets of amino-JSON uint64
 values (x/params/types/subspace.go:100-109,218-222; x/auth/types/params.go:55-62).
+Multisig keys nest: CountSubKeys (x/auth/types/stdtx.go:125-137), the gas
+consumer and VerifyBytes all recurse into a sub-key that is itself a multisig,
+and the Go panics on the way (a Multisignature that does not decode, an index
+past Elems / Sigs / PubKeys) are raised as Panic where the reference reaches them.
 Signature verdicts come from the oracle (secp256k1) and oracle.ed25519_ref.
 Absolute gas is parity-unpinned (no Go toolchain runs the reference); the
 ORDER of the charges is what this restatement exists to check.
@@ -88,6 +92,8 @@ def account_value_len(pub: bytes, number: int, seq: int) -> int:
 def _read_uvarint(b, i):
     x = s = 0
     while True:
+        if i >= len(b):
+            raise ValueError("EOF decoding uvarint")
         c = b[i]
         i += 1
         x |= (c & 0x7F) << s
@@ -108,7 +114,7 @@ def _fields(b):
             n, i = _read_uvarint(b, i)
             v, i = b[i:i + n], i + n
             if len(v) != n:
-                raise ValueError("truncated")
+                raise ValueError("insufficient bytes decoding byteslice")
         else:
             raise ValueError("wire type")
         out.append((f, wt, v))
@@ -134,19 +140,58 @@ def decode_pubkey(amino: bytes):
     raise ValueError("unknown pubkey")
 
 
+def count_subkeys(pk) -> int:
+    """types.CountSubKeys (x/auth/types/stdtx.go:125-137): the leaves of the key tree."""
+    if pk[0] != "multi":
+        return 1
+    return sum(count_subkeys(s) for s in pk[2])
+
+
+INDEX_PANIC = "runtime error: index out of range"
+
+
+class BitArray:
+    """tendermint libs/bits CompactBitArray as decoded (nil: no field 1).  Bits
+    are read one at a time, as Size / GetIndex do: GetIndex indexes Elems without
+    a bounds check of its own, so a bit below Size() whose byte is past Elems is
+    a Go index panic at the moment that bit is asked for."""
+
+    def __init__(self, present=False, extra=0, elems=b""):
+        self.present, self.extra, self.elems = present, extra, elems
+
+    def size(self) -> int:
+        if not self.present:
+            return 0
+        if self.extra == 0:
+            return 8 * len(self.elems)
+        return 8 * (len(self.elems) - 1) + self.extra
+
+    def get(self, i: int) -> bool:
+        if not self.present or i >= self.size():
+            return False
+        if i >> 3 >= len(self.elems):
+            raise Panic(INDEX_PANIC)
+        return bool(self.elems[i >> 3] >> (7 - i % 8) & 1)
+
+    def true_bits_before(self, n: int) -> int:
+        return sum(self.get(i) for i in range(n))
+
+
 def decode_multisig(sig: bytes):
-    """tendermint multisig.Multisignature: (bit list, [sigs])"""
-    bits, sigs = [], []
+    """tendermint multisig.Multisignature: (BitArray, [sigs]); ValueError on
+    bytes amino does not decode.  No bit is read here."""
+    bits, sigs = BitArray(), []
     for f, wt, v in _fields(sig):
         if f == 1 and wt == 2:
             extra, elems = 0, b""
             for g, wt2, w in _fields(v):
                 if g == 1 and wt2 == 0:
+                    if w > 255:
+                        raise ValueError("byte overflow")
                     extra = w
                 elif g == 2 and wt2 == 2:
                     elems = w
-            size = 8 * len(elems) if extra == 0 else 8 * (len(elems) - 1) + extra
-            bits = [bool(elems[i // 8] >> (7 - i % 8) & 1) for i in range(size)]
+            bits = BitArray(True, extra, elems)
         elif f == 2 and wt == 2:
             sigs.append(v)
         else:
@@ -163,14 +208,16 @@ def verify_bytes(pk, msg: bytes, sig: bytes) -> bool:
     _, k, subs = pk
     try:
         bits, sigs = decode_multisig(sig)
-    except Exception:
+    except ValueError:
         return False
-    size = len(bits)
-    if len(subs) != size or len(sigs) < k or len(sigs) > size or sum(bits) < k:
+    size = bits.size()
+    if len(subs) != size or len(sigs) < k or len(sigs) > size or bits.true_bits_before(size) < k:
         return False
     j = 0
-    for i, b in enumerate(bits):
-        if b:
+    for i in range(size):
+        if bits.get(i):
+            if j >= len(sigs):
+                raise Panic(INDEX_PANIC)
             if not verify_bytes(subs[i], msg, sigs[j]):
                 return False
             j += 1
@@ -214,6 +261,13 @@ class AnteRef:
         m.consume(WRITE_BYTE * acc.value_len(), "WritePerByte")
 
     def _sig_gas(self, m, sig, pk, top):
+        """DefaultSigVerificationGasConsumer (sigverify.go:299-322) and, for a
+        multisig, ConsumeMultisignatureVerificationGas (:325-338), which calls
+        back into it for every set bit and drops the error it returns (a nested
+        ed25519 key is charged and passes).  Its panics are not dropped: the
+        MustUnmarshalBinaryBare of a Multisignature at any depth, a bit whose
+        byte is past Elems, Sigs[sigIndex] and PubKeys[i] past their ends --
+        each raised when the loop gets there, after the charges before it."""
         if pk[0] == "ed":
             m.consume(self.cost_ed, "ante verify: ed25519")
             if top:
@@ -221,12 +275,33 @@ class AnteRef:
         elif pk[0] == "secp":
             m.consume(self.cost_secp, "ante verify: secp256k1")
         else:
-            bits, sigs = decode_multisig(sig)
+            try:
+                bits, sigs = decode_multisig(sig)
+            except ValueError as e:
+                raise Panic(str(e))
             j = 0
-            for i, b in enumerate(bits):
-                if b:
+            for i in range(bits.size()):
+                if bits.get(i):
+                    if j >= len(sigs) or i >= len(pk[2]):
+                        raise Panic(INDEX_PANIC)
                     self._sig_gas(m, sigs[j], pk[2][i], False)
                     j += 1
+
+    def consume_sig_gas(self, sig, pub, gas_limit=0):
+        """The gas consumer alone on a meter of its own (gas_limit 0: infinite):
+        (code, log, gas_used)."""
+        m = Meter(gas_limit or None)
+        try:
+            if not pub:
+                raise Fail(8, "unrecognized public key type: <nil>")
+            self._sig_gas(m, sig, decode_pubkey(pub), True)
+        except Fail as f:
+            return f.code, f"{f.msg}: {ERR_DESC[f.code]}", m.used
+        except Panic as p:
+            return 111222, f"{p}: panic", m.used
+        except OutOfGas as o:
+            return 11, f"out of gas in location: {o}: out of gas", m.used
+        return 0, "", m.used
 
     def ante(self, msgs, fee, memo, sigs, tx_len):
         """(code, log, gas_used) of one tx; state changes applied on success."""
@@ -259,8 +334,7 @@ class AnteRef:
             self._params(m)                                                   # ValidateSigCount
             count = 0
             for pub, _ in sigs:
-                pk = decode_pubkey(pub) if pub else None
-                count += len(pk[2]) if pk and pk[0] == "multi" else 1
+                count += count_subkeys(decode_pubkey(pub)) if pub else 1     # CountSubKeys(nil) = 1
                 if count > self.sig_limit:
                     raise Fail(14, f"signatures: {count}, limit: {self.sig_limit}")
             if self._read(m, signers[0]) is None:                              # DeductFee

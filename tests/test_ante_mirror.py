@@ -5,8 +5,11 @@
                                   TestSigVerification (:103-160), TestSigIntegration (:162-176)
   x/auth/ante/ante_test.go        TestAnteHandlerSigErrors (:92-138), TestAnteHandlerMultiSigner (:416-464),
                                   TestAnteHandlerBadSignBytes (:466-541), TestAnteHandlerSetPubKey (:543-593),
-                                  TestCountSubkeys (:627-659), TestAnteHandlerSigLimitExceeded (:661-698),
-                                  TestAnteHandlerReCheck (:747-826)
+                                  TestAnteHandlerSigLimitExceeded (:661-698), TestAnteHandlerReCheck (:747-826)
+
+TestCountSubkeys (:627-659) and every other path of a multisig key whose
+sub-key is a multisig are in tests/test_nested_multisig.py; the keys here
+have one level.
 
 Tests that never reach a secp256k1 verification run on the CPU (the host app
 has no verifier attached and would fail loudly if one were needed); the rest
