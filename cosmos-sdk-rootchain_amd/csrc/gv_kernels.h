@@ -479,34 +479,26 @@ hipError_t gvk_keys_entry(uint32_t n, const uint32_t* slots, const uint32_t* gro
                           const uint32_t* kqt, const uint32_t* kqt2, const uint32_t* kzq, uint32_t kC,
                           const uint32_t* kok, uint32_t kcount, uint32_t nt, uint32_t ew, uint32_t ng, uint8_t* out_xy,
                           uint8_t* out_ok, hipStream_t st);
-// The resident arena's pubkey index (gv_kidx.hip; gv_kidx.h: GV_KIDX_ROW words
-// per key row, a table of tslots words, a power of two, GV_KIDX_EMPTY or a
-// slot).  Keys and slots as the key-table builds take them: n keys for slots
-// base.., or for slots[g] (device, n words, bounded and distinct).
-// gvk_kidx_rows: the chunk's device pub33 -> the slots' key rows.
+// The pubkey index of the two resident key arenas (gv_kidx.hip; gv_kidx.h: a
+// key row of row_words words -- GV_KIDX_ROW for a pub33, GV_KIDX_ROW_ED for a
+// pub32, any other value is hipErrorInvalidValue -- and a table of tslots
+// words, a power of two, GV_KIDX_EMPTY or a slot).  Keys and slots as the
+// key-table builds take them: n keys for slots base.., or for slots[g]
+// (device, n words, bounded and distinct).
+// gvk_kidx_rows: the chunk's device pub33 -> the slots' key rows (the ed25519
+// arena's rows are its ekpub rows, written by gvk_ed_keys: no row kernel).
 // gvk_kidx_put: the slots enter the table (their rows written by an earlier
 // launch); *left_out += the keys that found no word within GV_KIDX_PROBE.
-// gvk_kidx_find: item g's 33 bytes (AoS, unaligned) -> slot_out[g], the lowest
-// slot below count holding exactly those bytes, or GV_KIDX_EMPTY; *miss (may
-// be null) += the items not found.
+// gvk_kidx_find: item g's 33 or 32 bytes (AoS, any alignment) -> slot_out[g],
+// the lowest slot below count holding exactly those bytes, or GV_KIDX_EMPTY;
+// *miss (may be null) += the items not found.
 hipError_t gvk_kidx_rows(const uint8_t* pub33, uint32_t n, uint32_t base, const uint32_t* slots, uint32_t* rows,
                          hipStream_t st);
-hipError_t gvk_kidx_put(uint32_t* table, uint32_t tslots, const uint32_t* rows, uint32_t n, uint32_t base,
-                        const uint32_t* slots, uint64_t seed, uint32_t* left_out, hipStream_t st);
-hipError_t gvk_kidx_find(const uint32_t* table, uint32_t tslots, const uint32_t* rows, uint32_t count, uint64_t seed,
-                         const uint8_t* pub33, uint32_t n, uint32_t* slot_out, uint32_t* miss, hipStream_t st);
-// The ed25519 arena's pubkey index (option "ed_keys_index"): the same table
-// over GV_EDKIDX_ROW-word rows, which are the arena's ekpub rows (written by
-// gvk_ed_keys), so there is no row kernel.
-// gvk_edkidx_put: slots base.. (or slots[g]) enter the table; *left_out += the
-// keys that found no word within GV_KIDX_PROBE.
-// gvk_edkidx_find: item g's 32 bytes (AoS, any alignment) -> slot_out[g], the
-// lowest slot below count holding exactly those bytes, or GV_KIDX_EMPTY; *miss
-// (may be null) += the items not found.
-hipError_t gvk_edkidx_put(uint32_t* table, uint32_t tslots, const uint32_t* rows, uint32_t n, uint32_t base,
-                          const uint32_t* slots, uint64_t seed, uint32_t* left_out, hipStream_t st);
-hipError_t gvk_edkidx_find(const uint32_t* table, uint32_t tslots, const uint32_t* rows, uint32_t count, uint64_t seed,
-                           const uint8_t* pub32, uint32_t n, uint32_t* slot_out, uint32_t* miss, hipStream_t st);
+hipError_t gvk_kidx_put(uint32_t row_words, uint32_t* table, uint32_t tslots, const uint32_t* rows, uint32_t n,
+                        uint32_t base, const uint32_t* slots, uint64_t seed, uint32_t* left_out, hipStream_t st);
+hipError_t gvk_kidx_find(uint32_t row_words, const uint32_t* table, uint32_t tslots, const uint32_t* rows,
+                         uint32_t count, uint64_t seed, const uint8_t* keys, uint32_t n, uint32_t* slot_out,
+                         uint32_t* miss, hipStream_t st);
 // A routed batch with a few keys that are not resident (option
 // "keys_index_split"): the dense sub-batch of those items, `cap` rows (device).
 // count: one word, the rows taken; idx[j]: the item of row j; pub33 / sig64 /

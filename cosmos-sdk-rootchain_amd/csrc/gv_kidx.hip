@@ -1,6 +1,7 @@
-// gv_kidx.hip -- kernels of the resident key arena's pubkey index (option
-// "keys_index"; gv_kidx.h holds the hash, the probe sequence, insert and
-// lookup), of a routed batch's split into resident and non-resident items
+// gv_kidx.hip -- kernels of the resident key arenas' pubkey index (options
+// "keys_index" and "ed_keys_index": one put and one find kernel, templates over
+// the row length; gv_kidx.h holds the row loader, the hash, the probe sequence,
+// insert and lookup), of a routed batch's split into resident and non-resident items
 // (option "keys_index_split"), and of the grouped route's per-set key-table
 // cache over the same routines (option "group_reuse").  All are one lane per
 // key or item, memory-bound and tiny beside a table build or a ladder.
@@ -25,72 +26,45 @@ __global__ __launch_bounds__(256) void k_kidx_rows(const uint8_t* pub33, u32 n, 
   const u32 g = blockIdx.x * blockDim.x + threadIdx.x;
   if (g >= n) return;
   u32 row[GV_KIDX_ROW];
-  gv_kidx_row(pub33 + (size_t)g * 33u, row);
+  gv_kidx_row_n<GV_KIDX_ROW>(pub33 + (size_t)g * 33u, row);
   u32* out = rows + (size_t)(slots ? slots[g] : base + g) * GV_KIDX_ROW;
 #pragma unroll
   for (int i = 0; i < GV_KIDX_ROW; ++i) out[i] = row[i];
 }
 
-// Slot base + g (or slots[g]) enters the table.  The rows were written by an
-// earlier launch; the lanes share table words only.
+// Slot base + g (or slots[g]) of an arena of R-word rows enters the table.
+// The rows were written by an earlier launch (k_kidx_rows, k_group_put; the
+// ed25519 arena's table builds); the lanes share table words only (atomicCAS /
+// atomicMin, gv_kidx.h).
+template <int R>
 __global__ __launch_bounds__(256) void k_kidx_put(u32* table, u32 tmask, const u32* rows, u32 n, u32 base,
                                                    const u32* slots, uint64_t seed, u32* left_out) {
   const u32 g = blockIdx.x * blockDim.x + threadIdx.x;
   bool out = false;
-  if (g < n) out = !gv_kidx_put(table, tmask, rows, slots ? slots[g] : base + g, seed);
+  if (g < n) out = !gv_kidx_put_n<R>(table, tmask, rows, slots ? slots[g] : base + g, seed);
   wave_count(out, left_out);
 }
 
-// Item g's 33 bytes (the caller's AoS pub33, unaligned) -> slot_out[g]: the
-// lowest slot holding exactly those bytes, or GV_KIDX_EMPTY.  miss (may be
-// null) counts the items not found.
-__global__ __launch_bounds__(256) void k_kidx_find(const u32* table, u32 tmask, const u32* rows, u32 count,
-                                                    uint64_t seed, const uint8_t* pub33, u32 n, u32* slot_out,
-                                                    u32* miss) {
-  const u32 g = blockIdx.x * blockDim.x + threadIdx.x;
-  u32 slot = 0;
-  if (g < n) {
-    u32 row[GV_KIDX_ROW];
-    gv_kidx_row(pub33 + (size_t)g * 33u, row);
-    slot = gv_kidx_find(table, tmask, rows, count, row, seed);
-    slot_out[g] = slot;
-  }
-  wave_count(g < n && slot == GV_KIDX_EMPTY, miss);
-}
-
-// ---- the ed25519 arena's pubkey index (option "ed_keys_index"; DESIGN
-// section 4.3e): the same table and routines over 8-word rows, which are the
-// arena's own ekpub rows (k_ed_keys / k_ed_keys_chain write them), so no
-// row-writing kernel exists.
-//
-// Slot base + g (or slots[g]) enters the table; the lanes share table words
-// only (atomicCAS / atomicMin, gv_kidx.h).
-__global__ __launch_bounds__(256) void k_edkidx_put(u32* table, u32 tmask, const u32* rows, u32 n, u32 base,
-                                                     const u32* slots, uint64_t seed, u32* left_out) {
-  const u32 g = blockIdx.x * blockDim.x + threadIdx.x;
-  bool out = false;
-  if (g < n) out = !gv_kidx_put_n<GV_EDKIDX_ROW>(table, tmask, rows, slots ? slots[g] : base + g, seed);
-  wave_count(out, left_out);
-}
-
-// Item g's 32 bytes (the caller's AoS pub32, any alignment) -> slot_out[g]:
-// the lowest slot below `count` holding exactly those bytes, or GV_KIDX_EMPTY.
+// Item g's key bytes (KB of them, by the row length; the caller's AoS, any alignment) -> slot_out[g]: the
+// lowest slot below `count` holding exactly those bytes, or GV_KIDX_EMPTY.
 // miss (may be null) counts the items not found.
-__global__ __launch_bounds__(256) void k_edkidx_find(const u32* table, u32 tmask, const u32* rows, u32 count,
-                                                      uint64_t seed, const uint8_t* pub32, u32 n, u32* slot_out,
-                                                      u32* miss) {
+template <int R>
+__global__ __launch_bounds__(256) void k_kidx_find(const u32* table, u32 tmask, const u32* rows, u32 count,
+                                                    uint64_t seed, const uint8_t* keys, u32 n, u32* slot_out,
+                                                    u32* miss) {
+  constexpr int KB = gv_kidx_key<R>::bytes;
   const u32 g = blockIdx.x * blockDim.x + threadIdx.x;
   u32 slot = 0;
   if (g < n) {
-    u32 row[GV_EDKIDX_ROW];
-    const uint8_t* p = pub32 + (size_t)g * 32u;
-    if (((uintptr_t)pub32 & 3u) == 0) {                  // kernel-uniform: whole words
+    u32 row[R];
+    const uint8_t* p = keys + (size_t)g * KB;
+    if (KB % 4 == 0 && ((uintptr_t)keys & 3u) == 0) {   // kernel-uniform: a pub32 batch as whole words
 #pragma unroll
-      for (int i = 0; i < GV_EDKIDX_ROW; ++i) row[i] = ((const u32*)p)[i];
+      for (int i = 0; i < R; ++i) row[i] = ((const u32*)p)[i];
     } else {
-      gv_edkidx_row(p, row);
+      gv_kidx_row_n<R>(p, row);
     }
-    slot = gv_kidx_find_n<GV_EDKIDX_ROW>(table, tmask, rows, count, row, seed);
+    slot = gv_kidx_find_n<R>(table, tmask, rows, count, row, seed);
     slot_out[g] = slot;
   }
   wave_count(g < n && slot == GV_KIDX_EMPTY, miss);
@@ -184,7 +158,7 @@ __global__ __launch_bounds__(256) void k_group_find(const u32* table, u32 tmask,
     key[0] = kpfx[u];
 #pragma unroll
     for (int i = 0; i < 8; ++i) key[1 + i] = kx[(size_t)i * CU + u];
-    r = gv_kidx_find(table, tmask, rows, count, key, seed);
+    r = gv_kidx_find_n<GV_KIDX_ROW>(table, tmask, rows, count, key, seed);
   }
   const bool missed = live && r == GV_KIDX_EMPTY;
   const uint64_t m = __ballot(missed);
@@ -241,39 +215,27 @@ hipError_t gvk_kidx_rows(const uint8_t* pub33, uint32_t n, uint32_t base, const 
   return hipGetLastError();
 }
 
-hipError_t gvk_kidx_put(uint32_t* table, uint32_t tslots, const uint32_t* rows, uint32_t n, uint32_t base,
-                        const uint32_t* slots, uint64_t seed, uint32_t* left_out, hipStream_t st) {
+// row_words picks the instantiation: GV_KIDX_ROW or GV_KIDX_ROW_ED, nothing else.
+hipError_t gvk_kidx_put(uint32_t row_words, uint32_t* table, uint32_t tslots, const uint32_t* rows, uint32_t n,
+                        uint32_t base, const uint32_t* slots, uint64_t seed, uint32_t* left_out, hipStream_t st) {
+  if (row_words != GV_KIDX_ROW && row_words != GV_KIDX_ROW_ED) return hipErrorInvalidValue;
   if (n == 0) return hipSuccess;
   if (tslots == 0 || (tslots & (tslots - 1))) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(gv::k_kidx_put, dim3((n + 255) / 256), dim3(256), 0, st, table, tslots - 1, rows, n, base, slots,
-                     seed, left_out);
+  const auto k = row_words == GV_KIDX_ROW ? gv::k_kidx_put<GV_KIDX_ROW> : gv::k_kidx_put<GV_KIDX_ROW_ED>;
+  hipLaunchKernelGGL(k, dim3((n + 255) / 256), dim3(256), 0, st, table, tslots - 1, rows, n, base, slots, seed,
+                     left_out);
   return hipGetLastError();
 }
 
-hipError_t gvk_kidx_find(const uint32_t* table, uint32_t tslots, const uint32_t* rows, uint32_t count, uint64_t seed,
-                         const uint8_t* pub33, uint32_t n, uint32_t* slot_out, uint32_t* miss, hipStream_t st) {
+hipError_t gvk_kidx_find(uint32_t row_words, const uint32_t* table, uint32_t tslots, const uint32_t* rows,
+                         uint32_t count, uint64_t seed, const uint8_t* keys, uint32_t n, uint32_t* slot_out,
+                         uint32_t* miss, hipStream_t st) {
+  if (row_words != GV_KIDX_ROW && row_words != GV_KIDX_ROW_ED) return hipErrorInvalidValue;
   if (n == 0) return hipSuccess;
   if (tslots == 0 || (tslots & (tslots - 1))) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(gv::k_kidx_find, dim3((n + 255) / 256), dim3(256), 0, st, table, tslots - 1, rows, count, seed,
-                     pub33, n, slot_out, miss);
-  return hipGetLastError();
-}
-
-hipError_t gvk_edkidx_put(uint32_t* table, uint32_t tslots, const uint32_t* rows, uint32_t n, uint32_t base,
-                          const uint32_t* slots, uint64_t seed, uint32_t* left_out, hipStream_t st) {
-  if (n == 0) return hipSuccess;
-  if (tslots == 0 || (tslots & (tslots - 1))) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(gv::k_edkidx_put, dim3((n + 255) / 256), dim3(256), 0, st, table, tslots - 1, rows, n, base, slots,
-                     seed, left_out);
-  return hipGetLastError();
-}
-
-hipError_t gvk_edkidx_find(const uint32_t* table, uint32_t tslots, const uint32_t* rows, uint32_t count, uint64_t seed,
-                           const uint8_t* pub32, uint32_t n, uint32_t* slot_out, uint32_t* miss, hipStream_t st) {
-  if (n == 0) return hipSuccess;
-  if (tslots == 0 || (tslots & (tslots - 1))) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(gv::k_edkidx_find, dim3((n + 255) / 256), dim3(256), 0, st, table, tslots - 1, rows, count, seed,
-                     pub32, n, slot_out, miss);
+  const auto k = row_words == GV_KIDX_ROW ? gv::k_kidx_find<GV_KIDX_ROW> : gv::k_kidx_find<GV_KIDX_ROW_ED>;
+  hipLaunchKernelGGL(k, dim3((n + 255) / 256), dim3(256), 0, st, table, tslots - 1, rows, count, seed, keys, n,
+                     slot_out, miss);
   return hipGetLastError();
 }
 
@@ -313,7 +275,7 @@ hipError_t gvk_group_put(uint32_t* table, uint32_t tslots, uint32_t* rows, uint6
   if (tslots == 0 || (tslots & (tslots - 1)) || n > CU) return hipErrorInvalidValue;
   const dim3 blk(256), grd((n + 255) / 256);
   hipLaunchKernelGGL(gv::k_group_put, grd, blk, 0, st, kx, kpfx, CU, list, n, base, rows, mx, mpfx);
-  hipLaunchKernelGGL(gv::k_kidx_put, grd, blk, 0, st, table, tslots - 1, (const uint32_t*)rows, n, base,
+  hipLaunchKernelGGL(gv::k_kidx_put<GV_KIDX_ROW>, grd, blk, 0, st, table, tslots - 1, (const uint32_t*)rows, n, base,
                      (const uint32_t*)nullptr, seed, (uint32_t*)nullptr);
   return hipGetLastError();
 }

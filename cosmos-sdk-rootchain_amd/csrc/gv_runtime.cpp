@@ -288,6 +288,40 @@ InLayout in_layout(size_t C, bool keyed, bool msgs) {
   return L;
 }
 
+// A key arena's pubkey index (options "keys_index" / "ed_keys_index";
+// gv_kidx.h; DESIGN sections 4.1j and 4.3e).  Per context: device batches the
+// index routed keyed / that fell through on a miss, and k_kidx_* launches
+// since gv_open ("keys_index_hit", "_miss", "_launches"; the same behind "ed_").
+struct KeyIndexStats {
+  std::atomic<uint64_t> hit{0}, miss{0}, launches{0};
+};
+// ... and per device: the key rows of `row` words per slot (the bytes as
+// loaded -- a rejected key's too), the table of T words (kidx_table_words of
+// the arena's capacity: a power of two >= 2 cap, >= 512; a slot or
+// GV_KIDX_EMPTY); `keys` leading slots went through k_kidx_put.  own_rows (the
+// secp256k1 index): rows of capacity cap and the table are one block, the
+// rows first; else (the ed25519 index) the rows are the arena's ekpub rows and
+// only the table is the index's.  on: the running arena took the option at
+// slot 0.  failed: an allocation was refused or a launch failed (no index
+// until the arena's reset).  cnt (device): [0] keys k_kidx_put left out since
+// the last refill (left_out: its last read-back), [16] the misses of the
+// lookup in flight; h: its pinned copy.  seed, stat: the context's.
+struct KeyIndex {
+  const uint32_t row;
+  const bool own_rows;
+  const uint64_t* seed = nullptr;
+  KeyIndexStats* stat = nullptr;
+  uint32_t *rows = nullptr, *tab = nullptr, *cnt = nullptr, *h = nullptr;
+  size_t cap = 0, T = 0, keys = 0;
+  bool on = false, failed = false;
+  uint64_t left_out = 0;
+  size_t key_bytes() const {
+    return row == GV_KIDX_ROW ? gv_kidx_key<GV_KIDX_ROW>::bytes : gv_kidx_key<GV_KIDX_ROW_ED>::bytes;
+  }
+  size_t bytes() const { return ((own_rows ? cap * row : 0) + T) * 4; }   // of the block it owns
+  bool filled() const { return tab && keys && !failed; }                  // some slot's bytes are in the table
+};
+
 struct Dev {
   int id = 0;
   uint32_t* gtab = nullptr;
@@ -318,19 +352,9 @@ struct Dev {
   KeyTabs kw;
   size_t keysw = 0;
   bool kw_full = false;
-  // the arena's pubkey index (option "keys_index"; gv_kidx.h): per slot the raw
-  // key row (GV_KIDX_ROW words: the prefix and x as k_unpack forms them, the
-  // bytes as loaded -- a rejected key's too), capacity kidx_cap = k4.cap; the
-  // table of kidx_T words (a power of two >= 2 k4.cap, >= 512; a slot or
-  // GV_KIDX_EMPTY); kidx_keys leading slots have their row and went through
-  // k_kidx_put.  kidx_on: the running arena took the option at slot 0.
-  // kidx_failed: an allocation was refused or a launch failed (no index until
-  // gv_keys_reset).  kidx_cnt (device): [0] keys k_kidx_put left out since the
-  // last refill, [16] the misses of the lookup in flight; kidx_h: its pinned copy
-  uint32_t *kidx_rows = nullptr, *kidx_tab = nullptr, *kidx_cnt = nullptr, *kidx_h = nullptr;
-  size_t kidx_cap = 0, kidx_T = 0, kidx_keys = 0;
-  bool kidx_on = false, kidx_failed = false;
-  uint64_t kidx_left_out = 0;
+  // the arena's pubkey index (option "keys_index"): rows of its own, the prefix
+  // and x as k_unpack forms them, capacity k4.cap
+  KeyIndex kidx{GV_KIDX_ROW, true};
   hipEvent_t kidx_ev[2] = {nullptr, nullptr};     // time_kernels: around the last routed lookup's k_kidx_find
   hipEvent_t kidx_found = nullptr;                // the last gv_dev_keys_find on the context stream: the next pipelined
   bool kidx_found_used = false;                   // calls' FRONT streams wait for it (their sort / k_prep read its slots)
@@ -380,19 +404,9 @@ struct Dev {
   size_t edkd_s_cap = 0;
   hipEvent_t edkd_last = nullptr;
   hipStream_t edkd_last_st = nullptr;
-  // the ed25519 arena's pubkey index (option "ed_keys_index"; gv_kidx.h at
-  // GV_EDKIDX_ROW words): its rows are the arena's ekpub rows, so only the
-  // table is kept -- edkidx_T words (kidx_table_words(ekcap); a slot or
-  // GV_KIDX_EMPTY); edkidx_keys leading slots went through k_edkidx_put.
-  // edkidx_on: the running arena took the option at slot 0.  edkidx_failed: an
-  // allocation was refused or a launch failed (no index until
-  // gv_ed_keys_reset).  edkidx_cnt (device): [0] keys k_edkidx_put left out
-  // since the last refill, [16] the misses of the lookup in flight; edkidx_h:
-  // its pinned copy
-  uint32_t *edkidx_tab = nullptr, *edkidx_cnt = nullptr, *edkidx_h = nullptr;
-  size_t edkidx_T = 0, edkidx_keys = 0;
-  bool edkidx_on = false, edkidx_failed = false;
-  uint64_t edkidx_left_out = 0;
+  // the ed25519 arena's pubkey index (option "ed_keys_index"): its rows are the
+  // arena's ekpub rows (ensure_ed_keys keeps ed_kidx.rows == ekpub)
+  KeyIndex ed_kidx{GV_KIDX_ROW_ED, false};
   uint8_t* edl_h = nullptr;                      // small keyed ed25519 batches: pinned inputs + verdicts (zero-copy)
   size_t edl_h_cap = 0;
   // ed25519 in-batch key grouping: per-batch key arena (comb tables of -A), pinned count, stats
@@ -776,8 +790,8 @@ struct gv_ctx {
   std::atomic<uint64_t> keys_gen{0};  // gv_keys_reset calls
   std::atomic<uint64_t> keys_replaced{0};   // slots gv_keys_replace rewrote since gv_open ("keys_replaced")
   std::mutex keys_mu;
-  std::atomic<uint64_t> kidx_hit{0}, kidx_miss{0};   // pub33 device batches routed keyed / that fell through
-  // ... routed with their non-resident items split off ("keys_index_split_calls"; they count in kidx_hit
+  KeyIndexStats kidx_stat;      // the arena's index: pub33 device batches (and the k_kidx_split / k_bits_merge launches)
+  // ... routed with their non-resident items split off ("keys_index_split_calls"; they count in kidx_stat.hit
   // too), and those items ("keys_index_split_items")
   std::atomic<uint64_t> kidx_split_calls{0}, kidx_split_items{0};
   // the grouped route's key-table cache (option "group_reuse"): keys whose tables were reused / built by calls
@@ -785,7 +799,6 @@ struct gv_ctx {
   std::atomic<uint64_t> grp_hit{0}, grp_built{0}, grp_reset{0}, grp_launches{0};
   // ... and its layout promotion (option "group_promote"): sets moved to the kg layout / back to k4's
   std::atomic<uint64_t> grp_promoted{0}, grp_demoted{0};
-  std::atomic<uint64_t> kidx_launches{0};            // k_kidx_* launches since gv_open ("keys_index_launches")
   std::atomic<uint64_t> kidx_find_ns{0};             // time_kernels: the last routed lookup's k_kidx_find
   // ed25519 key arena (gv_ed_keys_load), same on every device
   size_t ed_keys = 0;
@@ -794,9 +807,7 @@ struct gv_ctx {
   std::mutex ed_keys_mu;
   std::vector<uint8_t> ed_kpub;  // the raw keys per slot (large keyed batches run the throughput kernels on them)
   std::atomic<uint64_t> ed_keyed_wide{0};   // keyed batches / chunks that ran on wide tables since gv_open ("ed_keyed_wide")
-  // the ed25519 index (option "ed_keys_index"): pub32 device batches run keyed / that fell through, and
-  // k_edkidx_* launches since gv_open ("ed_keys_index_hit", "_miss", "_launches")
-  std::atomic<uint64_t> edkidx_hit{0}, edkidx_miss{0}, edkidx_launches{0};
+  KeyIndexStats ed_kidx_stat;   // the ed25519 arena's index: pub32 device batches
 };
 
 namespace {
@@ -1232,97 +1243,180 @@ void plan_sort(gv_ctx* ctx, Set* s, gvk_batch& b, uint32_t* base) {
   b.srt = so;
 }
 
-// ---- the resident arena's pubkey index (option "keys_index"; gv_kidx.h;
-// kidx_table_words: gv_keytabs.h)
-size_t kidx_bytes(size_t cap, size_t T) { return (cap * GV_KIDX_ROW + T) * 4; }
+// ---- the key arenas' pubkey index (KeyIndex above; gv_kidx.h;
+// kidx_table_words: gv_keytabs.h).  One set of functions serves d->kidx and
+// d->ed_kidx; the callers hold the arena's locks (d->mu; the ed25519 arena's
+// ed_keys_mu before it, and they have waited for edkd_last).
 constexpr size_t kKidxCntBytes = 256;
 
-void kidx_free(Dev* d) {
-  opt_free(d, d->kidx_rows, kidx_bytes(d->kidx_cap, d->kidx_T));   // one block: the rows, then the table
-  d->kidx_tab = nullptr;
-  d->kidx_cap = d->kidx_T = 0;
+void kidx_free(Dev* d, KeyIndex& ix) {
+  opt_free(d, ix.own_rows ? ix.rows : ix.tab, ix.bytes());   // (own rows: one block, the table behind them)
+  ix.tab = nullptr;
+  ix.cap = ix.T = 0;
 }
-// No index on this device until gv_keys_reset: every call takes the routes it
-// takes without one.
-void kidx_stop(Dev* d) {
+// No index on this device until the arena's reset: every call takes the routes
+// it takes without one.
+void kidx_stop(Dev* d, KeyIndex& ix) {
   (void)hipGetLastError();
-  kidx_free(d);
-  d->kidx_failed = true;
-  d->kidx_keys = 0;
+  kidx_free(d, ix);
+  ix.failed = true;
+  ix.keys = 0;
+  ix.left_out = 0;
 }
-// The index covers the arena as it stands (an empty arena: every key misses).
-bool kidx_live(const gv_ctx* ctx, const Dev* d) {
-  if (!ctx->opt.keys_index || d->kidx_failed || d->kidx_keys != ctx->keys) return false;
-  return ctx->keys == 0 || (d->kidx_on && d->kidx_tab);
+// The arena is empty again (its reset, or a load from slot 0): so is the
+// index -- the next load from slot 0 clears the table -- and a stopped one may
+// start again.
+void kidx_reset(KeyIndex& ix) {
+  ix.keys = 0;
+  ix.left_out = 0;
+  ix.failed = false;
+}
+// The index covers its arena of `count` slots as it stands (an empty arena:
+// every key misses).  enabled: the arena's option now.
+bool kidx_live(const KeyIndex& ix, bool enabled, size_t count) {
+  if (!enabled || ix.failed || ix.keys != count) return false;
+  return count == 0 || (ix.on && ix.tab);
+}
+bool kidx_live(const gv_ctx* ctx, const Dev* d) { return kidx_live(d->kidx, ctx->opt.keys_index, ctx->keys); }
+bool ed_kidx_live(const gv_ctx* ctx, const Dev* d) {
+  return kidx_live(d->ed_kidx, ctx->opt.ed_keys_index, ctx->ed_keys);
 }
 
-// Empty the table and enter slots [0, count) from their rows.
-int kidx_refill(gv_ctx* ctx, Dev* d, size_t count, hipStream_t st) {
-  CK(hipMemsetAsync(d->kidx_tab, 0xFF, d->kidx_T * 4, st));
-  CK(hipMemsetAsync(d->kidx_cnt, 0, 4, st));
-  if (count) {
-    CK(gvk_kidx_put(d->kidx_tab, (uint32_t)d->kidx_T, d->kidx_rows, (uint32_t)count, 0, nullptr, ctx->opt.kidx_seed,
-                    d->kidx_cnt, st));
-    ctx->kidx_launches++;
+// The counters and the pinned word, once per device.
+int kidx_setup(gv_ctx* ctx, Dev* d, KeyIndex& ix, hipStream_t st) {
+  if (!ix.cnt) {
+    if (!(ix.cnt = opt_alloc(ctx, d, kKidxCntBytes))) return GV_ENOMEM;
+    CK(hipMemsetAsync(ix.cnt, 0, kKidxCntBytes, st));
+  }
+  if (!ix.h && hipHostMalloc((void**)&ix.h, 64, hipHostMallocDefault) != hipSuccess) {
+    ix.h = nullptr;
+    return GV_ENOMEM;
   }
   return GV_OK;
 }
 
-// Rows and table for the arena's capacity (d->k4.cap), charged to the HBM budget
-// like the other optional tables.  On growth the rows of the first `used`
-// slots are copied and the table refilled from them.
-int kidx_ensure(gv_ctx* ctx, Dev* d, size_t used, hipStream_t st) {
-  if (!d->kidx_cnt) {
-    if (!(d->kidx_cnt = opt_alloc(ctx, d, kKidxCntBytes))) return GV_ENOMEM;
-    CK(hipMemsetAsync(d->kidx_cnt, 0, kKidxCntBytes, st));
-  }
-  if (!d->kidx_h && hipHostMalloc((void**)&d->kidx_h, 64, hipHostMallocDefault) != hipSuccess) {
-    d->kidx_h = nullptr;
-    return GV_ENOMEM;
-  }
-  if (d->kidx_rows && d->kidx_cap >= d->k4.cap) return GV_OK;
-  const size_t cap = d->k4.cap, T = kidx_table_words(cap);
-  if (T > (size_t(1) << 31)) return GV_ENOMEM;
-  uint32_t* rows = opt_alloc(ctx, d, kidx_bytes(cap, T));      // one block: the rows, then the table
-  if (!rows) return GV_ENOMEM;
-  uint32_t* tab = rows + cap * GV_KIDX_ROW;
-  used = d->kidx_rows ? std::min(used, d->kidx_keys) : 0;
-  if (used && (hipMemcpyAsync(rows, d->kidx_rows, used * GV_KIDX_ROW * 4, hipMemcpyDeviceToDevice, st) != hipSuccess ||
-               hipStreamSynchronize(st) != hipSuccess)) {
-    opt_free(d, rows, kidx_bytes(cap, T));
-    return GV_EHIP;
-  }
-  kidx_free(d);
-  d->kidx_rows = rows; d->kidx_tab = tab; d->kidx_cap = cap; d->kidx_T = T;
-  return kidx_refill(ctx, d, used, st);
+// Slots base.. (or d_slots[g]) enter the table from their rows; a launch counts.
+hipError_t kidx_put(KeyIndex& ix, size_t n, size_t base, const uint32_t* d_slots, hipStream_t st) {
+  if (n == 0) return hipSuccess;
+  const hipError_t e = gvk_kidx_put(ix.row, ix.tab, (uint32_t)ix.T, ix.rows, (uint32_t)n, (uint32_t)base, d_slots,
+                                    *ix.seed, ix.cnt, st);
+  if (e == hipSuccess) ix.stat->launches++;
+  return e;
+}
+// k_kidx_find over the arena's first `count` slots (the caller counts the launch).
+hipError_t kidx_find(const KeyIndex& ix, size_t count, const uint8_t* d_keys, size_t n, uint32_t* d_out,
+                     uint32_t* d_miss, hipStream_t st) {
+  return gvk_kidx_find(ix.row, ix.tab, (uint32_t)ix.T, ix.rows, (uint32_t)count, *ix.seed, d_keys, (uint32_t)n, d_out,
+                       d_miss, st);
 }
 
-// The slots of a pub33 device batch (n items, device AoS) into `out` (n
+// Empty the table and enter slots [0, count) from their rows.
+int kidx_refill(KeyIndex& ix, size_t count, hipStream_t st) {
+  CK(hipMemsetAsync(ix.tab, 0xFF, ix.T * 4, st));
+  CK(hipMemsetAsync(ix.cnt, 0, 4, st));
+  CK(kidx_put(ix, count, 0, nullptr, st));
+  return GV_OK;
+}
+// The keys the table's last fill and the appends since left out.
+int kidx_read_left_out(KeyIndex& ix, hipStream_t st) {
+  CK(hipMemcpyAsync(ix.h + 8, ix.cnt, 4, hipMemcpyDeviceToHost, st));
+  CK(hipStreamSynchronize(st));
+  ix.left_out = ix.h[8];
+  return GV_OK;
+}
+// After a replacement rewrote rows: the table again from the first `count`
+// rows -- the old bytes leave it, and the order of replacements does not
+// matter -- or no index.
+void kidx_refilled(Dev* d, KeyIndex& ix, size_t count, hipStream_t st) {
+  if (kidx_refill(ix, count, st) != GV_OK || kidx_read_left_out(ix, st) != GV_OK) kidx_stop(d, ix);
+}
+// A load that wrote the slots [base, base + n) also enters them into the
+// index while every earlier slot is in it (enabled: the arena's option now);
+// the arena's own load then decides kidx_stop or keys = base + n: a refused
+// allocation or a failed launch only stops the index on this device.
+bool kidx_appendable(const KeyIndex& ix, bool enabled, size_t base) {
+  return enabled && ix.on && !ix.failed && ix.keys == base;
+}
+
+// The secp256k1 index's rows and table for the arena's capacity (d->k4.cap),
+// charged to the HBM budget like the other optional tables.  On growth the
+// rows of the first `used` slots are copied and the table refilled from them.
+int kidx_ensure(gv_ctx* ctx, Dev* d, size_t used, hipStream_t st) {
+  KeyIndex& ix = d->kidx;
+  int rc;
+  if ((rc = kidx_setup(ctx, d, ix, st))) return rc;
+  if (ix.rows && ix.cap >= d->k4.cap) return GV_OK;
+  const size_t cap = d->k4.cap, T = kidx_table_words(cap), bytes = (cap * ix.row + T) * 4;
+  if (T > (size_t(1) << 31)) return GV_ENOMEM;
+  uint32_t* rows = opt_alloc(ctx, d, bytes);                  // one block: the rows, then the table
+  if (!rows) return GV_ENOMEM;
+  used = ix.rows ? std::min(used, ix.keys) : 0;
+  if (used && (hipMemcpyAsync(rows, ix.rows, used * ix.row * 4, hipMemcpyDeviceToDevice, st) != hipSuccess ||
+               hipStreamSynchronize(st) != hipSuccess)) {
+    opt_free(d, rows, bytes);
+    return GV_EHIP;
+  }
+  kidx_free(d, ix);
+  ix.rows = rows; ix.tab = rows + cap * ix.row; ix.cap = cap; ix.T = T;
+  return kidx_refill(ix, used, st);
+}
+
+// The slots of a device batch of keys (n items, device AoS) into `out` (n
 // words): k_kidx_find on st, then one 4-byte read-back of the miss count and
 // a sync -- what group_keys pays for its key count.  *nmiss: the items whose
-// key was not found (their word of `out` is GV_KIDX_EMPTY).
-int kidx_lookup(gv_ctx* ctx, Dev* d, size_t n, const uint8_t* pub, uint32_t* out, hipStream_t st, size_t* nmiss) {
-  uint32_t* miss = d->kidx_cnt + 16;
+// key was not found (their word of `out` is GV_KIDX_EMPTY).  ev (may be null):
+// two events recorded around the kernel.
+int kidx_lookup(KeyIndex& ix, size_t count, size_t n, const uint8_t* pub, uint32_t* out, hipStream_t st, size_t* nmiss,
+                hipEvent_t* ev) {
+  uint32_t* miss = ix.cnt + 16;
   CK(hipMemsetAsync(miss, 0, 4, st));
+  if (ev) CK(hipEventRecord(ev[0], st));
+  CK(kidx_find(ix, count, pub, n, out, miss, st));
+  ix.stat->launches++;
+  if (ev) CK(hipEventRecord(ev[1], st));
+  CK(hipMemcpyAsync(ix.h, miss, 4, hipMemcpyDeviceToHost, st));
+  CK(hipStreamSynchronize(st));
+  *nmiss = *ix.h;
+  return GV_OK;
+}
+// ... of a pub33 batch, timed with "time_kernels" on ("keys_index_find_ns").
+int kidx_lookup33(gv_ctx* ctx, Dev* d, size_t n, const uint8_t* pub, uint32_t* out, hipStream_t st, size_t* nmiss) {
   const bool timed = ctx->opt.time_kernels;
-  if (timed) {
+  if (timed)
     for (hipEvent_t& e : d->kidx_ev)
       if (!e) CK(hipEventCreate(&e));
-    CK(hipEventRecord(d->kidx_ev[0], st));
-  }
-  CK(gvk_kidx_find(d->kidx_tab, (uint32_t)d->kidx_T, d->kidx_rows, (uint32_t)ctx->keys, ctx->opt.kidx_seed, pub,
-                   (uint32_t)n, out, miss, st));
-  ctx->kidx_launches++;
-  if (timed) CK(hipEventRecord(d->kidx_ev[1], st));
-  CK(hipMemcpyAsync(d->kidx_h, miss, 4, hipMemcpyDeviceToHost, st));
-  CK(hipStreamSynchronize(st));
-  *nmiss = *d->kidx_h;
+  int rc;
+  if ((rc = kidx_lookup(d->kidx, ctx->keys, n, pub, out, st, nmiss, timed ? d->kidx_ev : nullptr))) return rc;
   if (timed) {
     float ms = 0;
     CK(hipEventElapsedTime(&ms, d->kidx_ev[0], d->kidx_ev[1]));
     ctx->kidx_find_ns = (uint64_t)(ms * 1e6f);
   }
   return GV_OK;
+}
+
+// gv_keys_find / gv_ed_keys_find on a live index of `count` slots: the n host
+// keys staged, looked up and the slots read back, in scratch of the call's
+// own.  The launch counts even when the call fails.
+int kidx_find_host(Dev* d, KeyIndex& ix, size_t count, size_t n, const uint8_t* pub, uint32_t* slot_out) {
+  if (count == 0) {
+    memset(slot_out, 0xFF, n * 4);
+    return GV_OK;
+  }
+  CK(hipSetDevice(d->id));
+  hipStream_t st = d->set[0].st;
+  uint8_t* buf = nullptr;
+  const size_t kb = ix.key_bytes(), pb = round_up(n * kb, 256);
+  if (hipMalloc(&buf, pb + n * 4) != hipSuccess) return GV_ENOMEM;
+  int rc = GV_OK;
+  if (hipMemcpyAsync(buf, pub, n * kb, hipMemcpyHostToDevice, st) != hipSuccess ||
+      kidx_find(ix, count, buf, n, (uint32_t*)(buf + pb), nullptr, st) != hipSuccess ||
+      hipMemcpyAsync(slot_out, buf + pb, n * 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
+      hipStreamSynchronize(st) != hipSuccess)
+    rc = GV_EHIP;
+  ix.stat->launches++;
+  (void)hipFree(buf);
+  return rc;
 }
 
 // The sub-batch buffers and the scratch set of a call on set s that splits
@@ -1457,16 +1551,16 @@ int launch(gv_ctx* ctx, Dev* d, Set* s, const Items& it, const LaunchOut& out, h
   size_t split = 0;                             // the items split off
   if (it.index && it.pub33 && !kslot && n > ctx->opt.lat_max && ctx->keys && kidx_live(ctx, d)) {
     size_t nmiss = 0;
-    if ((rc = kidx_lookup(ctx, d, n, it.pub33, s->qtab, st, &nmiss))) return rc;
+    if ((rc = kidx_lookup33(ctx, d, n, it.pub33, s->qtab, st, &nmiss))) return rc;
     const size_t bound = ctx->opt.keys_index_split;
     const bool wanted = kidx_split_ok(bound, nmiss, true, true);   // (the buffers are asked for only then)
     if (kidx_split_ok(bound, nmiss, true, wanted && miss_ensure(ctx, d, s, nmiss))) split = nmiss;
     via_index = nmiss == 0 || split;
     if (via_index) kslot = s->qtab;
-    (via_index ? ctx->kidx_hit : ctx->kidx_miss)++;
+    (via_index ? ctx->kidx_stat.hit : ctx->kidx_stat.miss)++;
     if (split) {
       CK(gvk_kidx_split(&s->miss, s->qtab, (uint32_t)n, it.pub33, it.sig64, it.dig32, it.off, it.len, st));
-      ctx->kidx_launches++;
+      ctx->kidx_stat.launches++;
       ctx->kidx_split_calls++;
       ctx->kidx_split_items += split;
     }
@@ -1582,7 +1676,7 @@ int launch(gv_ctx* ctx, Dev* d, Set* s, const Items& it, const LaunchOut& out, h
         CK(hipStreamWaitEvent(se, s->miss_done, 0));
       }
       CK(gvk_bits_merge(&m, (uint32_t)split, (uint32_t)n, out.bits, se));
-      ctx->kidx_launches++;
+      ctx->kidx_stat.launches++;
       if (pipelined && d->bits_rec) CK(hipEventRecord(d->bits_rec, se));
     }
   }
@@ -2402,6 +2496,10 @@ int gv_open(const int* dev_ids, int n_dev, gv_ctx** out) {
   for (size_t k = 0; k < ids.size(); ++k) {
     Dev* d = new Dev();
     d->id = ids[k];
+    d->kidx.seed = &ctx->opt.kidx_seed;
+    d->kidx.stat = &ctx->kidx_stat;
+    d->ed_kidx.seed = &ctx->opt.ed_kidx_seed;
+    d->ed_kidx.stat = &ctx->ed_kidx_stat;
     ctx->devs.push_back(d);
     d->pool = new Pool(ctx->opt.stage_threads - 1);
     if (k > 0) d->worker = new Worker();
@@ -2506,10 +2604,11 @@ void gv_close(gv_ctx* ctx) {
     for (uint32_t* p : {d->ektab, d->ekpub, d->ekok, d->ektabw}) if (p) (void)hipFree(p);
     if (d->edkd_s) (void)hipFree(d->edkd_s);
     if (d->edkd_last) (void)hipEventDestroy(d->edkd_last);
-    for (uint32_t* p : {d->edkidx_tab, d->edkidx_cnt}) if (p) (void)hipFree(p);
-    if (d->edkidx_h) (void)hipHostFree(d->edkidx_h);
-    for (uint32_t* p : {d->kidx_rows, d->kidx_cnt}) if (p) (void)hipFree(p);   // (the table rides behind the rows)
-    if (d->kidx_h) (void)hipHostFree(d->kidx_h);
+    for (KeyIndex* ix : {&d->kidx, &d->ed_kidx}) {
+      kidx_free(d, *ix);
+      if (ix->cnt) (void)hipFree(ix->cnt);
+      if (ix->h) (void)hipHostFree(ix->h);
+    }
     for (hipEvent_t e : d->kidx_ev) if (e) (void)hipEventDestroy(e);
     if (d->kidx_found) (void)hipEventDestroy(d->kidx_found);
     if (d->edl_h) (void)hipHostFree(d->edl_h);
@@ -2769,33 +2868,26 @@ int build_wide(gv_ctx* ctx, Dev* d, Set* s, hipStream_t st, const uint8_t* pub33
 // turns a rejected key's prefix into 00.
 int kidx_write(gv_ctx* ctx, Dev* d, Set* s, hipStream_t st, const uint8_t* pub33, size_t n, size_t base,
                const uint32_t* slots, bool put) {
+  KeyIndex& ix = d->kidx;
   return key_chunks(s, st, pub33, n, slots, ctx->opt.max_batch, nullptr,
                     [&](size_t c0, uint32_t cn, uint32_t, const uint32_t* d_slots) {
     const uint32_t b0 = slots ? 0u : (uint32_t)(base + c0);
-    hipError_t e = gvk_kidx_rows(s->d_in, cn, b0, d_slots, d->kidx_rows, st);
-    if (e == hipSuccess) ctx->kidx_launches++;
-    if (e == hipSuccess && put && (e = gvk_kidx_put(d->kidx_tab, (uint32_t)d->kidx_T, d->kidx_rows, cn, b0, d_slots,
-                                                    ctx->opt.kidx_seed, d->kidx_cnt, st)) == hipSuccess)
-      ctx->kidx_launches++;
+    hipError_t e = gvk_kidx_rows(s->d_in, cn, b0, d_slots, ix.rows, st);
+    if (e == hipSuccess) ix.stat->launches++;
+    if (e == hipSuccess && put) e = kidx_put(ix, cn, b0, d_slots, st);
     return e;
   });
-}
-// The keys the table's last fill and the appends since left out.
-int kidx_read_left_out(Dev* d, hipStream_t st) {
-  CK(hipMemcpyAsync(d->kidx_h + 8, d->kidx_cnt, 4, hipMemcpyDeviceToHost, st));
-  CK(hipStreamSynchronize(st));
-  d->kidx_left_out = d->kidx_h[8];
-  return GV_OK;
 }
 // gv_keys_load's part: rows and table entries of the new slots base.., after
 // their tables.
 int kidx_load(gv_ctx* ctx, Dev* d, Set* s, hipStream_t st, const uint8_t* pub33, size_t n, size_t base) {
   int rc;
-  const bool had = d->kidx_rows && d->kidx_cap >= d->k4.cap;
+  KeyIndex& ix = d->kidx;
+  const bool had = ix.rows && ix.cap >= d->k4.cap;
   if ((rc = kidx_ensure(ctx, d, base, st))) return rc;
-  if (base == 0 && had && (rc = kidx_refill(ctx, d, 0, st))) return rc;   // an arena restarted: the table is cleared
+  if (base == 0 && had && (rc = kidx_refill(ix, 0, st))) return rc;   // an arena restarted: the table is cleared
   if ((rc = kidx_write(ctx, d, s, st, pub33, n, base, nullptr, true))) return rc;
-  return kidx_read_left_out(d, st);
+  return kidx_read_left_out(ix, st);
 }
 
 // Affine 1*Q (64 bytes) and the verdict of the n slots `slots` (host) of the
@@ -2865,14 +2957,12 @@ int gv_keys_load(gv_ctx* ctx, size_t n, const uint8_t* pub33, uint32_t* slot_out
     if (base == 0) {                            // after gv_keys_reset the slots are rewritten from 0
       d->keys6 = d->keysw = 0;
       d->kw_full = false;
-      d->kidx_keys = 0;
-      d->kidx_left_out = 0;
-      d->kidx_failed = false;
-      d->kidx_on = ctx->opt.keys_index;             // the arena takes the option here
+      kidx_reset(d->kidx);
+      d->kidx.on = ctx->opt.keys_index;             // the arena takes the option here
     }
     // an earlier load that failed on a later device left this one's index ahead
     // of the arena (rows of keys no slot holds): no index until gv_keys_reset
-    if (d->kidx_keys > base) kidx_stop(d);
+    if (d->kidx.keys > base) kidx_stop(d, d->kidx);
     // the k6 tables too when their G tables exist (or can be built) and the
     // arena has room for them (else k4 only: the k4 route serves the slots)
     int rc = ensure_gtab4(ctx, d, s, st);
@@ -2925,9 +3015,9 @@ int gv_keys_load(gv_ctx* ctx, size_t n, const uint8_t* pub33, uint32_t* slot_out
     }
     // the pubkey index, while every earlier slot is in it: a refused
     // allocation or a failed launch only stops it on this device
-    if (ctx->opt.keys_index && d->kidx_on && !d->kidx_failed && d->kidx_keys == base) {
-      if (kidx_load(ctx, d, s, st, pub33, n, base) != GV_OK) kidx_stop(d);
-      else d->kidx_keys = base + n;
+    if (kidx_appendable(d->kidx, ctx->opt.keys_index, base)) {
+      if (kidx_load(ctx, d, s, st, pub33, n, base) != GV_OK) kidx_stop(d, d->kidx);
+      else d->kidx.keys = base + n;
     }
   }
   ctx->keys = base + n;
@@ -2986,11 +3076,12 @@ int gv_keys_replace(gv_ctx* ctx, size_t n, const uint32_t* slots, const uint8_t*
     // the index (whatever the option says now: its rows must not go stale):
     // the named slots' rows, then the table refilled from every row -- the
     // old bytes leave it, and the order of replacements does not matter
-    if (d->kidx_rows && d->kidx_keys && !d->kidx_failed) {
-      below(d->kidx_keys);
-      if ((!fs.empty() && kidx_write(ctx, d, s, st, fp.data(), fs.size(), 0, fs.data(), false) != GV_OK) ||
-          kidx_refill(ctx, d, d->kidx_keys, st) != GV_OK || kidx_read_left_out(d, st) != GV_OK)
-        kidx_stop(d);
+    if (d->kidx.filled()) {
+      below(d->kidx.keys);
+      if (!fs.empty() && kidx_write(ctx, d, s, st, fp.data(), fs.size(), 0, fs.data(), false) != GV_OK)
+        kidx_stop(d, d->kidx);
+      else
+        kidx_refilled(d, d->kidx, d->kidx.keys, st);
     }
   }
   ctx->keys_replaced.fetch_add(n);
@@ -3005,9 +3096,7 @@ int gv_keys_reset(gv_ctx* ctx) {
   ctx->keys_gen.fetch_add(1);
   for (Dev* d : ctx->devs) {                    // the index is empty with the arena; a stopped one may start again
     std::lock_guard<std::mutex> lk(d->mu);
-    d->kidx_keys = 0;
-    d->kidx_left_out = 0;
-    d->kidx_failed = false;
+    kidx_reset(d->kidx);
   }
   return GV_OK;
 }
@@ -3039,6 +3128,7 @@ int ensure_ed_keys(Dev* d, size_t need, size_t used, hipStream_t st, size_t cap_
   }
   for (uint32_t* q : {d->ektab, d->ekpub, d->ekok}) if (q) (void)hipFree(q);
   d->ektab = t; d->ekpub = p; d->ekok = o; d->ekcap = cap;
+  d->ed_kidx.rows = p;                          // (the index reads the arena's rows)
   return GV_OK;
 }
 
@@ -3150,96 +3240,31 @@ int ed_arena_quiesce(Dev* d) {
   return GV_OK;
 }
 
-// ---- the ed25519 arena's pubkey index (option "ed_keys_index"; gv_kidx.h at
-// GV_EDKIDX_ROW words).  Its rows are d->ekpub, which the
-// table builds write; the callers hold ed_keys_mu and d->mu and have waited
-// for edkd_last.
-constexpr size_t kEdKidxCntBytes = 256;
-
-void edkidx_free(Dev* d) {
-  opt_free(d, d->edkidx_tab, d->edkidx_T * 4);
-  d->edkidx_T = 0;
-}
-// No index on this device until gv_ed_keys_reset: every call takes the routes
-// it takes without one.
-void edkidx_stop(Dev* d) {
-  (void)hipGetLastError();
-  edkidx_free(d);
-  d->edkidx_failed = true;
-  d->edkidx_keys = 0;
-  d->edkidx_left_out = 0;
-}
-// The index covers the arena as it stands (an empty arena: every key misses).
-bool edkidx_live(const gv_ctx* ctx, const Dev* d) {
-  if (!ctx->opt.ed_keys_index || d->edkidx_failed || d->edkidx_keys != ctx->ed_keys) return false;
-  return ctx->ed_keys == 0 || (d->edkidx_on && d->edkidx_tab);
-}
-
-// Empty the table and enter slots [0, count) from their ekpub rows.
-int edkidx_refill(gv_ctx* ctx, Dev* d, size_t count, hipStream_t st) {
-  CK(hipMemsetAsync(d->edkidx_tab, 0xFF, d->edkidx_T * 4, st));
-  CK(hipMemsetAsync(d->edkidx_cnt, 0, 4, st));
-  if (count) {
-    CK(gvk_edkidx_put(d->edkidx_tab, (uint32_t)d->edkidx_T, d->ekpub, (uint32_t)count, 0, nullptr, ctx->opt.ed_kidx_seed,
-                      d->edkidx_cnt, st));
-    ctx->edkidx_launches++;
-  }
-  return GV_OK;
-}
-
-int edkidx_read_left_out(Dev* d, hipStream_t st) {
-  CK(hipMemcpyAsync(d->edkidx_h + 8, d->edkidx_cnt, 4, hipMemcpyDeviceToHost, st));
-  CK(hipStreamSynchronize(st));
-  d->edkidx_left_out = d->edkidx_h[8];
-  return GV_OK;
-}
-
-// After a load has written the rows of slots [base, base + n): the table for
-// the arena's capacity (d->ekcap), charged to the HBM budget like the other
-// optional tables, and the new slots into it.  A table that had to grow, and
-// one of an arena restarted from slot 0, is filled from every row.
-int edkidx_load(gv_ctx* ctx, Dev* d, hipStream_t st, size_t n, size_t base) {
-  if (!d->edkidx_cnt) {
-    if (!(d->edkidx_cnt = opt_alloc(ctx, d, kEdKidxCntBytes))) return GV_ENOMEM;
-    CK(hipMemsetAsync(d->edkidx_cnt, 0, kEdKidxCntBytes, st));
-  }
-  if (!d->edkidx_h && hipHostMalloc((void**)&d->edkidx_h, 64, hipHostMallocDefault) != hipSuccess) {
-    d->edkidx_h = nullptr;
-    return GV_ENOMEM;
-  }
+// gv_ed_keys_load's part of the pubkey index (option "ed_keys_index"; DESIGN
+// section 4.3e), after the load has written the ekpub rows of slots [base,
+// base + n): the table for the arena's capacity (d->ekcap), charged to the HBM
+// budget like the other optional tables, and the new slots into it.  A table
+// that had to grow, and one of an arena restarted from slot 0, is filled from
+// every row.
+int ed_kidx_load(gv_ctx* ctx, Dev* d, hipStream_t st, size_t n, size_t base) {
+  KeyIndex& ix = d->ed_kidx;
+  int rc;
+  if ((rc = kidx_setup(ctx, d, ix, st))) return rc;
   const size_t T = kidx_table_words(d->ekcap);
   if (T > (size_t(1) << 31)) return GV_ENOMEM;
-  int rc;
-  if (!d->edkidx_tab || d->edkidx_T < T) {
+  if (!ix.tab || ix.T < T) {
     uint32_t* tab = opt_alloc(ctx, d, T * 4);
     if (!tab) return GV_ENOMEM;
-    edkidx_free(d);
-    d->edkidx_tab = tab;
-    d->edkidx_T = T;
-    if ((rc = edkidx_refill(ctx, d, base + n, st))) return rc;
+    kidx_free(d, ix);
+    ix.tab = tab;
+    ix.T = T;
+    if ((rc = kidx_refill(ix, base + n, st))) return rc;
   } else if (base == 0) {
-    if ((rc = edkidx_refill(ctx, d, n, st))) return rc;
+    if ((rc = kidx_refill(ix, n, st))) return rc;
   } else {
-    CK(gvk_edkidx_put(d->edkidx_tab, (uint32_t)d->edkidx_T, d->ekpub, (uint32_t)n, (uint32_t)base, nullptr,
-                      ctx->opt.ed_kidx_seed, d->edkidx_cnt, st));
-    ctx->edkidx_launches++;
+    CK(kidx_put(ix, n, base, nullptr, st));
   }
-  return edkidx_read_left_out(d, st);
-}
-
-// The slots of a pub32 device batch (n items, device AoS) into `out` (n
-// words): k_edkidx_find on st, then one 4-byte read-back of the miss count and
-// a sync, as kidx_lookup.  *nmiss: the items whose key was not found.
-int edkidx_lookup(gv_ctx* ctx, Dev* d, size_t n, const uint8_t* pub, uint32_t* out, hipStream_t st, size_t* nmiss) {
-  uint32_t* miss = d->edkidx_cnt + 16;
-  CK(hipMemsetAsync(miss, 0, 4, st));
-  CK(gvk_edkidx_find(d->edkidx_tab, (uint32_t)d->edkidx_T, d->ekpub, (uint32_t)ctx->ed_keys, ctx->opt.ed_kidx_seed, pub,
-                     (uint32_t)n, out, miss, st));
-  ctx->edkidx_launches++;
-  CK(hipMemcpyAsync(d->edkidx_h, miss, 4, hipMemcpyDeviceToHost, st));
-  CK(hipStreamSynchronize(st));
-  *nmiss = *d->edkidx_h;
-  return GV_OK;
+  return kidx_read_left_out(ix, st);
 }
 }  // namespace
 
@@ -3263,14 +3288,12 @@ int gv_ed_keys_load(gv_ctx* ctx, size_t n, const uint8_t* pub32, uint32_t* slot_
         free_ed_keys_wide(d);
         d->ekw_rb = ctx->opt.ed_keys_wide;
       }
-      d->edkidx_keys = 0;
-      d->edkidx_left_out = 0;
-      d->edkidx_failed = false;
-      d->edkidx_on = ctx->opt.ed_keys_index;        // the arena takes the option here
+      kidx_reset(d->ed_kidx);
+      d->ed_kidx.on = ctx->opt.ed_keys_index;       // the arena takes the option here
     }
     // an earlier load that failed on a later device left this one's index ahead
     // of the arena (slots the count does not cover): no index until gv_ed_keys_reset
-    if (d->edkidx_keys > base) edkidx_stop(d);
+    if (d->ed_kidx.keys > base) kidx_stop(d, d->ed_kidx);
     rc = ensure_ed_keys(d, base + n, base, st, ctx->opt.ed_key_cap);
     if (!rc) rc = ed_build(ctx, d, st, pub32, n, base, nullptr);
     if (rc) return rc;
@@ -3289,9 +3312,9 @@ int gv_ed_keys_load(gv_ctx* ctx, size_t n, const uint8_t* pub32, uint32_t* slot_
     // the index, behind the builds that wrote the slots' ekpub rows (the wide
     // chain rewrites them with the same words); a refusal or a failure stops
     // it until gv_ed_keys_reset: never an error
-    if (ctx->opt.ed_keys_index && d->edkidx_on && !d->edkidx_failed && d->edkidx_keys == base) {
-      if (edkidx_load(ctx, d, st, n, base) != GV_OK) edkidx_stop(d);
-      else d->edkidx_keys = base + n;
+    if (kidx_appendable(d->ed_kidx, ctx->opt.ed_keys_index, base)) {
+      if (ed_kidx_load(ctx, d, st, n, base) != GV_OK) kidx_stop(d, d->ed_kidx);
+      else d->ed_kidx.keys = base + n;
     }
   }
   ctx->ed_kpub.insert(ctx->ed_kpub.end(), pub32, pub32 + n * 32);
@@ -3319,14 +3342,12 @@ int gv_ed_keys_replace(gv_ctx* ctx, size_t n, const uint32_t* slots, const uint8
     if (!rc) rc = ed_build(ctx, d, d->set[0].st, pub32, n, 0, slots);
     // the index names bytes: once rows may have changed it is refilled from
     // every row or stopped, whatever "ed_keys_index" says now
-    const bool indexed = d->edkidx_tab && d->edkidx_keys && !d->edkidx_failed;
+    const bool indexed = d->ed_kidx.filled();
     if (rc) {
-      if (indexed) edkidx_stop(d);
+      if (indexed) kidx_stop(d, d->ed_kidx);
       return rc;
     }
-    if (indexed && (edkidx_refill(ctx, d, std::min(d->edkidx_keys, count), d->set[0].st) != GV_OK ||
-                    edkidx_read_left_out(d, d->set[0].st) != GV_OK))
-      edkidx_stop(d);
+    if (indexed) kidx_refilled(d, d->ed_kidx, std::min(d->ed_kidx.keys, count), d->set[0].st);
     if (d->ektabw && d->ekeysw) {               // the wide tables of the named slots that have them
       const uint32_t* sl = slots;
       const uint8_t* pb = pub32;
@@ -3390,9 +3411,7 @@ int gv_ed_keys_reset(gv_ctx* ctx) {
     std::lock_guard<std::mutex> lk(d->mu);
     d->ekeysw = 0;
     d->ekw_full = false;
-    d->edkidx_keys = 0;                           // the index too (its table is cleared by the next load from slot 0)
-    d->edkidx_left_out = 0;
-    d->edkidx_failed = false;
+    kidx_reset(d->ed_kidx);                       // the index too
   }
   ctx->ed_keys_gen.fetch_add(1);
   return GV_OK;
@@ -3560,7 +3579,7 @@ int gv_verify_ed25519_msgs_keyed(gv_ctx* ctx, size_t n, const uint32_t* slot, co
 // and d->mu: gv_dev_verify_ed25519_msgs_keyed with the caller's d_slot, and
 // gv_dev_verify_ed25519_msgs (option "ed_keys_index") with d_slot null and the
 // batch's d_pub32 -- the slots are then looked up into the same scratch, n
-// words behind the sort's, by one k_edkidx_find ordered behind edkd_last like
+// words behind the sort's, by one k_kidx_find ordered behind edkd_last like
 // every other user of it, and the host waits for the miss count.  Any miss:
 // *missed is set and nothing else was enqueued (the caller takes the pub32
 // route).  kcount > 0.
@@ -3584,7 +3603,7 @@ int ed_dev_keyed(gv_ctx* ctx, Dev* d, size_t n, size_t kcount, const uint32_t* d
   if (!d_slot) {
     uint32_t* found = (uint32_t*)(d->edkd_s + C + sw * 4);
     size_t nmiss = 0;
-    if ((rc = edkidx_lookup(ctx, d, n, d_pub32, found, st, &nmiss))) return rc;
+    if ((rc = kidx_lookup(d->ed_kidx, ctx->ed_keys, n, d_pub32, found, st, &nmiss, nullptr))) return rc;
     if (nmiss) {
       *missed = true;
       return GV_OK;
@@ -3655,12 +3674,12 @@ int gv_dev_verify_ed25519_msgs(gv_ctx* ctx, int dev_slot, size_t n, const void* 
   CK(hipSetDevice(d->id));
   hipStream_t st = stream ? (hipStream_t)stream : d->set[0].st;
   order_after_pipeline(d, st);
-  if (kl.owns_lock() && ctx->opt.ed_keys_index && ctx->ed_keys && ctx->ed_keys <= d->ekcap && edkidx_live(ctx, d)) {
+  if (kl.owns_lock() && ctx->opt.ed_keys_index && ctx->ed_keys && ctx->ed_keys <= d->ekcap && ed_kidx_live(ctx, d)) {
     bool missed = false;
     if ((rc = ed_dev_keyed(ctx, d, n, ctx->ed_keys, nullptr, (const uint8_t*)d_pub32, d_sig64, d_msg_blob, d_msg_off,
                            d_msg_len, d_bits, st, &missed)))
       return rc;
-    (missed ? ctx->edkidx_miss : ctx->edkidx_hit)++;
+    (missed ? ctx->ed_kidx_stat.miss : ctx->ed_kidx_stat.hit)++;
     if (!missed) return GV_OK;
   }
   return ed_launch(ctx->opt.time_kernels, d, n, (const uint8_t*)d_pub32, (const uint8_t*)d_sig64, (const uint8_t*)d_msg_blob,
@@ -3674,26 +3693,8 @@ int gv_ed_keys_find(gv_ctx* ctx, size_t n, const uint8_t* pub32, uint32_t* slot_
   std::lock_guard<std::mutex> kl(ctx->ed_keys_mu);
   Dev* d = ctx->devs[0];
   std::lock_guard<std::mutex> lk(d->mu);
-  if (!edkidx_live(ctx, d)) return GV_EINVAL;   // cannot tell (not: not resident)
-  if (ctx->ed_keys == 0) {
-    memset(slot_out, 0xFF, n * 4);
-    return GV_OK;
-  }
-  CK(hipSetDevice(d->id));
-  hipStream_t st = d->set[0].st;
-  uint8_t* buf = nullptr;
-  const size_t pb = round_up(n * 32, 256);
-  if (hipMalloc(&buf, pb + n * 4) != hipSuccess) return GV_ENOMEM;
-  int rc = GV_OK;
-  if (hipMemcpyAsync(buf, pub32, n * 32, hipMemcpyHostToDevice, st) != hipSuccess ||
-      gvk_edkidx_find(d->edkidx_tab, (uint32_t)d->edkidx_T, d->ekpub, (uint32_t)ctx->ed_keys, ctx->opt.ed_kidx_seed, buf,
-                      (uint32_t)n, (uint32_t*)(buf + pb), nullptr, st) != hipSuccess ||
-      hipMemcpyAsync(slot_out, buf + pb, n * 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
-      hipStreamSynchronize(st) != hipSuccess)
-    rc = GV_EHIP;
-  ctx->edkidx_launches++;
-  (void)hipFree(buf);
-  return rc;
+  if (!ed_kidx_live(ctx, d)) return GV_EINVAL;   // cannot tell (not: not resident)
+  return kidx_find_host(d, d->ed_kidx, ctx->ed_keys, n, pub32, slot_out);
 }
 
 // Asynchronous on `stream`: the lookup reads the table and the arena's rows,
@@ -3707,7 +3708,7 @@ int gv_dev_ed_keys_find(gv_ctx* ctx, int dev_slot, size_t n, const void* d_pub32
   Dev* d = ctx->devs[dev_slot];
   std::lock_guard<std::mutex> kl(ctx->ed_keys_mu);
   std::lock_guard<std::mutex> lk(d->mu);
-  if (!edkidx_live(ctx, d)) return GV_EINVAL;
+  if (!ed_kidx_live(ctx, d)) return GV_EINVAL;
   CK(hipSetDevice(d->id));
   hipStream_t st = stream ? (hipStream_t)stream : d->set[0].st;
   order_after_pipeline(d, st);
@@ -3717,9 +3718,8 @@ int gv_dev_ed_keys_find(gv_ctx* ctx, int dev_slot, size_t n, const void* d_pub32
   }
   if (!d->edkd_last) CK(hipEventCreateWithFlags(&d->edkd_last, hipEventDisableTiming));
   if (d->edkd_last_st && d->edkd_last_st != st) CK(hipStreamWaitEvent(st, d->edkd_last, 0));
-  CK(gvk_edkidx_find(d->edkidx_tab, (uint32_t)d->edkidx_T, d->ekpub, (uint32_t)ctx->ed_keys, ctx->opt.ed_kidx_seed,
-                     (const uint8_t*)d_pub32, (uint32_t)n, (uint32_t*)d_slot_out, nullptr, st));
-  ctx->edkidx_launches++;
+  CK(kidx_find(d->ed_kidx, ctx->ed_keys, (const uint8_t*)d_pub32, n, (uint32_t*)d_slot_out, nullptr, st));
+  ctx->ed_kidx_stat.launches++;
   CK(hipEventRecord(d->edkd_last, st));
   d->edkd_last_st = st;
   return GV_OK;
@@ -3908,25 +3908,7 @@ int gv_keys_find(gv_ctx* ctx, size_t n, const uint8_t* pub33, uint32_t* slot_out
   Dev* d = ctx->devs[0];
   std::lock_guard<std::mutex> lk(d->mu);
   if (!kidx_live(ctx, d)) return GV_EINVAL;     // cannot tell (not: not resident)
-  if (ctx->keys == 0) {
-    memset(slot_out, 0xFF, n * 4);
-    return GV_OK;
-  }
-  CK(hipSetDevice(d->id));
-  hipStream_t st = d->set[0].st;
-  uint8_t* buf = nullptr;
-  const size_t pb = round_up(n * 33, 256);
-  if (hipMalloc(&buf, pb + n * 4) != hipSuccess) return GV_ENOMEM;
-  int rc = GV_OK;
-  if (hipMemcpyAsync(buf, pub33, n * 33, hipMemcpyHostToDevice, st) != hipSuccess ||
-      gvk_kidx_find(d->kidx_tab, (uint32_t)d->kidx_T, d->kidx_rows, (uint32_t)ctx->keys, ctx->opt.kidx_seed, buf,
-                    (uint32_t)n, (uint32_t*)(buf + pb), nullptr, st) != hipSuccess ||
-      hipMemcpyAsync(slot_out, buf + pb, n * 4, hipMemcpyDeviceToHost, st) != hipSuccess ||
-      hipStreamSynchronize(st) != hipSuccess)
-    rc = GV_EHIP;
-  ctx->kidx_launches++;
-  (void)hipFree(buf);
-  return rc;
+  return kidx_find_host(d, d->kidx, ctx->keys, n, pub33, slot_out);
 }
 
 int gv_dev_keys_find(gv_ctx* ctx, int dev_slot, size_t n, const void* d_pub33, void* d_slot_out, void* stream) {
@@ -3952,9 +3934,8 @@ int gv_dev_keys_find(gv_ctx* ctx, int dev_slot, size_t n, const void* d_pub33, v
       }
       return GV_OK;
     }
-    CK(gvk_kidx_find(d->kidx_tab, (uint32_t)d->kidx_T, d->kidx_rows, (uint32_t)ctx->keys, ctx->opt.kidx_seed,
-                     (const uint8_t*)d_pub33, (uint32_t)n, (uint32_t*)d_slot_out, nullptr, st));
-    ctx->kidx_launches++;
+    CK(kidx_find(d->kidx, ctx->keys, (const uint8_t*)d_pub33, n, (uint32_t*)d_slot_out, nullptr, st));
+    ctx->kidx_stat.launches++;
     if (!stream) {
       CK(hipEventRecord(d->kidx_found, st));
       d->kidx_found_used = true;
@@ -3989,6 +3970,27 @@ int gv_dev_verify_digests_keyed(gv_ctx* ctx, int dev_slot, size_t n, const void*
   return dev_launch(ctx, d, stream, it, d_bits);
 }
 
+namespace {
+// gv_get_option's rows of a pubkey index, by the name behind "keys_index_" /
+// "ed_keys_index_".  Of the context: batches routed keyed, batches that fell
+// through on a miss, k_kidx_* launches so far (false: not one of the three).
+bool kidx_stat_option(const KeyIndexStats& st, const char* name, long long* val) {
+  const std::atomic<uint64_t>* c = !strcmp(name, "hit") ? &st.hit : !strcmp(name, "miss") ? &st.miss
+                                   : !strcmp(name, "launches") ? &st.launches : nullptr;
+  if (c) *val = (long long)c->load();
+  return c != nullptr;
+}
+// Of the first device, under the arena's locks: whether the index covers the
+// arena (`live`), the slots in it, the keys its probe bound left out, its table
+// words -- 0 each without a table or after a stop.
+const char* const kKidxDevOptions[] = {"live", "keys", "left_out", "words"};
+long long kidx_dev_option(const KeyIndex& ix, bool live, const char* name) {
+  if (!strcmp(name, "live")) return live;
+  if (!ix.tab || ix.failed) return 0;
+  return (long long)(!strcmp(name, "keys") ? ix.keys : !strcmp(name, "left_out") ? ix.left_out : ix.T);
+}
+}  // namespace
+
 int gv_get_option(gv_ctx* ctx, const char* key, long long* val) {
   if (!ctx || !key || !val) return GV_EINVAL;
   if (const gvopt::Row* r = gvopt::opt_find(key)) {   // the tunables (gv_options.h)
@@ -3996,20 +3998,16 @@ int gv_get_option(gv_ctx* ctx, const char* key, long long* val) {
     *val = gvopt::opt_read(ctx->opt, *r);
     return GV_OK;
   }
-  // read-only live values
+  // read-only live values: an index's, under the same names for both arenas
+  const bool edi = !strncmp(key, "ed_keys_index_", 14);
+  const char* const iname = edi ? key + 14 : !strncmp(key, "keys_index_", 11) ? key + 11 : nullptr;
+  if (iname && kidx_stat_option(edi ? ctx->ed_kidx_stat : ctx->kidx_stat, iname, val)) return GV_OK;
   const struct {
     const char* k;
     long long v;
   } live[] = {{"keys_replaced", (long long)ctx->keys_replaced.load()},   // gv_keys_replace's slots so far
               {"ed_keys_replaced", (long long)ctx->ed_keys_replaced.load()},   // the same for gv_ed_keys_replace
               {"ed_keyed_wide", (long long)ctx->ed_keyed_wide.load()},   // keyed batches / chunks on wide tables
-              {"keys_index_hit", (long long)ctx->kidx_hit.load()},     // pub33 device batches routed keyed
-              {"keys_index_miss", (long long)ctx->kidx_miss.load()},   // ... that fell through on a miss
-              {"keys_index_launches", (long long)ctx->kidx_launches.load()},   // k_kidx_* launches so far
-              // the same three for the ed25519 arena's index ("ed_keys_index"): pub32 device batches
-              {"ed_keys_index_hit", (long long)ctx->edkidx_hit.load()},
-              {"ed_keys_index_miss", (long long)ctx->edkidx_miss.load()},
-              {"ed_keys_index_launches", (long long)ctx->edkidx_launches.load()},
               // routed batches whose non-resident items were split off ("keys_index_split"), and those items
               {"keys_index_split_calls", (long long)ctx->kidx_split_calls.load()},
               {"keys_index_split_items", (long long)ctx->kidx_split_items.load()},
@@ -4029,34 +4027,30 @@ int gv_get_option(gv_ctx* ctx, const char* key, long long* val) {
       return GV_OK;
     }
   // the first device's wide arena as gv_keys_load left it -- its window width
-  // (0: no slot has wide tables) and its groups; its pubkey index -- whether
-  // it covers the arena, the slots in it, the keys its probe bound left out,
-  // its table words; its wide ed25519 arena as gv_ed_keys_load left it -- its
+  // (0: no slot has wide tables) and its groups; its pubkey indexes
+  // (kidx_dev_option); its wide ed25519 arena as gv_ed_keys_load left it -- its
   // radix bits (0: no slot has wide tables) and the slots that have them;
   // whether it holds a built radix-2^16 comb table of B ("ed_btab16_live":
   // 0 also when the build failed and k_ed_keyed adds [s]B from the radix-256
   // table; reading it never builds the table)
-  // ... and its pubkey index, under the same four names behind "ed_"
-  const bool edi = !strncmp(key, "ed_keys_index_", 14);
+  const bool idx = iname && std::any_of(std::begin(kKidxDevOptions), std::end(kKidxDevOptions),
+                                        [&](const char* k) { return !strcmp(iname, k); });
   const bool ed = !strcmp(key, "ed_kw_rb") || !strcmp(key, "ed_kw_keys") || edi;
-  static const char* const kDev[] = {"kw_arena_qw", "kw_arena_ng", "keys_index_live", "keys_index_keys",
-                                     "keys_index_left_out", "keys_index_words", "group_reuse_rows", "group_layout",
+  static const char* const kDev[] = {"kw_arena_qw", "kw_arena_ng", "group_reuse_rows", "group_layout",
                                      "hbm_optional_bytes", "ed_btab16_live"};
-  static const char* const kEdIdx[] = {"ed_keys_index_live", "ed_keys_index_keys", "ed_keys_index_left_out",
-                                       "ed_keys_index_words"};
-  if (edi && std::none_of(std::begin(kEdIdx), std::end(kEdIdx), [&](const char* k) { return !strcmp(key, k); }))
-    return GV_EINVAL;
-  if (!ed && std::none_of(std::begin(kDev), std::end(kDev), [&](const char* k) { return !strcmp(key, k); }))
+  if (edi && !idx) return GV_EINVAL;
+  if (!ed && !idx && std::none_of(std::begin(kDev), std::end(kDev), [&](const char* k) { return !strcmp(key, k); }))
     return GV_EINVAL;
   if (ctx->devs.empty()) return GV_EINVAL;
   std::unique_lock<std::mutex> kl;
   if (ed) kl = std::unique_lock<std::mutex>(ctx->ed_keys_mu);
   Dev* d = ctx->devs[0];
   std::lock_guard<std::mutex> lk(d->mu);
-  const bool kw = d->kw.qt && d->keysw, has = d->kidx_tab && !d->kidx_failed, ekw = d->ektabw && d->ekeysw;
-  const bool ehas = d->edkidx_tab && !d->edkidx_failed;
+  const bool kw = d->kw.qt && d->keysw, ekw = d->ektabw && d->ekeysw;
   // (the row capacity of the first scratch set's grouping arena; 0: none yet)
-  *val = !strcmp(key, "group_reuse_rows")      ? (long long)d->set[0].gk.cap
+  *val = idx                                   ? kidx_dev_option(edi ? d->ed_kidx : d->kidx,
+                                                                 edi ? ed_kidx_live(ctx, d) : kidx_live(ctx, d), iname)
+         : !strcmp(key, "group_reuse_rows")    ? (long long)d->set[0].gk.cap
          // groups per key of the device's last grouped call (4: k4's and k6's layouts; 0: none yet); the
          // bytes of optional tables the HBM budget counts on the device
          : !strcmp(key, "group_layout")        ? (long long)d->group_layout
@@ -4064,14 +4058,6 @@ int gv_get_option(gv_ctx* ctx, const char* key, long long* val) {
          : !strcmp(key, "ed_btab16_live")      ? (long long)(d->edtab16 ? 1 : 0)
          : !strcmp(key, "kw_arena_qw")         ? (kw ? d->kw.lay.qw() : 0)
          : !strcmp(key, "kw_arena_ng")         ? (kw ? (int)d->kw.lay.ng : 0)
-         : !strcmp(key, "keys_index_live")     ? (long long)kidx_live(ctx, d)
-         : !strcmp(key, "keys_index_keys")     ? (long long)(has ? d->kidx_keys : 0)
-         : !strcmp(key, "keys_index_left_out") ? (long long)(has ? d->kidx_left_out : 0)
-         : !strcmp(key, "keys_index_words")    ? (long long)(has ? d->kidx_T : 0)
-         : !strcmp(key, "ed_keys_index_live")     ? (long long)edkidx_live(ctx, d)
-         : !strcmp(key, "ed_keys_index_keys")     ? (long long)(ehas ? d->edkidx_keys : 0)
-         : !strcmp(key, "ed_keys_index_left_out") ? (long long)(ehas ? d->edkidx_left_out : 0)
-         : !strcmp(key, "ed_keys_index_words")    ? (long long)(ehas ? d->edkidx_T : 0)
          : !strcmp(key, "ed_kw_rb")            ? (ekw ? d->ekw_rb : 0)
                                                : (long long)(ekw ? d->ekeysw : 0);
   return GV_OK;

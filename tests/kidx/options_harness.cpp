@@ -2,7 +2,7 @@
 // a program of its own.  Prints one "name = value(s)" line per case;
 // tests/test_ed_keys_index_host.py holds the expected numbers.  Test
 // infrastructure only.
-//   g++ -std=c++17 -Icosmos-sdk-rootchain_amd/csrc tests/edkidx/options_harness.cpp
+//   g++ -std=c++17 -Icosmos-sdk-rootchain_amd/csrc tests/kidx/options_harness.cpp
 #include <cstdio>
 #include <initializer_list>
 

@@ -7,22 +7,27 @@ gv_dev_verify_ed25519_msgs_keyed would (include/gpuverify.h, DESIGN section
 Expectations come from outside the code under test: oracle/ed25519_ref.py
 (verdicts, point decoding), tests/ed_openssl.py (signing),
 tests/golden/ed25519_vectors.json (every rejection class), the host model
-(tests/edkidx_model.py over tools/fe29/edkidx_host.cpp) and the load order.
+(tests/kidx_model.py at 8-word rows, over tools/fe29/kidx_host.cpp) and the
+load order.
 Bitmaps are compared for equality."""
 import ctypes
 import json
 import os
 import random
+from functools import partial
 
 import numpy as np
 import pytest
 
 import ed_openssl as OSSL
 import gpuverify as gvm
-from edkidx_model import SEED, Model, homed_keys, load_model
+import kidx_model
+from kidx_model import SEED, load_model
 from oracle import ed25519_ref as E
 
 pytestmark = pytest.mark.gpu
+Model = partial(kidx_model.Model, row=8)                 # the ed25519 arena's rows
+homed_keys = partial(kidx_model.homed_keys, row=8)
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 NONE = 0xFFFFFFFF
 ED_LAT_MAX = 2048                       # the option's default

@@ -1,6 +1,6 @@
 """The ed25519 key arena's pubkey index on the CPU (no GPU): the exact device
 source (csrc/gv_kidx.h at 8-word rows -- hash, probe sequence, insert, lookup
--- built by g++ through tools/fe29/edkidx_host.cpp) against the load order:
+-- built by g++ through tools/fe29/kidx_host.cpp) against the load order:
 every resident key is found at its lowest slot, nothing is ever found at a
 slot with other bytes, the probe wraps at the table's end and stops at
 GV_KIDX_PROBE.  The 9-word routines of the secp256k1 index give the home
@@ -8,19 +8,22 @@ words they gave before they became instances of the R-word templates
 (tests/golden/kidx_home_parent.json), the option rows stand where
 tests/golden/options_parent.json lets them, and the same scenarios run once
 more as a program of their own under ASan + UBSan
-(tests/edkidx/edkidx_harness.cpp)."""
+(tests/kidx/kidx_harness.cpp)."""
 import json
 import os
 import subprocess
 import tempfile
+from functools import partial
 
 import numpy as np
 import pytest
 
 import kidx_model
-from edkidx_model import NONE, SEED, Model, _p, homed_keys, load_model, table_words
+from kidx_model import NONE, SEED, _p, load_model, table_words
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+Model = partial(kidx_model.Model, row=8)                 # the ed25519 arena's rows
+homed_keys = partial(kidx_model.homed_keys, row=8)
 SAN = ["-fno-omit-frame-pointer", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"]
 
 
@@ -220,7 +223,7 @@ def test_option_rows(flags):
     exe = os.path.join(tempfile.mkdtemp(), "edkidx_options")
     subprocess.run(["g++", "-O1", "-g", "-std=c++17", "-Wall", "-Wno-unused-function", *flags,
                     "-I" + os.path.join(REPO, "cosmos-sdk-rootchain_amd", "csrc"),
-                    os.path.join(REPO, "tests", "edkidx", "options_harness.cpp"), "-o", exe], check=True)
+                    os.path.join(REPO, "tests", "kidx", "options_harness.cpp"), "-o", exe], check=True)
     r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
     out = r.stdout + r.stderr
     assert r.returncode == 0 and out.rstrip().endswith("options ok"), out
@@ -239,8 +242,8 @@ def test_new_rows_are_not_in_the_recorded_table():
 
 # ---------------------------------------------------------------- sanitizers (host code, a program of its own)
 def test_the_same_scenarios_under_asan_and_ubsan_as_a_program():
-    exe = os.path.join(tempfile.mkdtemp(), "edkidx_harness")
-    subprocess.run(["g++", "-O1", "-g", "-std=c++17", *SAN, os.path.join(REPO, "tests", "edkidx", "edkidx_harness.cpp"),
+    exe = os.path.join(tempfile.mkdtemp(), "kidx_harness")
+    subprocess.run(["g++", "-O1", "-g", "-std=c++17", *SAN, os.path.join(REPO, "tests", "kidx", "kidx_harness.cpp"),
                     "-o", exe], check=True)
     r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
     out = r.stdout + r.stderr

@@ -138,7 +138,7 @@ def test_the_same_scenarios_under_asan_and_ubsan_as_a_program():
                     "-o", exe], check=True)
     r = subprocess.run([exe], capture_output=True, text=True, timeout=120)
     out = r.stdout + r.stderr
-    assert r.returncode == 0 and "kidx ok" in out, out
+    assert r.returncode == 0 and "\nkidx ok" in "\n" + out, out
     assert "Sanitizer" not in out and "runtime error" not in out, out
 
 
