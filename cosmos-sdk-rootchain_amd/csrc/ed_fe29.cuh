@@ -10,7 +10,8 @@
 // F29_B = 2^29 + 2^18): mul needs mag(a) * mag(b) <= 6, sqr mag(a) <= 2,
 // add/sub results <= 7, e29_norm input <= 7; mul/sqr/norm outputs are
 // magnitude 1.  Checked by the host build's GV_F29_CHECK traps in
-// tests/test_ed_fe29_host.py.
+// tests/test_ed_host.py and, op by op at these bounds, in
+// tests/test_lane_host.py; on the device by tests/test_lane_gpu.py.
 #pragma once
 #include "secp_fe29.cuh"
 

@@ -3,6 +3,9 @@
 // source runs in tests/test_ed_host.py (g++, overflow traps) and in the
 // gfx950 kernels (ed_verify.hip).
 //
+// Each function at its operand bounds: tests/test_lane_host.py (host) and
+// tests/test_lane_gpu.py (device, k_debug_elane).
+//
 // Restates (go1.14 crypto/ed25519 + internal/edwards25519, the code
 // tendermint v0.33.4 PubKeyEd25519.VerifyBytes calls):
 //   ge_frombytes   ExtendedGroupElement.FromBytes (y = bytes mod 2^255, no

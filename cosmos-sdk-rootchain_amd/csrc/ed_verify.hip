@@ -22,6 +22,7 @@
 
 #include "ed_group.cuh"
 #include "gv_kernels.h"
+#include "ed_lane_ops.cuh"
 
 #if defined(__HIP_DEVICE_COMPILE__) && defined(__AMDGCN_WAVEFRONT_SIZE) && __AMDGCN_WAVEFRONT_SIZE != 64
 #error "ed_verify.hip writes one 64-bit ballot word per wave64"
@@ -103,8 +104,29 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3, 3))) voi
   if ((threadIdx.x & 63) == 0 && g < b.n) b.bits[g >> 6] = mask;   // words up to ceil(n / 64) only
 }
 
+// ------------------------------------------------------------- k_debug_elane
+// Test hook (gv_debug_lane_op, ops GV_LNOP_ED_*): one item per lane in 64-lane
+// blocks, tail lanes inactive, one function of the one-lane ed25519 layers
+// per item (ed_lane_ops.cuh).  atab: n x ED_ATAB_WORDS words of scratch,
+// lane-major as k_ed_prep lays it out (null unless the op is GV_LNOP_GE_ADD_TAB,
+// the one op that touches it).  out is zero on entry.
+__global__ __launch_bounds__(64) void k_debug_elane(int op, u32 n, const u32* in, u32* out, u32* atab) {
+  const u32 g = blockIdx.x * 64u + threadIdx.x;
+  if (g >= n) return;
+  lane_ed_op(op, in + (size_t)g * GV_LN_IN, out + (size_t)g * GV_LN_OUT, atab + (size_t)g * ED_ATAB_WORDS, 1);
+}
+
+static_assert(ED_ATAB_WORDS == GV_LN_ATAB_WORDS, "gv_debug_lane_op's table scratch");
+
 }  // namespace ed
 }  // namespace gv
+
+extern "C" hipError_t gvk_debug_elane(int op, uint32_t n, const uint32_t* in, uint32_t* out, uint32_t* atab,
+                                      hipStream_t st) {
+  if (n == 0) return hipSuccess;
+  hipLaunchKernelGGL(gv::ed::k_debug_elane, dim3((n + 63) / 64), dim3(64), 0, st, op, n, in, out, atab);
+  return hipGetLastError();
+}
 
 extern "C" hipError_t gvk_ed_btab(uint32_t* btab, hipStream_t st) {
   const int n = ED_BTAB_WINDOWS * ED_BTAB_ENTRIES;

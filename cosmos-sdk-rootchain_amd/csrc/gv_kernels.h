@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "gv_lane.h"
 
 #ifndef GV_GW
 #define GV_GW 20                // G / lambda*G signed window width (bits); multiple of GV_QW
@@ -574,6 +575,14 @@ enum {
 };
 hipError_t gvk_debug_sl(int op, uint32_t n, const uint32_t* in, uint32_t* out, hipStream_t st);    // gv_lat.hip
 hipError_t gvk_debug_esl(int op, uint32_t n, const uint32_t* in, uint32_t* out, hipStream_t st);   // ed_lat.hip
+// gv_debug_lane_op: the one-lane 9 x 29 layers, one item per lane (layout and
+// op codes GV_LNOP_*: gv_lane.h).  atab: n x GV_LN_ATAB_WORDS words of scratch
+// for the per-lane j(-A) table.
+#define GV_LN_ATAB_WORDS 324   // ED_ATAB_WORDS (ed_group.cuh): 9 cached entries of 36 words
+hipError_t gvk_debug_lane(int op, uint32_t n, const uint32_t* in, uint32_t* out, hipStream_t st);       // gv_kernels.hip
+hipError_t gvk_debug_lane_lat(int op, uint32_t n, const uint32_t* in, uint32_t* out, hipStream_t st);   // gv_lat.hip
+hipError_t gvk_debug_elane(int op, uint32_t n, const uint32_t* in, uint32_t* out, uint32_t* atab,
+                           hipStream_t st);                                                              // ed_verify.hip
 #if GV_STAMP
 hipError_t gvk_stamps_read(uint64_t* host, size_t n_u64);   // diagnostic builds (gv_kernels.hip GV_STAMP)
 #endif

@@ -34,6 +34,7 @@
 #include "secp_modinv.cuh"
 #include "secp_sha256.cuh"
 #include "gv_kernels.h"
+#include "secp_lane_ops.cuh"
 
 namespace gv {
 
@@ -2257,6 +2258,17 @@ __global__ void k_debug(int op, u32 n, const u32* in, u32* out) {
   }
 }
 
+// -------------------------------------------------------------- k_debug_lane
+// Test hook (gv_debug_lane_op in the C-ABI, secp256k1 ops below GV_LNOP_LAT):
+// one item per lane in 64-lane blocks, tail lanes inactive, one function of
+// the one-lane 9 x 29 layers per item (secp_lane_ops.cuh) as this unit builds
+// them: one mad chain per column.  out is zero on entry.
+__global__ __launch_bounds__(64) void k_debug_lane(int op, u32 n, const u32* in, u32* out) {
+  const u32 g = blockIdx.x * 64u + threadIdx.x;
+  if (g >= n) return;
+  lane_secp_op(op, in + (size_t)g * GV_LN_IN, out + (size_t)g * GV_LN_OUT);
+}
+
 }  // namespace gv
 
 // ------------------------------------------------------------- host launchers
@@ -2636,6 +2648,12 @@ hipError_t gvk_stamps_read(uint64_t* host, size_t n_u64) {
 
 hipError_t gvk_debug(int op, uint32_t n, const uint32_t* in, uint32_t* out, hipStream_t st) {
   hipLaunchKernelGGL(gv::k_debug, dim3((n + 255) / 256), dim3(256), 0, st, op, n, in, out);
+  return hipGetLastError();
+}
+
+hipError_t gvk_debug_lane(int op, uint32_t n, const uint32_t* in, uint32_t* out, hipStream_t st) {
+  if (n == 0) return hipSuccess;
+  hipLaunchKernelGGL(gv::k_debug_lane, dim3((n + 63) / 64), dim3(64), 0, st, op, n, in, out);
   return hipGetLastError();
 }
 

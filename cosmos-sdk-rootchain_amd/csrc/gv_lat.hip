@@ -37,6 +37,7 @@
 #include "secp_sha256.cuh"
 
 #include "gv_kernels.h"
+#include "secp_lane_ops.cuh"
 
 static_assert(F29_NCH == 2, "gv_lat.hip is built with -DF29_NCH=2");
 #if defined(__HIP_DEVICE_COMPILE__) && defined(__AMDGCN_WAVEFRONT_SIZE) && __AMDGCN_WAVEFRONT_SIZE != 64
@@ -1805,7 +1806,23 @@ __global__ __launch_bounds__(64) void k_debug_sl(int op, const u32* in, u32* out
   }
 }
 
+// ---------------------------------------------------------- k_debug_lane_lat
+// gv_kernels.hip's k_debug_lane (gv_debug_lane_op, ops GV_LNOP_LAT + c) with
+// the field layers as THIS unit builds them: two mad chains per column
+// (F29_NCH = F29X_NCH = 2), the code the k_verify_lat* kernels run.
+__global__ __launch_bounds__(64) void k_debug_lane_lat(int op, u32 n, const u32* in, u32* out) {
+  const u32 g = blockIdx.x * 64u + threadIdx.x;
+  if (g >= n) return;
+  lane_secp_op(op, in + (size_t)g * GV_LN_IN, out + (size_t)g * GV_LN_OUT);
+}
+
 }  // namespace gv
+
+extern "C" hipError_t gvk_debug_lane_lat(int op, uint32_t n, const uint32_t* in, uint32_t* out, hipStream_t st) {
+  if (n == 0) return hipSuccess;
+  hipLaunchKernelGGL(gv::k_debug_lane_lat, dim3((n + 63) / 64), dim3(64), 0, st, op, n, in, out);
+  return hipGetLastError();
+}
 
 extern "C" hipError_t gvk_debug_sl(int op, uint32_t n, const uint32_t* in, uint32_t* out, hipStream_t st) {
   if (n == 0) return hipSuccess;

@@ -4327,4 +4327,40 @@ int gv_debug_sl_op(gv_ctx* ctx, int dev_slot, int op, size_t n, const uint32_t* 
   return rc;
 }
 
+int gv_debug_lane_op(gv_ctx* ctx, int dev_slot, int op, size_t n, const uint32_t* in, uint32_t* out) {
+  if (!ctx || dev_slot < 0 || dev_slot >= (int)ctx->devs.size() || !in || !out) return GV_EINVAL;
+  const bool secp = op >= 0 && op < GV_LNOP_SECP_END;                                  // gv_kernels.hip: one chain
+  const bool lat = op >= GV_LNOP_LAT && op < GV_LNOP_LAT + GV_LNOP_SECP_END;           // gv_lat.hip: two chains
+  const bool ed = op >= GV_LNOP_ED_MUL && op < GV_LNOP_ED_END;
+  if (!secp && !lat && !ed) return GV_EINVAL;
+  if (n == 0) return GV_OK;
+  if (n > kMaxItems) return GV_EINVAL;
+  Dev* d = ctx->devs[dev_slot];
+  std::lock_guard<std::mutex> lk(d->mu);
+  CK(hipSetDevice(d->id));
+  hipStream_t st = d->set[0].st;
+  const size_t bin = n * GV_LN_IN * 4, bout = n * GV_LN_OUT * 4;
+  uint32_t *din = nullptr, *dout = nullptr, *atab = nullptr;
+  CK(hipMalloc(&din, bin));
+  if (hipMalloc(&dout, bout) != hipSuccess) { (void)hipFree(din); return GV_ENOMEM; }
+  if (op == GV_LNOP_GE_ADD_TAB && hipMalloc(&atab, n * GV_LN_ATAB_WORDS * 4) != hipSuccess) {
+    (void)hipFree(din);
+    (void)hipFree(dout);
+    return GV_ENOMEM;
+  }
+  int rc = GV_OK;
+  if (hipMemcpyAsync(din, in, bin, hipMemcpyHostToDevice, st) != hipSuccess ||
+      hipMemsetAsync(dout, 0, bout, st) != hipSuccess ||
+      (secp  ? gvk_debug_lane(op, (uint32_t)n, din, dout, st)
+       : lat ? gvk_debug_lane_lat(op - GV_LNOP_LAT, (uint32_t)n, din, dout, st)
+             : gvk_debug_elane(op, (uint32_t)n, din, dout, atab, st)) != hipSuccess ||
+      hipMemcpyAsync(out, dout, bout, hipMemcpyDeviceToHost, st) != hipSuccess ||
+      hipStreamSynchronize(st) != hipSuccess)
+    rc = GV_EHIP;
+  (void)hipFree(din);
+  (void)hipFree(dout);
+  if (atab) (void)hipFree(atab);
+  return rc;
+}
+
 }  // extern "C"

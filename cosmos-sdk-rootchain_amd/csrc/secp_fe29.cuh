@@ -18,7 +18,9 @@
 //
 // Magnitude m: every limb <= m * F29_B, F29_B = 2^29 + 2^18.  mul/sqr outputs
 // and f29_norm outputs have magnitude 1.  Limits (checked by the host build's
-// GV_F29_CHECK overflow traps and by tests/test_fe29_host.py):
+// GV_F29_CHECK overflow traps and by tests/test_fe29_host.py and
+// tests/test_lane_host.py; on the device, in both chain configurations, by
+// tests/test_lane_gpu.py):
 //   mul(a, b):   mag(a) * mag(b) <= 6          sqr(a):  mag(a) <= 2
 //   add/sub/neg: result magnitude <= 7 (limbs stay below 2^32)
 //   f29_norm:    input magnitude <= 7
@@ -157,7 +159,12 @@ GV_DEV void f29_mulsqr(fe29& r, const fe29& a, const fe29& b) {
   x = f29_mad(clo, kr1, x);
   x = f29_mad(chi, F29_RH1, x);
   o.n[1] = (u32)x & F29_M;
-  o.n[2] = f29_add32(o.n[2], f29_add32((u32)(x >> 29), chi * F29_RH2));
+  // chi reaches 192 at mag(a) * mag(b) = 6 (limb 17 < 6 * 2^29 * 1.001, times
+  // 256, over 2^32), so chi * F29_RH2 alone passes 2^18: limb 2 is carried
+  // once more into limb 3 (< 2^29 before), which keeps the output at magnitude 1
+  const u32 y = f29_add32(o.n[2], f29_add32((u32)(x >> 29), chi * F29_RH2));
+  o.n[2] = y & F29_M;
+  o.n[3] += y >> 29;
   r = o;
 }
 
@@ -252,7 +259,9 @@ GV_DEV void f29_multi(fe29* r, const fe29* a, const fe29* b) {
 #pragma unroll
   for (int s = 0; s < S; ++s) {
     o[s].n[1] = (u32)x[s] & F29_M;
-    o[s].n[2] = f29_add32(o[s].n[2], f29_add32((u32)(x[s] >> 29), chi[s] * F29_RH2));
+    const u32 y = f29_add32(o[s].n[2], f29_add32((u32)(x[s] >> 29), chi[s] * F29_RH2));
+    o[s].n[2] = y & F29_M;              // as in f29_mulsqr: limb 2 carried into limb 3
+    o[s].n[3] += y >> 29;
   }
 #pragma unroll
   for (int s = 0; s < S; ++s) r[s] = o[s];

@@ -22,7 +22,8 @@
 //    and the caller's 2a can double as another product's operand.
 //
 // Bounds (host build: GV_F29_CHECK traps every wrapping mad / add; tests/
-// test_fe29_host.py drives the extremes):
+// test_fe29x_host.py and tests/test_lane_host.py drive the extremes, tests/
+// test_lane_gpu.py the same operands on the device):
 //   mul: mag(a) * mag(b) <= 6           -> column sums <= 54 B^2 < 2^63.8
 //   sqr (dg, cr) = (a, 2a): mag(a) <= 2 (column 8: 9 m^2 B^2)
 //   sqr (dg, cr) = (3a, 6a): mag(a) <= 1 (column 8: 27 B^2)
@@ -130,7 +131,9 @@ GV_DEV void f29x_reduce(fe29& r, const u32 t[9], const LOW& lowterms, const EX& 
   x = f29_mad(clo, kr1, x);
   x = f29_mad(chi, F29_RH1, x);
   o.n[1] = (u32)x & F29_M;
-  o.n[2] = f29_add32(o.n[2], f29_add32((u32)(x >> 29), chi * F29_RH2));
+  const u32 y = f29_add32(o.n[2], f29_add32((u32)(x >> 29), chi * F29_RH2));
+  o.n[2] = y & F29_M;                         // as in f29_mulsqr: limb 2 carried into limb 3
+  o.n[3] += y >> 29;
   r = o;
 }
 

@@ -9,6 +9,8 @@
 // mag(a) * mag(b) <= 6, sqr mag <= 2, linear results <= 7).
 //
 // Point invariant between operations: X and Y magnitude 1, Z magnitude <= 2.
+// Each function at these bounds, with its exceptional branches: tests/
+// test_lane_host.py (host, traps on) and tests/test_lane_gpu.py (device).
 #pragma once
 #include "secp_fe29.cuh"
 

@@ -6,6 +6,8 @@
 // carry pass.  Magnitudes after each step in the comments.
 //
 // Point invariant between operations: X, Y, Z magnitude 1 (Z <= 2 accepted).
+// Checked at these bounds by tests/test_fe29x_host.py, tests/test_lane_host.py
+// (host, traps on) and tests/test_lane_gpu.py (device).
 #pragma once
 #include "secp_group29.cuh"
 #include "secp_fe29x.cuh"

@@ -49,7 +49,7 @@ EXPORTED_SYMBOLS = (
     "gv_ed_keys_replace", "gv_ed_keys_point", "gv_dev_verify_ed25519_msgs_keyed", "gv_ed_keys_wide_point",
     "gv_submit_digests", "gv_submit_digests_keyed", "gv_submit_msgs", "gv_submit_msgs_keyed", "gv_wait",
     "gv_keys_find", "gv_dev_keys_find", "gv_debug_sl_op", "gv_keys_entry", "gv_group_entry",
-    "gv_ed_keys_find", "gv_dev_ed_keys_find",
+    "gv_ed_keys_find", "gv_dev_ed_keys_find", "gv_debug_lane_op",
 )
 
 # gv_debug_sl_op (csrc/gv_kernels.h): words per item, flags, status words, op codes
@@ -64,6 +64,25 @@ SLOP.update({name: 64 + i for i, name in enumerate((
     "ed_mul", "ed_sqr", "ed_norm", "ed_sub", "ed_is_zero", "ed_to_words", "ed_from_words", "ed_pow22523",
     "ed_decode_strict", "ed_decode_lenient", "gesl_add_cached", "gesl_add_pre", "gesl_add", "ge4_double",
     "ge4_add_cached", "ge4_add", "ed_digits"))})
+
+# gv_debug_lane_op (csrc/gv_lane.h): the item layout of gv_debug_sl_op; secp256k1 op c runs in the
+# one-chain unit, c + LNOP_LAT in the two-chain unit
+LN_IN, LN_OUT = 80, 80
+LNF_NEG, LNF_NOT, LNF_INF_A, LNF_INF_B, LNF_WORDS, LNF_ENTRY_SHIFT = 1, 2, 4, 8, 16, 8
+LNS_FLAG, LNS_INF, LNS_KNOWN = 0, 1, 3
+LNOP_LAT = 64
+LNOP = {name: i for i, name in enumerate((
+    "mul", "sqr", "multi_ss", "multi_mmm", "multi_mm", "multi_ssm", "sub1", "neg1", "sub_norm1", "sub_norm2",
+    "sub_norm3", "shl_norm1", "shl_norm2", "shl_norm3", "mul3_norm", "norm", "to_words", "from_words", "is_zero",
+    "is_zero_fast", "equal", "inv", "sqrt", "x_mul", "x_mul_p1", "x_mul_p8", "x_mul2", "x_sqr", "x_sqrd_p1",
+    "x_sqrd_p8", "x_sqr3", "x_sqrt", "gej_double", "gej_add_ge", "gej_add_gej", "gejx_double", "gejx_add_scaled"))}
+LNOP_SECP_END = len(LNOP)
+LNOP.update({name: 128 + i for i, name in enumerate((
+    "ed_mul", "ed_sqr", "ed_sub1", "ed_neg1", "ed_sub_norm1", "ed_sub_norm2", "ed_sub_norm3", "ed_add_norm", "ed_norm",
+    "ed_to_words", "ed_from_words", "ed_is_zero", "ed_is_negative", "ed_inv", "ed_pow22523", "ge_dbl_t", "ge_dbl_nt",
+    "ge_add_cached", "ge_add_pre", "ge_to_cached", "ge_to_pre", "ge_neg", "ge_frombytes", "ge_tobytes", "ge_add_tab",
+    "sc_reduce512", "sc_minimal", "ed_radix16", "ed_comb4", "ed_comb6", "ed_comb8"))})
+LNOP_ED_END = 128 + len(LNOP) - LNOP_SECP_END
 
 
 class GpuVerifyError(RuntimeError):
@@ -142,6 +161,8 @@ def load(path: str = LIB_PATH):
     L.gv_debug_op.restype = i32
     L.gv_debug_sl_op.argtypes = [vp, i32, i32, sz, vp, vp]
     L.gv_debug_sl_op.restype = i32
+    L.gv_debug_lane_op.argtypes = [vp, i32, i32, sz, vp, vp]
+    L.gv_debug_lane_op.restype = i32
     L.gv_dev_alloc.argtypes = [vp, i32, sz, ctypes.POINTER(vp)]
     L.gv_dev_alloc.restype = i32
     L.gv_dev_free.argtypes = [vp, i32, vp]
@@ -835,6 +856,22 @@ class Verifier:
         out = np.zeros((n, SL_OUT), dtype=np.uint32)
         code = SLOP[op] if isinstance(op, str) else int(op)
         _check(self._L.gv_debug_sl_op(self._ctx, slot, code, n, _ptr(words), _ptr(out)), "gv_debug_sl_op")
+        return out
+
+    def debug_lane_op(self, op, words: np.ndarray, chains: int = 1, slot: int = 0) -> np.ndarray:
+        """One function of the one-lane 9 x 29 layers (LNOP name or code) per
+        item, one item per lane: words n x LN_IN -> n x LN_OUT, the layout of
+        debug_sl_op.  chains = 2 runs a secp256k1 op (given by name) in the
+        two-chain unit of the small-batch kernels."""
+        words = np.ascontiguousarray(words, dtype=np.uint32)
+        n = words.shape[0]
+        assert words.shape == (n, LN_IN) and chains in (1, 2)
+        out = np.zeros((n, LN_OUT), dtype=np.uint32)
+        code = LNOP[op] if isinstance(op, str) else int(op)
+        if chains == 2:
+            assert isinstance(op, str) and code < LNOP_SECP_END
+            code += LNOP_LAT
+        _check(self._L.gv_debug_lane_op(self._ctx, slot, code, n, _ptr(words), _ptr(out)), "gv_debug_lane_op")
         return out
 
 

@@ -850,6 +850,19 @@ int gv_debug_op(gv_ctx* ctx, int dev_slot, int op, size_t n, const uint32_t* in,
  * Used by the GPU unit tests only. */
 int gv_debug_sl_op(gv_ctx* ctx, int dev_slot, int op, size_t n, const uint32_t* in, uint32_t* out);
 
+/* Test hook for the one-lane 9 x 29 layers (secp_fe29.cuh, secp_fe29x.cuh,
+ * secp_group29.cuh, secp_group29x.cuh, ed_fe29.cuh, ed_group.cuh,
+ * ed_scalar.cuh): one item per lane, one function per item, in the item
+ * layout of gv_debug_sl_op.  in = n x 80 words: operand j's nine raw limbs at
+ * 9j..9j+8, j < 8, word 79 = flags (1 neg, 2 no T out, 4 / 8 first / second
+ * input at infinity, 16 words, not limbs, bits 8..11 the table entry of
+ * ge_add_tab).  out = n x 80 words: four result slots of 16 words, then 16
+ * status words (0 boolean result, 1 infinity out, 3 op known and run).
+ * Op codes: GV_LNOP_* in csrc/gv_lane.h; a secp256k1 op c runs in the
+ * one-chain unit, c + 64 in the two-chain unit of the small-batch kernels.
+ * GV_EINVAL for an unknown op.  Used by the GPU unit tests only. */
+int gv_debug_lane_op(gv_ctx* ctx, int dev_slot, int op, size_t n, const uint32_t* in, uint32_t* out);
+
 #ifdef __cplusplus
 }
 #endif
